@@ -17,6 +17,7 @@ other layout (`layouts`).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N            (no WORLD_SIZE in the environment: starts the N ranks itself, same launcher)
     python bench.py --config C3         (2 x 150 bp paired ends, -s5 -U3 -d200 -D400: SE pass + PE association per step)
+    python bench.py --dump-outputs DIR  (also writes the bk_hit records of the headline's last timed step, a seeded sample, as DIR/<field>.npy)
 
 Workload at N = 1: BASELINE.json configs[1] restated over a synthetic genome (SURVEY.md 8d "C2"):
 50 M x 100 bp SE reads, 0-3 substitutions, vs a 24-sequence 3.1 Gbp GRCh38-like genome, `-s3`.
@@ -545,6 +546,7 @@ class HostLeg:
                 st.wait(t)
             barrier()
             elapsed = time.time() - t_start
+            self.last_set = (steps - 1) % self.n_sets          # the set of result records the last timed step wrote
             stats = st.stats()
             tim = al.timing(reset=True)
         if all_reduce is not None:
@@ -565,6 +567,31 @@ class HostLeg:
     def same_as(self, expect, steps):
         import numpy as np
         return all(bool(np.array_equal(h.view(np.uint8), expect.view(np.uint8))) for h in self.h_out[: min(self.n_sets, steps)])
+
+
+DUMP_SAMPLE_READS = 1 << 19          # at most this many reads' records in a --dump-outputs directory (about 32 MB of arrays)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_hits(hits, out_dir):
+    """--dump-outputs: the bk_hit records a caller of the timed path receives, one array per field as <out_dir>/<field>.npy - a
+    fixed, seeded sample of the reads when there are more than DUMP_SAMPLE_READS (read_index.npy: which ones).  Fields of 32 bits
+    are written as float64, the narrower ones as float32, so that every value is exact."""
+    import numpy as np
+    n = len(hits)
+    if n > DUMP_SAMPLE_READS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=DUMP_SAMPLE_READS, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(out_dir, exist_ok=True)
+    sample = hits[idx]
+    arrays = {"read_index": idx.astype(np.float64)}
+    for f in hits.dtype.names:
+        arrays[f] = sample[f].astype(np.float64 if sample[f].dtype.itemsize >= 4 else np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "reads_sampled": len(idx), "reads": n,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def metric_text(args, cfg, E):
@@ -636,6 +663,8 @@ def main():
     ap.add_argument("--kmer-bits", type=int, default=0, help="override the k of the k-mer interval table")
     ap.add_argument("--tune", action="append", default=[], help="name=value passed to bk_ctx_tune (repeatable)")
     ap.add_argument("--sweep", default="", help="name=v1,v2,..: re-time the kernel-only steps for each value and log device ms")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the bk_hit records of the headline's last "
+                    "timed step (rank 0; a fixed, seeded sample of the reads) as DIR/<field>.npy")
     args = ap.parse_args()
     if args.pmc_child:
         args.steps, args.warmup, args.cpu_baseline_secs, args.no_live_traffic, args.no_host_leg, args.no_other_layout = 1, 0, 0.0, True, True, True
@@ -823,9 +852,10 @@ def main():
         except Exception as e:       # reporting only - never lose the measured line
             log(f"host leg unavailable: {e!r}")
 
-    def measure(layout):
+    def measure(layout, keep_host_hits=False):
         """both clocks in one index layout: `warmup` untimed + exactly `steps` timed steps each, a barrier + device synchronisation on
-        both sides of the timed steps, the maximum over ranks"""
+        both sides of the timed steps, the maximum over ranks.  keep_host_hits: a copy of what the host leg's last timed step received
+        (res["host_hits"])"""
         res = {"layout": layout}
         torch.cuda.empty_cache()                           # (what the library may give the window array is what hipMemGetInfo calls free)
         t_set = time.time()
@@ -863,6 +893,8 @@ def main():
             try:
                 res["host"] = host.run(al, args.warmup, args.steps, barrier, all_reduce if dist is not None else None, dev, pe_params)
                 res["host"]["results_bit_identical_to_kernel_only_steps"] = host.same_as(res["hits"], args.steps)
+                if keep_host_hits:
+                    res["host_hits"] = host.h_out[host.last_set].copy()
             except Exception as e:
                 res["host"] = {"value": None, "error": repr(e)}
         return res
@@ -886,7 +918,7 @@ def main():
         torch.cuda.synchronize()
         al.close()
         return
-    main_leg = measure(headline)
+    main_leg = measure(headline, keep_host_hits=bool(args.dump_outputs) and rank == 0)
     if headline != "off" and not main_leg["window_array_resident"]:
         headline = "off"                 # (asked for, but this index / these reads cannot have it: 5-byte elements, long reads, no room)
     other_legs = {}
@@ -962,6 +994,12 @@ def main():
     host_ok = bool(host_leg and host_leg.get("value"))
     value = host_leg["value"] if host_ok else kernel_only_value
     ms_per_step = host_leg["ms_per_step"] if host_ok else main_leg["kernel_only_elapsed"] / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the clock of `value` timed: the host-in / host-out steps, else the kernel-only ones
+        dumped = dump_hits(main_leg["host_hits"] if host_ok else hits, args.dump_outputs)
+        dumped["path"] = "host-in / host-out" if host_ok else "kernel-only"
+        main_leg.pop("host_hits", None)
 
     multi = None
     if world > 1 and E == 4:
@@ -1096,6 +1134,7 @@ def main():
                                    "more at 3.1 Gbp, made behind the suffix array's upload with the other tables",
                         "other": other_image},
         "t_align_host_resident": host_leg,
+        "dump_outputs": dumped,
         "rccl": {"torch_distributed": rccl_info, "library_binding_one_device": lib_rccl} if world == 1 else {"torch_distributed": {"backend": args.dist_backend, "world_size": world}},
     }
     if multi is not None:

@@ -53,3 +53,36 @@ def test_fetch_size_correction_follows_the_committed_calibration():
     assert b.fetch_correction("k_flat", True)[0] == 1.0 and b.fetch_correction("k_wave", False)[0] == 1.0
     f, src = b.fetch_correction("k_wave", True)
     assert 1.5 < f < 2.5, (f, src)
+
+
+def test_dump_outputs_sample_is_fixed_exact_and_bounded(tmp_path):
+    """--dump-outputs: one float32 / float64 array per bk_hit field, every value exact, the same seeded sample of the reads in
+    every run, at most 64 MB in all"""
+    import biokanga_amd as bk
+    b = _bench()
+    n = b.DUMP_SAMPLE_READS * 3 + 11
+    hits = np.zeros(n, dtype=bk.HIT_DTYPE)
+    hits["match_loci"] = np.arange(n, dtype=np.uint32) * 1237 + 0xF0000000
+    hits["chrom_id"] = np.arange(n) % 24
+    hits["low_mm"] = -1
+    hits["low_hit_instances"] = -(np.arange(n) % 300)
+    hits["nar"] = np.arange(n) % 6
+    r1 = b.dump_hits(hits, str(tmp_path / "a"))
+    r2 = b.dump_hits(hits, str(tmp_path / "b"))
+    assert r1["reads_sampled"] == b.DUMP_SAMPLE_READS and r1["reads"] == n
+    assert sorted(r1["arrays"]) == sorted(list(bk.HIT_DTYPE.names) + ["read_index"])
+    total = 0
+    for f in r1["arrays"]:
+        x = np.load(str(tmp_path / "a" / (f + ".npy")))
+        y = np.load(str(tmp_path / "b" / (f + ".npy")))
+        assert x.dtype in (np.float32, np.float64) and len(x) == b.DUMP_SAMPLE_READS
+        assert np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 << 20
+    idx = np.load(str(tmp_path / "a" / "read_index.npy")).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[-1] < n
+    for f in bk.HIT_DTYPE.names:
+        assert np.array_equal(np.load(str(tmp_path / "a" / (f + ".npy"))), hits[f][idx].astype(np.float64)), f
+    small = hits[:1000]
+    b.dump_hits(small, str(tmp_path / "c"))
+    assert np.array_equal(np.load(str(tmp_path / "c" / "match_loci.npy")), small["match_loci"].astype(np.float64))
