@@ -8,12 +8,19 @@ per-sequence hit counts (RCCL all-reduce when N > 1).
 
 `value` is the metric's own clock (T_align: first batch submitted -> last result back): the reads of every step leave
 pinned HOST buffers (2 bit/base, bk_stream_submit_packed), cross PCIe while the batch before them runs through the phases, and every
-bk_hit record is back in HOST memory when the clock stops.  `value_kernel_only` is the same steps with reads and results resident in
-HBM (bk_align_batch_device).  Both are measured in the index layout `biokanga align` itself would pick for the configuration's read
-count (the 149 GB suffix-ordered window array only from 600 M reads per device on, host/biokanga_main.cpp) and, beside it, in the
-other layout (`layouts`).
+bk_hit record is back in HOST memory when the clock stops.  `value_kernel_only` (--full) is the same steps with reads and results
+resident in HBM (bk_align_batch_device).  Both are measured in the index layout `biokanga align` itself would pick for the
+configuration's read count (the 149 GB suffix-ordered window array only from 600 M reads per device on, host/biokanga_main.cpp) and,
+with --full, beside it in the other layouts (`layouts`).
+
+A plain run does what `value` needs and nothing else: set-up, the warm-up steps, the timed steps, the --dump-outputs arrays, the line.
+`--full` adds every other leg to the same line: the kernel-only steps (`value_kernel_only`, `roofline`, the checks that the results are the
+same from step to step and on both clocks), the other index layouts and the other image (`layouts`, `index_image.other`), the library's own
+exchange step (`rccl.library_binding_one_device`), the HBM traffic observed under rocprofv3, `cpu_baseline` (the oracle, the reference binary
+and both command lines on the same reads) and, at N > 1, `shard_check` and `strong_scaling`.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full   (every leg; minutes instead of seconds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N            (no WORLD_SIZE in the environment: starts the N ranks itself, same launcher)
     python bench.py --config C3         (2 x 150 bp paired ends, -s5 -U3 -d200 -D400: SE pass + PE association per step)
@@ -630,14 +637,17 @@ def main():
     ap.add_argument("--reads", type=int, default=0, help="reads per step per GPU (0 = the config's own: 50 M for C2, 40 M = 20 M pairs for C3)")
     ap.add_argument("--read-len", type=int, default=0)
     ap.add_argument("--max-subs", type=int, default=-1, help="`-s` of biokanga align")
-    ap.add_argument("--cpu-baseline-secs", type=float, default=15.0, help="0 disables the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true", help="beside the headline, every other leg of the benchmark: kernel-only steps and roofline, the other index "
+                    "layouts and image, live HBM traffic, the library's RCCL binding, cpu_baseline, N > 1: shard check and strong scaling. "
+                    "Off: set-up, warm-up, the timed steps of `value`, --dump-outputs, the line")
+    ap.add_argument("--cpu-baseline-secs", type=float, default=15.0, help="--full: seconds of CPU work of the cpu_baseline leg; 0 disables it")
     ap.add_argument("--reference-reads", type=int, default=2_000_000,
                     help="reads given to the real reference binary (oracle/_ref/biokanga) in the cpu_baseline leg; 0 = port only. "
                          "Kept at 2 M: the reference's loader hand-off breaks when loading takes > 3 s (Aligner.cpp:4822) - "
                          "3 M reads crash it on the MI355X host about every other run (profiles/r01_host_cpu_scaling.md)")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) one step only, nothing reported: what the live counter passes profile")
-    ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the committed profile instead of two live rocprofv3 --pmc passes")
-    ap.add_argument("--no-full-cli", action="store_true", help="skip the T_e2e run of our command line on a whole step's reads")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: roofline.traffic from the committed profile instead of two live rocprofv3 --pmc passes")
+    ap.add_argument("--no-full-cli", action="store_true", help="--full: skip the T_e2e run of our command line on a whole step's reads")
     ap.add_argument("--window-array", default="policy", choices=["policy", "partial", "on", "off", "full", "forced"],
                     help="index layout of the headline: 'policy' = what `biokanga align` picks for this many reads per device; 'partial' (= 'on') = the "
                          "suffix-ordered window array for the part of the suffix array the wave kernel's long walks visit; 'full' = for every suffix "
@@ -645,15 +655,15 @@ def main():
     ap.add_argument("--index-image", default="policy", choices=["policy", "full", "lean"],
                     help="index image of the headline: 'policy' = what bk_image_policy gives this many reads per device; 'full' = every table; "
                          "'lean' = no second words in the k-mer table, no third- / fourth-level search keys; the other image is measured beside it")
-    ap.add_argument("--no-other-layout", action="store_true", help="measure the headline's index layout and image only")
-    ap.add_argument("--other-layouts", default="off,partial,full", help="which of off / partial / full to measure beside the headline's")
+    ap.add_argument("--no-other-layout", action="store_true", help="--full: measure the headline's index layout and image only")
+    ap.add_argument("--other-layouts", default="off,partial,full", help="--full: which of off / partial / full to measure beside the headline's")
     ap.add_argument("--no-host-leg", action="store_true", help="kernel-only steps only (profiling runs): `value` is then the kernel-only rate and says so")
     ap.add_argument("--stream-form", default="packed", choices=["packed", "bytes"], help="form in which the reads cross PCIe: "
                     "2 bit/base (bk_stream_submit_packed) or 1 byte/base (bk_stream_submit)")
     ap.add_argument("--host-ramp", default="0.06,0.34", help="the first host-in / host-out step's batches end at these fractions of a step (then the rest)")
     ap.add_argument("--host-sets", type=int, default=3, help="sets of host result records of the host-in / host-out steps (steps in flight + 1)")
     ap.add_argument("--stream-batch", type=int, default=0, help="reads per submitted batch of the host-in / host-out steps (0 = a whole step; the first step ramps up to it)")
-    ap.add_argument("--shard-check-reads", type=int, default=8_000_000, help="N > 1: size of the ONE read set that is sharded i mod N and "
+    ap.add_argument("--shard-check-reads", type=int, default=8_000_000, help="--full, N > 1: size of the ONE read set that is sharded i mod N and "
                                                                               "whose reduced counts are compared with a 1-GPU run of all of it")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend; 'gloo' only for dry runs of the multi-rank path")
     ap.add_argument("--no-rccl-world1", action="store_true", help="N = 1: no torch.distributed process group of one rank (default: RCCL is initialised and the "
@@ -795,7 +805,7 @@ def main():
     counts_dev = torch.zeros(len(entries), dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
     log(f"reads: {args.reads} x {args.read_len} bp generated in {time.time() - t0:.1f}s")
-    keep_index_for_baseline = args.cpu_baseline_secs > 0 and rank == 0 and world == 1
+    keep_index_for_baseline = args.full and args.cpu_baseline_secs > 0 and rank == 0 and world == 1
     # the context holds its own image; the bench's copy of the suffix array (12 GB at 3.1 Gbp, 85 GB at 17 Gbp; with 5-byte elements
     # the sequence too) leaves the HBM before the batch scratch - and the context's window array - are sized
     t0 = time.time()
@@ -852,24 +862,9 @@ def main():
         except Exception as e:       # reporting only - never lose the measured line
             log(f"host leg unavailable: {e!r}")
 
-    def measure(layout, keep_host_hits=False):
-        """both clocks in one index layout: `warmup` untimed + exactly `steps` timed steps each, a barrier + device synchronisation on
-        both sides of the timed steps, the maximum over ranks.  keep_host_hits: a copy of what the host leg's last timed step received
-        (res["host_hits"])"""
-        res = {"layout": layout}
-        torch.cuda.empty_cache()                           # (what the library may give the window array is what hipMemGetInfo calls free)
-        t_set = time.time()
-        al.tune("use_swin", SWIN_TUNE[layout])
-        step()                                             # (builds the window array when it is asked for, fits and serves these reads)
-        if E != 4 and layout == "forced":
-            step()                                         # (an index of 5-byte elements: made when a second batch arrives, from what the first one's phases say)
-        torch.cuda.synchronize()
-        t_first = time.time() - t_set
-        res["window_array_resident"] = al.tune("swin_resident", 0) == 1
-        if res["window_array_resident"]:
-            # the library's own clock around allocation + construction, what array and map occupy, the share of the suffix array held
-            res["window_array"] = {"setup_s": al.tune("swin_setup_us", 0) / 1e6, "gb": al.tune("swin_mbytes", 0) * 1048576 / 1e9,
-                                   "share_of_suffix_array": al.tune("swin_covered_ppm", 0) / 1e6}
+    def kernel_only_steps(res):
+        """the kernel-only clock in the layout that is set: the rest of `warmup` untimed steps (measure() has run the first), then exactly
+        `steps` timed ones"""
         for _ in range(max(0, args.warmup - 1)):
             step()
         first_out = out.clone()                            # results of an untimed step, to check repeatability
@@ -886,17 +881,41 @@ def main():
             all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         res.update(kernel_only_elapsed=elapsed, ctr=al.counters(), tim=al.timing(reset=True),
-                   repeatable=bool(torch.equal(first_out, out)), first_step_s=t_first)
+                   repeatable=bool(torch.equal(first_out, out)))
         del first_out
         res["hits"] = out.cpu().numpy().view(bk.HIT_DTYPE).copy()
+
+    def measure(layout, keep_host_hits=False, kernel_only=True):
+        """both clocks in one index layout: `warmup` untimed + exactly `steps` timed steps each, a barrier + device synchronisation on
+        both sides of the timed steps, the maximum over ranks.  keep_host_hits: a copy of what the host leg's last timed step received
+        (res["host_hits"]).  kernel_only=False: the host-in / host-out clock alone - the kernel-only steps are timed only if it fails"""
+        res = {"layout": layout}
+        torch.cuda.empty_cache()                           # (what the library may give the window array is what hipMemGetInfo calls free)
+        t_set = time.time()
+        al.tune("use_swin", SWIN_TUNE[layout])
+        step()                                             # (builds the window array when it is asked for, fits and serves these reads)
+        if E != 4 and layout == "forced":
+            step()                                         # (an index of 5-byte elements: made when a second batch arrives, from what the first one's phases say)
+        torch.cuda.synchronize()
+        res["first_step_s"] = time.time() - t_set
+        res["window_array_resident"] = al.tune("swin_resident", 0) == 1
+        if res["window_array_resident"]:
+            # the library's own clock around allocation + construction, what array and map occupy, the share of the suffix array held
+            res["window_array"] = {"setup_s": al.tune("swin_setup_us", 0) / 1e6, "gb": al.tune("swin_mbytes", 0) * 1048576 / 1e9,
+                                   "share_of_suffix_array": al.tune("swin_covered_ppm", 0) / 1e6}
+        if kernel_only:
+            kernel_only_steps(res)
         if host is not None:
             try:
                 res["host"] = host.run(al, args.warmup, args.steps, barrier, all_reduce if dist is not None else None, dev, pe_params)
-                res["host"]["results_bit_identical_to_kernel_only_steps"] = host.same_as(res["hits"], args.steps)
+                if kernel_only:
+                    res["host"]["results_bit_identical_to_kernel_only_steps"] = host.same_as(res["hits"], args.steps)
                 if keep_host_hits:
                     res["host_hits"] = host.h_out[host.last_set].copy()
             except Exception as e:
                 res["host"] = {"value": None, "error": repr(e)}
+        if not kernel_only and not (res.get("host") or {}).get("value"):
+            kernel_only_steps(res)                         # (no host-in / host-out steps, or they failed: `value` is then this clock's)
         return res
 
     if args.sweep:
@@ -918,9 +937,80 @@ def main():
         torch.cuda.synchronize()
         al.close()
         return
-    main_leg = measure(headline, keep_host_hits=bool(args.dump_outputs) and rank == 0)
+
+    def emit(result):
+        al.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), file=_REAL_STDOUT or sys.stdout, flush=True)
+
+    # a plain run times the clock of `value` alone; --full times the kernel-only steps before it
+    main_leg = measure(headline, keep_host_hits=bool(args.dump_outputs) and rank == 0, kernel_only=args.full)
     if headline != "off" and not main_leg["window_array_resident"]:
         headline = "off"                 # (asked for, but this index / these reads cannot have it: 5-byte elements, long reads, no room)
+    total_reads = args.reads * world * args.steps
+    host_leg = main_leg.get("host")
+    host_ok = bool(host_leg and host_leg.get("value"))
+    value = host_leg["value"] if host_ok else total_reads / main_leg["kernel_only_elapsed"]
+    ms_per_step = host_leg["ms_per_step"] if host_ok else main_leg["kernel_only_elapsed"] / args.steps * 1e3
+    # the records of the last timed step of `value`'s clock: the host-in / host-out steps, else the kernel-only ones
+    accepted = int(((host.h_out[host.last_set] if host_ok else main_leg["hits"])["nar"] == 1).sum())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_hits(main_leg["host_hits"] if host_ok else main_leg["hits"], args.dump_outputs)
+        dumped["path"] = "host-in / host-out" if host_ok else "kernel-only"
+        main_leg.pop("host_hits", None)
+    fmt = dict(reads=args.reads, pairs=args.reads // 2, read_len=args.read_len, max_subs=args.max_subs)
+    result = {
+        "metric": metric_text(args, cfg, E),
+        "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value_clock": ("T_align of SURVEY 8d: reads leave pinned host memory (2 bit/base), results are back in host memory; "
+                        f"{args.steps} steps between two barriers") if host_ok else
+                       "kernel-only: reads and results resident in HBM (the host-in / host-out steps were switched off or failed)",
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"{args.config}: {cfg['text'].format(**fmt)} vs synthetic {'wheat' if E == 5 else 'GRCh38'}-like genome of {total_bp} bp in "
+                               f"{len(seq_lens)} sequences ({int(100 * cfg.get('repeat_frac', 0.45))}% repeat-derived, N gaps), {cfg['cli'].format(**fmt)}",
+                   "window_array": headline + (f" (what `biokanga align` picks for the {job_reads} reads a device aligns in this configuration: the partial suffix-ordered "
+                                    f"window array from {bk.POLICY_MIN_READS} reads on, or --window-array)" if args.window_array == "policy" else " (forced with --window-array)"),
+                   "index_image": headline_image + (f" (what bk_image_policy - the function `biokanga align` calls - gives the {job_reads} reads a device aligns in this "
+                                                    f"configuration: every table from {bk.POLICY_MIN_READS} reads on)" if args.index_image == "policy" else " (forced with --index-image)"),
+                   "reads_per_gpu_per_step": args.reads, "read_len": args.read_len, "genome_bp": total_bp,
+                   "concat_len": n, "sfx_el_size": E, "index": "replicated per GPU, built on device",
+                   "parallelism": f"reads sharded over {world} GPU(s): read g of the job's set = read g // {world} of rank g % {world}",
+                   "accepted_frac_rank0": accepted / args.reads},
+        "index_image": {"headline": headline_image, "policy": policy_image, "policy_flags_of_bk_image_policy": policy_flags, "job_reads_per_gpu": job_reads,
+                        "resident": image_resident,
+                        "full_is": "k-mer table entries of two words (a bucket's only key, or the map of its keys' first five bits), third- and fourth-level search keys: 43 GB "
+                                   "more at 3.1 Gbp, made behind the suffix array's upload with the other tables"},
+        "t_align_host_resident": host_leg,
+        "dump_outputs": dumped,
+        "rccl": {"torch_distributed": rccl_info} if world == 1 else {"torch_distributed": {"backend": args.dist_backend, "world_size": world}},
+    }
+
+    def diag():
+        if os.environ.get("BK_DIAG"):
+            print("diag counters:", main_leg.get("ctr", "(of the kernel-only steps: --full)"), file=sys.stderr)
+            import ctypes
+            arr = (ctypes.c_ulonglong * 16)()
+            if bk.load_library().bk_debug_prof(arr) == 0:
+                print("diag prof:", list(arr), file=sys.stderr)
+            if hasattr(bk.load_library(), "bk_debug_prof_wave") and bk.load_library().bk_debug_prof_wave(arr) == 0:
+                print("diag prof wave:", list(arr)[:8], file=sys.stderr)
+
+    if not args.full:
+        # the line of a plain run: the headline, what it ran on, and what its set-up and its own steps told on the way
+        built = main_leg.get("window_array") or {}
+        result.update({"window_array_setup_s": built.get("setup_s"), "window_array_gb": built.get("gb"),
+                       "window_array_share_of_suffix_array": built.get("share_of_suffix_array")})
+        if "kernel_only_elapsed" in main_leg:
+            result["value_kernel_only"] = total_reads / main_leg["kernel_only_elapsed"]
+        diag()
+        emit(result)
+        return
+    # ---------------------------------------------------------------- --full: every other leg
     other_legs = {}
     if not args.no_other_layout:
         # (an index of 5-byte elements: the partial array made when asked for, "use_swin" 2 - the policy leaves such an index without)
@@ -978,28 +1068,9 @@ def main():
         except Exception as e:
             lib_rccl = {"error": repr(e)}
     headline_on = headline != "off"
-    if os.environ.get("BK_DIAG"):
-        print("diag counters:", main_leg["ctr"], file=sys.stderr)
-        import ctypes
-        arr = (ctypes.c_ulonglong * 16)()
-        if bk.load_library().bk_debug_prof(arr) == 0:
-            print("diag prof:", list(arr), file=sys.stderr)
-        if hasattr(bk.load_library(), "bk_debug_prof_wave") and bk.load_library().bk_debug_prof_wave(arr) == 0:
-            print("diag prof wave:", list(arr)[:8], file=sys.stderr)
+    diag()
     ctr, tim, hits = main_leg["ctr"], main_leg["tim"], main_leg["hits"]
-    accepted = int((hits["nar"] == 1).sum())
-    total_reads = args.reads * world * args.steps
     kernel_only_value = total_reads / main_leg["kernel_only_elapsed"]
-    host_leg = main_leg.get("host")
-    host_ok = bool(host_leg and host_leg.get("value"))
-    value = host_leg["value"] if host_ok else kernel_only_value
-    ms_per_step = host_leg["ms_per_step"] if host_ok else main_leg["kernel_only_elapsed"] / args.steps * 1e3
-    dumped = None
-    if args.dump_outputs and rank == 0:
-        # what the clock of `value` timed: the host-in / host-out steps, else the kernel-only ones
-        dumped = dump_hits(main_leg["host_hits"] if host_ok else hits, args.dump_outputs)
-        dumped["path"] = "host-in / host-out" if host_ok else "kernel-only"
-        main_leg.pop("host_hits", None)
 
     multi = None
     if world > 1 and E == 4:
@@ -1098,45 +1169,22 @@ def main():
     built = ((layouts.get("window_array_" + headline) or {}).get("window_array_built") or (part_rec or {}).get("window_array_built") or {})
     setup_s = built.get("setup_s")
 
-    fmt = dict(reads=args.reads, pairs=args.reads // 2, read_len=args.read_len, max_subs=args.max_subs)
-    result = {
-        "metric": metric_text(args, cfg, E),
-        "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "value_clock": ("T_align of SURVEY 8d: reads leave pinned host memory (2 bit/base), results are back in host memory; "
-                        f"{args.steps} steps between two barriers") if host_ok else
-                       "kernel-only: reads and results resident in HBM (the host-in / host-out steps were switched off or failed)",
+    result.update({
         "value_kernel_only": kernel_only_value,
         "value_no_window_array": (off_rec or {}).get("value_host_in_host_out") or (off_rec or {}).get("value_kernel_only"),
         "value_window_array": (part_rec or {}).get("value_host_in_host_out") or (part_rec or {}).get("value_kernel_only"),
         "value_window_array_full": (full_rec or {}).get("value_host_in_host_out") or (full_rec or {}).get("value_kernel_only"),
         "window_array_setup_s": setup_s, "window_array_gb": built.get("gb"), "window_array_share_of_suffix_array": built.get("share_of_suffix_array"),
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "config": {"workload": f"{args.config}: {cfg['text'].format(**fmt)} vs synthetic {'wheat' if E == 5 else 'GRCh38'}-like genome of {total_bp} bp in "
-                               f"{len(seq_lens)} sequences ({int(100 * cfg.get('repeat_frac', 0.45))}% repeat-derived, N gaps), {cfg['cli'].format(**fmt)}",
-                   "window_array": headline + (f" (what `biokanga align` picks for the {job_reads} reads a device aligns in this configuration: the partial suffix-ordered "
-                                    f"window array from {bk.POLICY_MIN_READS} reads on, or --window-array)" if args.window_array == "policy" else " (forced with --window-array)"),
-                   "index_image": headline_image + (f" (what bk_image_policy - the function `biokanga align` calls - gives the {job_reads} reads a device aligns in this "
-                                                    f"configuration: every table from {bk.POLICY_MIN_READS} reads on)" if args.index_image == "policy" else " (forced with --index-image)"),
-                   "reads_per_gpu_per_step": args.reads, "read_len": args.read_len, "genome_bp": total_bp,
-                   "concat_len": n, "sfx_el_size": E, "index": "replicated per GPU, built on device",
-                   "parallelism": f"reads sharded over {world} GPU(s): read g of the job's set = read g // {world} of rank g % {world}",
-                   "accepted_frac_rank0": accepted / args.reads,
-                   "n_search_per_read": ctr["n_search"] / (args.reads * args.steps),
-                   "n_cand_per_read": ctr["n_cand"] / (args.reads * args.steps),
-                   "heavy_calls_frac": ctr["n_heavy"] / max(1, ctr["n_lcm_calls"]),
-                   "results_bitwise_equal_across_steps": main_leg["repeatable"]},
         "roofline": roofline,
         "layouts": layouts,
-        "index_image": {"headline": headline_image, "policy": policy_image, "policy_flags_of_bk_image_policy": policy_flags, "job_reads_per_gpu": job_reads,
-                        "resident": image_resident,
-                        "full_is": "k-mer table entries of two words (a bucket's only key, or the map of its keys' first five bits), third- and fourth-level search keys: 43 GB "
-                                   "more at 3.1 Gbp, made behind the suffix array's upload with the other tables",
-                        "other": other_image},
-        "t_align_host_resident": host_leg,
-        "dump_outputs": dumped,
-        "rccl": {"torch_distributed": rccl_info, "library_binding_one_device": lib_rccl} if world == 1 else {"torch_distributed": {"backend": args.dist_backend, "world_size": world}},
-    }
+    })
+    result["config"].update({"n_search_per_read": ctr["n_search"] / (args.reads * args.steps),
+                             "n_cand_per_read": ctr["n_cand"] / (args.reads * args.steps),
+                             "heavy_calls_frac": ctr["n_heavy"] / max(1, ctr["n_lcm_calls"]),
+                             "results_bitwise_equal_across_steps": main_leg["repeatable"]})
+    result["index_image"]["other"] = other_image
+    if world == 1:
+        result["rccl"]["library_binding_one_device"] = lib_rccl
     if multi is not None:
         result.update(multi)
     if keep_index_for_baseline:
@@ -1147,12 +1195,7 @@ def main():
         except Exception as e:      # the baseline is reporting only - never lose the measured line
             result["cpu_baseline"] = {"value": None, "unit": "reads/s", "cores": effective_cpus(), "kind": "port",
                                       "sample": f"failed: {e!r}"}
-    al.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), file=_REAL_STDOUT or sys.stdout, flush=True)
+    emit(result)
 
 
 def multi_gpu_legs(al, make_set, run_step, counts_dev, args, rank, world, dev, barrier, all_reduce, dist):

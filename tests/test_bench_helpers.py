@@ -86,3 +86,14 @@ def test_dump_outputs_sample_is_fixed_exact_and_bounded(tmp_path):
     small = hits[:1000]
     b.dump_hits(small, str(tmp_path / "c"))
     assert np.array_equal(np.load(str(tmp_path / "c" / "match_loci.npy")), small["match_loci"].astype(np.float64))
+
+
+def test_full_is_an_option():
+    """every leg beyond the headline sits behind --full: the option is there and parses"""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "0", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--gpus must be >= 1" in r.stderr and "unrecognized" not in r.stderr

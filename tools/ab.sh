@@ -5,7 +5,7 @@ O=$1; shift
 mkdir -p $O
 for v in "$@"; do
   if [ "$v" = "-" ]; then unset BK_LIB; name=base; else export BK_LIB=$PWD/biokanga_amd/lib/libbiokanga_amd_$v.so; name=$v; fi
-  python3 bench.py --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --window-array on --steps 3 > $O/ab_$name.json 2> $O/ab_$name.err
+  python3 bench.py --full --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --window-array on --steps 3 > $O/ab_$name.json 2> $O/ab_$name.err
   python3 - "$O/ab_$name.json" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

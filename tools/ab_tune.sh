@@ -6,7 +6,7 @@ for t in "$@"; do
   name=$(echo "$t" | tr '= ' '__')
   args=""
   [ "$t" != none ] && args="--tune $t"
-  timeout 600 python3 bench.py --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --no-rccl-world1 $args > $O/abt_$name.json 2> $O/abt_$name.err
+  timeout 600 python3 bench.py --full --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --no-rccl-world1 $args > $O/abt_$name.json 2> $O/abt_$name.err
   python3 - "$O/abt_$name.json" "$t" <<'PY'
 import json, sys
 try:

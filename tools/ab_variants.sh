@@ -7,7 +7,7 @@ mkdir -p $O
 for v in "$@"; do
   lib=biokanga_amd/lib/libbiokanga_amd_$v.so
   [ "$v" = main ] && lib=biokanga_amd/lib/libbiokanga_amd.so
-  BK_LIB=$PWD/$lib timeout 600 python3 bench.py --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --no-rccl-world1 ${AB_ARGS:-} > $O/ab_$v.json 2> $O/ab_$v.err
+  BK_LIB=$PWD/$lib timeout 600 python3 bench.py --full --no-host-leg --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --no-rccl-world1 ${AB_ARGS:-} > $O/ab_$v.json 2> $O/ab_$v.err
   python3 - "$O/ab_$v.json" "$v" <<'PY'
 import json, sys
 try:

@@ -3,7 +3,7 @@
 #   tools/gpu_session.sh <tag> <what> [<what> ..]
 #     tests     the whole GPU suite (python -m pytest tests -m gpu)
 #     cli       the command-line golden tests only
-#     bench     python bench.py (the driver's command) -> bench.json / bench.err
+#     bench     python bench.py --full (every leg of the benchmark) -> bench.json / bench.err
 #     quick     kernel-only bench lines of 3 M and 50 M reads per step, both index layouts
 #     calib     FETCH_SIZE in our access patterns (tools/rand_access_bench calib under rocprofv3 --pmc)
 #     prof      tools/profile_round.sh + tools/pmc_busy.sh (kernel stats, counters, ALU busy) -> gpurun_out/profiles_<tag>/
@@ -24,10 +24,10 @@ for what in "$@"; do
   case $what in
     tests) timeout 1500 python3 -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1; tail -4 $O/gputests.log ;;
     cli)   timeout 600 python3 -m pytest tests/test_gpu_cli.py -x -q > $O/cli_tests.log 2>&1; tail -12 $O/cli_tests.log ;;
-    bench) timeout 900 python3 bench.py > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err; head -c 2500 $O/bench.json; echo ;;
+    bench) timeout 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err; head -c 2500 $O/bench.json; echo ;;
     quick)
-      python3 bench.py --reads 3000000 --no-host-leg --cpu-baseline-secs 0 --no-live-traffic > $O/b3m.json 2> $O/b3m.err
-      python3 bench.py --no-host-leg --cpu-baseline-secs 0 --no-live-traffic > $O/b50m.json 2> $O/b50m.err
+      python3 bench.py --full --reads 3000000 --no-host-leg --cpu-baseline-secs 0 --no-live-traffic > $O/b3m.json 2> $O/b3m.err
+      python3 bench.py --full --no-host-leg --cpu-baseline-secs 0 --no-live-traffic > $O/b50m.json 2> $O/b50m.err
       python3 - "$O" <<'PY'
 import json, sys
 for f in ("b3m", "b50m"):
@@ -54,7 +54,7 @@ PY
     quota)
       # two ranks on the one GPU and four contexts of the command line, unconstrained and held to four CPUs (what a rank of an 8-GPU job
       # gets of the box's 16-CPU quota): the host side must not need more
-      B="python3 bench.py --gpus 2 --force-device 0 --dist-backend gloo --genome-mbp 800 --reads 12000000 --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --steps 3"
+      B="python3 bench.py --full --gpus 2 --force-device 0 --dist-backend gloo --genome-mbp 800 --reads 12000000 --cpu-baseline-secs 0 --no-live-traffic --no-other-layout --steps 3"
       timeout 300 $B > $O/quota_2ranks_free.json 2> $O/quota_2ranks_free.err
       timeout 300 taskset -c 0-3 $B > $O/quota_2ranks_4cpus.json 2> $O/quota_2ranks_4cpus.err
       python3 - "$O" <<'PY'

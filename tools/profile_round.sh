@@ -12,7 +12,7 @@ raw=/tmp/prof_$tag                 # (the raw rocprofv3 output stays on the box:
 out=gpurun_out/profiles_$tag
 mkdir -p $raw $out
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 2 --warmup 1 --cpu-baseline-secs 0 --no-host-leg --no-live-traffic --no-other-layout --no-rccl-world1"      # (the layout the policy picks, nothing else in the trace)
+BENCH="python3 bench.py --full --steps 2 --warmup 1 --cpu-baseline-secs 0 --no-host-leg --no-live-traffic --no-other-layout --no-rccl-world1"      # (the layout the policy picks, nothing else in the trace)
 
 rocprofv3 --kernel-trace --stats --output-format csv -d $raw/stats -o run -- $BENCH > $raw/stats.log 2>&1
 grep '^{' $raw/stats.log | tail -1 > $out/${tag}_bench_line_under_rocprof.json
@@ -29,7 +29,7 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $raw/calib -o r
 python3 tools/summarize_prof.py pmc $raw/calib > $out/${tag}_fetch_calibration.csv
 grep calib: $raw/calib.log >> $out/${tag}_fetch_calibration.csv
 
-# a plain run for the bench line without profiler overhead, with the CPU baseline
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_line.json 2> $raw/bench.log      # (the driver's command)
+# a run of every leg for the bench line without profiler overhead, with the CPU baseline
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_line.json 2> $raw/bench.log
 tail -2 $raw/bench.log
 cat $out/${tag}_kernel_stats.csv
