@@ -101,6 +101,21 @@ class _StreamStats(ctypes.Structure):
                 ("bytes_d2h", ctypes.c_uint64), ("seconds_first_submit_to_last_result", ctypes.c_double)]
 
 
+class _SamJob(ctypes.Structure):
+    """bk_sam_job, field for field"""
+    _fields_ = [("bases", ctypes.c_void_p), ("n_bases", ctypes.c_uint64), ("offs", ctypes.c_void_p), ("lens", ctypes.c_void_p),
+                ("names", ctypes.c_void_p), ("n_name_bytes", ctypes.c_uint64), ("name_ofs", ctypes.c_void_p),
+                ("hits", ctypes.c_void_p), ("n_reads", ctypes.c_uint64), ("order", ctypes.c_void_p), ("n_order", ctypes.c_uint64),
+                ("report_unaligned", ctypes.c_int32), ("pe_mode", ctypes.c_int32), ("prep", ctypes.c_void_p),
+                ("pk_words", ctypes.c_void_p), ("n_pk_words", ctypes.c_uint64), ("pk_lens16", ctypes.c_void_p),
+                ("pk_exc", ctypes.c_void_p), ("n_pk_exc", ctypes.c_uint64),
+                ("src", ctypes.c_void_p), ("n_src_reads", ctypes.c_uint64), ("seg2", ctypes.c_void_p),
+                ("trim_left", ctypes.c_void_p), ("trim_right", ctypes.c_void_p)]
+
+
+_SAM_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
+
+
 def lib_path():
     # BK_LIB: another build of the same library (kernel experiments)
     return os.environ.get("BK_LIB") or os.path.join(_HERE, "lib", "libbiokanga_amd.so")
@@ -246,6 +261,8 @@ def load_library():
     lib.bk_stream_get_stats.restype = i32
     lib.bk_stream_destroy.argtypes = [vp]
     lib.bk_stream_destroy.restype = None
+    lib.bk_sam_format.argtypes = [vp, ctypes.POINTER(_SamJob), _SAM_SINK, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.bk_sam_format.restype = i32
     _lib = lib
     return lib
 
@@ -551,6 +568,48 @@ class Aligner:
         if rc:
             raise BkError(rc, "bk_pair_batch_seg2")
         return hits, seg2
+
+    def sam_format(self, bases, offs, lens, names, hits, order, report_unaligned=True, pe_mode=0, *, src=None, seg2=None,
+                   trim_left=None, trim_right=None):
+        """bk_sam_format: the SAM body of `hits` in the order given, as bytes.  `names`: a list of bytes, one per read.  Without `src`
+        hits go by read; with it (record -> read) hits, order and the trims go by record, the read store and seg2 by read."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        assert hits.dtype == HIT_DTYPE and len(names) == len(lens)
+        hits = np.ascontiguousarray(hits)
+        blob = np.frombuffer(b"".join(n + b"\0" for n in names), dtype=np.uint8)
+        name_ofs = np.zeros(len(names), dtype=np.uint64)
+        name_ofs[1:] = np.cumsum([len(n) + 1 for n in names[:-1]])
+        job = _SamJob(bases=bases.ctypes.data, n_bases=len(bases), offs=offs.ctypes.data, lens=lens.ctypes.data, names=blob.ctypes.data,
+                      n_name_bytes=len(blob), name_ofs=name_ofs.ctypes.data, hits=hits.ctypes.data, n_reads=len(hits),
+                      order=order.ctypes.data, n_order=len(order), report_unaligned=1 if report_unaligned else 0, pe_mode=pe_mode)
+        keep = []
+        for field, arr, dt, n in (("src", src, np.uint32, len(hits)), ("seg2", seg2, SEG2_DTYPE, len(lens)),
+                                  ("trim_left", trim_left, np.uint16, len(hits)), ("trim_right", trim_right, np.uint16, len(hits))):
+            if arr is None:
+                continue
+            arr = np.ascontiguousarray(arr, dtype=dt)
+            assert len(arr) == n, field
+            keep.append(arr)
+            setattr(job, field, arr.ctypes.data)
+        if src is not None:
+            job.n_src_reads = len(lens)
+        else:
+            assert len(hits) == len(lens)
+        parts = {}
+
+        def sink(user, text, n, ofs):
+            parts[ofs] = ctypes.string_at(text, n)
+            return 0
+        n_rep, n_bytes = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.bk_sam_format(self.h, ctypes.byref(job), _SAM_SINK(sink), None, ctypes.byref(n_rep), ctypes.byref(n_bytes))
+        if rc:
+            raise BkError(rc, "bk_sam_format")
+        text = b"".join(parts[k] for k in sorted(parts))
+        assert len(text) == n_bytes.value
+        return text
 
     def pair_device(self, d_bases, d_offs, d_lens, n_pairs, d_hits, pe, d_seg2=None):
         """PE association on device-resident buffers (ints = device pointers); hits (and seg2 records, when given) updated in place."""

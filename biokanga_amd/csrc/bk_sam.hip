@@ -37,6 +37,12 @@ struct SamDev {
     const bk_nbase *pk_exc;
     const uint32_t *pk_efirst;
     uint64_t n_pk_exc;
+    // what a record may carry besides its hit (all null, ext = 0, in a job of plain records): record -> read (-r5; reads and records are
+    // the same without), the reads' second segments, the records' end trims in read orientation
+    const uint32_t *src;
+    const bk_seg2 *seg2;
+    const uint16_t *trim_l, *trim_r;
+    int ext;                         // any of the four is there: the kernels ask this first, so plain jobs never look at a record for them
 };
 constexpr uint32_t kNoExc = 0xFFFFFFFFu;
 
@@ -46,6 +52,8 @@ __device__ __forceinline__ int n_digits(unsigned long v)
     while (v >= 10) { v /= 10; n++; }
     return n;
 }
+
+__device__ __forceinline__ int n_chars(long v) { return v < 0 ? 1 + n_digits((unsigned long)(-v)) : n_digits((unsigned long)v); }
 
 __device__ __forceinline__ char *put_num(char *w, long v)
 {
@@ -69,11 +77,61 @@ __device__ const char kSamNarTag[20][3] = {"NA", "AA", "EN", "NL", "MH", "ML", "
 
 // the fields of record k that both passes need
 struct SamRec {
-    uint32_t i, len, nml;
+    uint32_t i, rd, len, nml;        // record, its read, the read's length and name length
     bool acc, reported, has_qual;
     int flag, tlen;
     long pnext;
+    uint32_t pos, mlen;              // AdjStartLoci, AdjHitLen: the hit's own without trims
+    // jobs with ext only: soft clips in target orientation, and the second segment's gap (gop: 'N', 'I', 'D'; 0 = one segment)
+    uint32_t clip5, clip3, len2;
+    long gap;
+    char gop;
 };
+
+// trims and second segment of an accepted record (format_rec of host/report.cpp; CAligner::ReportBAMread, Aligner.cpp:5960-6033)
+__device__ __forceinline__ void sam_rec_ext(const SamDev &d, const bk_hit &h, SamRec &r)
+{
+    if (d.trim_l) {
+        const uint32_t tl = d.trim_l[r.i], tr = d.trim_r[r.i];
+        const bool plus = h.strand == '+';
+        r.pos = h.match_loci + (plus ? tl : tr);
+        r.mlen = (uint32_t)h.match_len - tl - tr;
+        r.clip5 = plus ? tl : tr;
+        r.clip3 = plus ? tr : tl;
+    }
+    if (d.seg2) {
+        const bk_seg2 g = d.seg2[r.rd];
+        if (g.flags & 5) {                                  // FlgInDel or FlgSplice
+            const long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len);
+            if (g.flags & 4) { r.gop = 'N'; r.gap = gap; }
+            else if (g.flags & 2) { r.gop = 'I'; r.gap = (long)r.len - ((long)h.match_len + g.match_len); }
+            else { r.gop = 'D'; r.gap = gap < 0 ? -gap : gap; }
+            r.len2 = g.match_len;
+        }
+    }
+}
+
+// [clip5 S] len M [clip3 S] [gap N|I|D len2 M]: the second segment follows the 3' clip, which is what the reference writes
+__device__ __forceinline__ int cigar_chars(const SamRec &r)
+{
+    return (r.clip5 ? n_digits(r.clip5) + 1 : 0) + n_digits(r.mlen) + 1 + (r.clip3 ? n_digits(r.clip3) + 1 : 0) +
+           (r.gop ? n_chars(r.gap) + 1 + n_digits(r.len2) + 1 : 0);
+}
+
+__device__ __forceinline__ char *put_cigar(char *w, const SamRec &r)
+{
+    if (r.clip5) { w = put_num(w, r.clip5); *w++ = 'S'; }
+    w = put_num(w, r.mlen);
+    *w++ = 'M';
+    if (r.clip3) { w = put_num(w, r.clip3); *w++ = 'S'; }
+    if (r.gop) {
+        w = put_num(w, r.gap);
+        *w++ = r.gop;
+        w = put_num(w, r.len2);
+        *w++ = 'M';
+    }
+    return w;
+}
 
 __device__ __forceinline__ SamRec sam_rec(const SamDev &d, uint64_t k)
 {
@@ -82,23 +140,34 @@ __device__ __forceinline__ SamRec sam_rec(const SamDev &d, uint64_t k)
     const bk_hit h = d.hits[r.i];
     r.acc = h.nar == BK_NAR_ACCEPTED;
     r.reported = r.acc || d.fmt6;
-    r.len = d.lens[r.i];
-    r.nml = (uint32_t)(d.name_ofs[r.i + 1] - d.name_ofs[r.i] - 1);
+    r.rd = (d.ext && d.src) ? d.src[r.i] : r.i;
+    r.len = d.lens[r.rd];
+    r.nml = (uint32_t)(d.name_ofs[r.rd + 1] - d.name_ofs[r.rd] - 1);
     r.flag = 0; r.tlen = 0; r.pnext = -1; r.has_qual = false;
+    r.pos = h.match_loci; r.mlen = h.match_len;
+    r.clip5 = 0; r.clip3 = 0; r.len2 = 0; r.gap = 0; r.gop = 0;
     if (!r.reported) return r;
+    if (d.ext && r.acc) sam_rec_ext(d, h, r);
     if (!d.pe_mode) r.flag = r.acc ? (h.strand == '+' ? 0 : 16) : 4;
     else {
         // flags of CAligner::ReportBAMread for paired ends (Aligner.cpp:5850-5924)
         const bool first_of_pair = (r.i & 1) == 0;
-        const bk_hit m = d.hits[first_of_pair ? r.i + 1 : r.i - 1];
+        const uint32_t mi = first_of_pair ? r.i + 1 : r.i - 1;
+        const bk_hit m = d.hits[mi];
         r.flag = 0x1 | 0x2 | (first_of_pair ? 0x40 : 0x80);
         r.flag |= r.acc ? (h.strand == '+' ? 0 : 0x10) : 0x4;
         if ((h.flags & 0x80) && (m.flags & 0x80) && m.nar == BK_NAR_ACCEPTED) {
             r.flag |= m.strand == '+' ? 0 : 0x20;
             if (r.acc) {
-                r.pnext = (long)m.match_loci;
-                const long s0 = (long)h.match_loci, s1 = (long)m.match_loci;
-                r.tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)m.match_len : (s0 - s1) + (long)h.match_len);
+                uint32_t m_pos = m.match_loci, m_len = m.match_len;             // the mate's start and length, trimmed as its own record's are
+                if (d.ext && d.trim_l) {
+                    const uint32_t tl = d.trim_l[mi], tr = d.trim_r[mi];
+                    m_pos += m.strand == '+' ? tl : tr;
+                    m_len -= tl + tr;
+                }
+                r.pnext = (long)m_pos;
+                const long s0 = (long)r.pos, s1 = (long)m_pos;
+                r.tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)m_len : (s0 - s1) + (long)r.mlen);
             }
         } else
             r.flag |= 0x8;
@@ -153,9 +222,9 @@ __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t rep = 0;
     SamRec r;
-    r.reported = false; r.len = 0; r.i = 0;
+    r.reported = false; r.len = 0; r.i = 0; r.rd = 0;
     if (j < n) r = sam_rec(d, k0 + j);
-    r.has_qual = wave_has_qual(d, (r.reported && d.bases) ? d.offs[r.i] : 0, (r.reported && d.bases) ? r.len : 0);
+    r.has_qual = wave_has_qual(d, (r.reported && d.bases) ? d.offs[r.rd] : 0, (r.reported && d.bases) ? r.len : 0);
     if (j < n) {
         unsigned long long b = 0;
         if (r.reported) {
@@ -167,9 +236,9 @@ __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint
                 const char *nm = d.ent_names + (size_t)(h.chrom_id - 1) * 81;
                 uint32_t cl = 0;
                 while (nm[cl]) cl++;
-                // \t RNAME \t POS \t255\t <len>M \t [*=] \t PNEXT \t TLEN \t SEQ \t QUAL \n
-                b += 1 + cl + 1 + n_digits((unsigned long)h.match_loci + 1) + 5 + n_digits(h.match_len) + 1 + 1 + 1 + 1 +
-                     n_digits((unsigned long)(r.pnext < 0 ? 0 : r.pnext + 1)) + 1 + n_digits((unsigned long)r.tlen) + 1 + r.len + 1 + qual + 1;
+                // \t RNAME \t POS \t255\t CIGAR \t [*=] \t PNEXT \t TLEN \t SEQ \t QUAL \n
+                b += 1 + cl + 1 + n_digits((unsigned long)r.pos + 1) + 5 + (d.ext ? cigar_chars(r) : n_digits(r.mlen) + 1) + 1 + 1 + 1 +
+                     n_digits((unsigned long)(r.pnext < 0 ? 0 : r.pnext + 1)) + 1 + n_chars((long)r.tlen) + 1 + r.len + 1 + qual + 1;
             } else
                 // \t*\t0\t255\t <len>M\t*\t0\t0\t SEQ \t QUAL \t\tYU:Z:xx \n
                 b += 9 + n_digits(r.len) + 8 + r.len + 1 + qual + 7 + 2 + 1;
@@ -214,11 +283,11 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     SamRec r;
-    r.reported = false; r.len = 0; r.i = 0; r.nml = 0; r.acc = false;
+    r.reported = false; r.len = 0; r.i = 0; r.rd = 0; r.nml = 0; r.acc = false;
     if (j < n) r = sam_rec(d, k0 + j);
     const bool packed = d.bases == nullptr;
-    const uint8_t *s = !r.reported ? nullptr : (packed ? reinterpret_cast<const uint8_t *>(d.pk_words + d.pk_wofs[r.i]) : d.bases + d.offs[r.i]);
-    r.has_qual = wave_has_qual(d, (r.reported && !packed) ? d.offs[r.i] : 0, (r.reported && !packed) ? r.len : 0);
+    const uint8_t *s = !r.reported ? nullptr : (packed ? reinterpret_cast<const uint8_t *>(d.pk_words + d.pk_wofs[r.rd]) : d.bases + d.offs[r.rd]);
+    r.has_qual = wave_has_qual(d, (r.reported && !packed) ? d.offs[r.rd] : 0, (r.reported && !packed) ? r.len : 0);
     // the lane writes its record's small fields and notes where the three bulk pieces go
     char *w_name = nullptr, *w_seq = nullptr, *w_qual = nullptr;
     int seq_mode = 1, qual_mode = 3;
@@ -233,10 +302,10 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
             *w++ = '\t';
             w = put_str(w, d.ent_names + (size_t)(h.chrom_id - 1) * 81);
             *w++ = '\t';
-            w = put_num(w, (long)h.match_loci + 1);
+            w = put_num(w, (long)r.pos + 1);
             *w++ = '\t'; *w++ = '2'; *w++ = '5'; *w++ = '5'; *w++ = '\t';
-            w = put_num(w, h.match_len);
-            *w++ = 'M';
+            if (d.ext) w = put_cigar(w, r);
+            else { w = put_num(w, r.mlen); *w++ = 'M'; }
             *w++ = '\t';
             *w++ = r.pnext < 0 ? '*' : '=';
             *w++ = '\t';
@@ -265,15 +334,15 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
             *w++ = '\n';
         }
     }
-    wave_copy(r.reported ? reinterpret_cast<const uint8_t *>(d.names + d.name_ofs[r.i]) : nullptr, w_name, r.reported ? r.nml : 0, 0);
+    wave_copy(r.reported ? reinterpret_cast<const uint8_t *>(d.names + d.name_ofs[r.rd]) : nullptr, w_name, r.reported ? r.nml : 0, 0);
     wave_copy(s, w_seq, r.reported ? r.len : 0, packed ? seq_mode + 4 : seq_mode);
     wave_copy(s, w_qual, w_qual ? r.len : 0, qual_mode);
     if (packed && r.reported) {
         // the record's bases that are not a,c,g,t: every code prints as N (the few there are: the lane walks its own runs)
-        uint32_t e = d.pk_efirst[r.i];
+        uint32_t e = d.pk_efirst[r.rd];
         if (e != kNoExc) {
             __threadfence_block();                         // (after the wave's letters, whichever lanes stored them)
-            for (; e < d.n_pk_exc && d.pk_exc[e].read == r.i; e++) {
+            for (; e < d.n_pk_exc && d.pk_exc[e].read == r.rd; e++) {
                 const bk_nbase x = d.pk_exc[e];
                 for (uint32_t t = 0; t <= x.run; t++) {
                     const uint32_t pp = (uint32_t)x.pos + t;
@@ -439,11 +508,15 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     *n_reported = 0;
     *n_bytes = 0;
     if (!job->n_order) return BK_OK;
-    if (!sam_job_reads_ok(job) || !job->hits || !job->order) return BK_ERR_PARAMS;
-    if (job->pe_mode && (job->n_reads & 1)) return BK_ERR_PARAMS;
+    // with `src` the job's n_reads counts records and n_src_reads the reads; the read side below sees a job that counts its reads
+    bk_sam_job rj = *job;
+    if (job->src) rj.n_reads = job->n_src_reads;
+    if (!sam_job_reads_ok(&rj) || !job->n_reads || !job->hits || !job->order) return BK_ERR_PARAMS;
+    if (job->pe_mode && ((job->n_reads & 1) || job->src)) return BK_ERR_PARAMS;       // (the reference refuses -r with -U)
+    if ((job->trim_left == nullptr) != (job->trim_right == nullptr)) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const uint64_t nr = job->n_reads;
+    const uint64_t nr = rj.n_reads, n_rec = job->n_reads;      // reads, records
     const uint32_t n_ent = (uint32_t)c->entries.size();
     const bool timing = bk::env::timing();
     auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
@@ -462,10 +535,10 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
         if (prep->rc != BK_OK) prep.reset();
     }
     lap(prep ? "head start taken, waited" : "no head start");
-    if (!prep) { int ru = sam_upload_reads(c, job, own); if (ru) return ru; }
+    if (!prep) { int ru = sam_upload_reads(c, &rj, own); if (ru) return ru; }
     SamReads &rd = prep ? prep->rd : own;
     const bool packed = job->pk_words != nullptr;
-    SAM_TRY(d_hits.alloc(nr * sizeof(bk_hit)));
+    SAM_TRY(d_hits.alloc(n_rec * sizeof(bk_hit)));
     SAM_TRY(d_order.alloc(job->n_order * 4));
     SAM_TRY(d_ent.alloc((size_t)n_ent * 81));
     const uint32_t slice = (uint32_t)std::min<uint64_t>(job->n_order, kSamSliceRecords);
@@ -475,8 +548,23 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     size_t tb = 0;
     SAM_TRY(bk::prim::exclusive_sum(nullptr, tb, d_bytes.as<unsigned long long>(), d_at.as<unsigned long long>(), (size_t)slice + 1, s));
     SAM_TRY(d_tmp.alloc(tb + 256));
-    if (bk::upload_host(d_hits.p, job->hits, nr * sizeof(bk_hit), c->device) || bk::upload_host(d_order.p, job->order, job->n_order * 4, c->device))
+    if (bk::upload_host(d_hits.p, job->hits, n_rec * sizeof(bk_hit), c->device) || bk::upload_host(d_order.p, job->order, job->n_order * 4, c->device))
         return BK_ERR_INTERNAL;
+    // what records carry besides their hits: record -> read, the reads' second segments, the records' trims
+    DevBuf d_src, d_seg2, d_tl, d_tr;
+    if (job->src) {
+        SAM_TRY(d_src.alloc(n_rec * 4));
+        if (bk::upload_host(d_src.p, job->src, n_rec * 4, c->device)) return BK_ERR_INTERNAL;
+    }
+    if (job->seg2) {
+        SAM_TRY(d_seg2.alloc(nr * sizeof(bk_seg2)));
+        if (bk::upload_host(d_seg2.p, job->seg2, nr * sizeof(bk_seg2), c->device)) return BK_ERR_INTERNAL;
+    }
+    if (job->trim_left) {
+        SAM_TRY(d_tl.alloc(n_rec * 2));
+        SAM_TRY(d_tr.alloc(n_rec * 2));
+        if (bk::upload_host(d_tl.p, job->trim_left, n_rec * 2, c->device) || bk::upload_host(d_tr.p, job->trim_right, n_rec * 2, c->device)) return BK_ERR_INTERNAL;
+    }
     {
         std::vector<char> en((size_t)n_ent * 81);
         for (uint32_t e = 0; e < n_ent; e++) memcpy(&en[(size_t)e * 81], c->entries[e].name, 81);
@@ -489,6 +577,9 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     d.pk_words = rd.d_words.as<uint32_t>(); d.pk_wofs = rd.d_wofs.as<uint64_t>(); d.pk_exc = rd.d_exc.as<bk_nbase>(); d.pk_efirst = rd.d_efirst.as<uint32_t>();
     d.n_pk_exc = packed ? job->n_pk_exc : 0;
     d.n_ent = n_ent; d.fmt6 = job->report_unaligned ? 1 : 0; d.pe_mode = job->pe_mode;
+    d.src = job->src ? d_src.as<uint32_t>() : nullptr; d.seg2 = job->seg2 ? d_seg2.as<bk_seg2>() : nullptr;
+    d.trim_l = job->trim_left ? d_tl.as<uint16_t>() : nullptr; d.trim_r = job->trim_left ? d_tr.as<uint16_t>() : nullptr;
+    d.ext = (d.src || d.seg2 || d.trim_l) ? 1 : 0;
     // does any base carry a score at all?  (one streaming pass; without scores - FASTA input, or -g3 - no record is scanned for them)
     DevBuf d_anyq;
     SAM_TRY(d_anyq.alloc(16));
@@ -497,16 +588,21 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     SAM_TRY(hipGetLastError());
     d.any_qual = d_anyq.as<uint32_t>();
     // Everything the device indexes with is checked here first (the command line passes consistent arrays; another caller of the ABI
-    // must get BK_ERR_PARAMS, not an out-of-bounds device access): chrom ids name entries 1..n, order[] names reads, every read lies
-    // inside the bases, names are '\0'-terminated stretches in ascending order inside the name bytes.  A few host threads, slices each.
+    // must get BK_ERR_PARAMS, not an out-of-bounds device access): chrom ids name entries 1..n, order[] names records, src[] names reads,
+    // every read lies inside the bases, names are '\0'-terminated stretches in ascending order inside the name bytes.  (Trims and second
+    // segments only ever become numbers in a line, and both passes make the same ones.)  A few host threads, slices each.
     {
-        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, std::max(nr, job->n_order) >> 16));
+        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(8, std::max(std::max(nr, n_rec), job->n_order) >> 16));
         std::vector<int> bad(nt, 0);
         auto check = [&](unsigned t) {
-            const uint64_t r0 = nr * t / nt, r1 = nr * (t + 1) / nt;
-            for (uint64_t i = r0; i < r1; i++) {
+            const uint64_t c0 = n_rec * t / nt, c1 = n_rec * (t + 1) / nt;
+            for (uint64_t i = c0; i < c1; i++) {
                 const bk_hit &h = job->hits[i];
                 if (h.nar == BK_NAR_ACCEPTED && (h.chrom_id < 1 || h.chrom_id > n_ent)) bad[t] = 1;
+                if (job->src && job->src[i] >= nr) bad[t] = 1;
+            }
+            const uint64_t r0 = nr * t / nt, r1 = nr * (t + 1) / nt;
+            for (uint64_t i = r0; i < r1; i++) {
                 if (!packed) {
                     const uint64_t o = job->offs[i], l = job->lens[i];
                     if (o > job->n_bases || l > job->n_bases - o) bad[t] = 1;
@@ -516,7 +612,7 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
             }
             const uint64_t k0 = job->n_order * t / nt, k1 = job->n_order * (t + 1) / nt;
             for (uint64_t k = k0; k < k1; k++)
-                if (job->order[k] >= nr) bad[t] = 1;
+                if (job->order[k] >= n_rec) bad[t] = 1;
         };
         std::vector<std::thread> th;
         for (unsigned t = 1; t < nt; t++) th.emplace_back(check, t);

@@ -957,12 +957,13 @@ int cmd_align(int argc, char **argv, int first)
     std::vector<bk_hit> &hits = A.hits;
     std::vector<bk_seg2> &seg2 = A.seg2;
     diag("Alignment of %zu from %zu loaded completed", nr, nr);
-    // plain SAM records of a large run are formatted by the device (report.cpp): what it needs of the reads travels there while the
-    // host resolves, filters and sorts
+    // the SAM records of a large run are formatted by the device (report.cpp): what it needs of the reads travels there while the
+    // host resolves, filters and sorts.  The head start is given the READS, in every mode: -r5's records are made later and come with
+    // the job of bk_sam_format, which names the read of each (bk_sam_job.src, n_src_reads = the reads handed over here)
     bk_sam_prep *sam_prep = nullptr;
     bk_sam_job pk_job{};
     struct PrepGuard { bk_sam_prep *&p; Submission &S; ~PrepGuard() { if (p) { S.done_with_head_start(); bk_sam_prep_free(p); p = nullptr; } } } prep_guard{sam_prep, S};      // (not consumed: given back)
-    if (pre.fd >= 0 && o.ml_mode != 5 && !o.micro_indel && !o.splice_len && !o.min_chim && !o.min_flank && nr == rs.lens.size()) {
+    if (pre.fd >= 0 && nr == rs.lens.size()) {
         bk_sam_job hj{};
         hj.bases = rs.bases.data(); hj.n_bases = rs.bases.size(); hj.offs = rs.offs.data(); hj.lens = rs.lens.data();
         hj.names = rs.names.data(); hj.n_name_bytes = rs.names.size(); hj.name_ofs = rs.name_ofs.data(); hj.n_reads = nr;
@@ -986,7 +987,10 @@ int cmd_align(int argc, char **argv, int first)
     for (const char *opt : {"i", "u"})
         if (a.has(opt))
             for (const std::string &fn : a.v[opt]) { struct stat ist; inputs_regular = inputs_regular && stat(fn.c_str(), &ist) == 0 && S_ISREG(ist.st_mode); }
-    const bool may_drop_bases = inputs_regular && pk_job.pk_words != nullptr && sam_prep != nullptr && !a.has("j") && !a.has("J") && !a.has("O") && o.snp.min_reads <= 0;
+    // (.. and not in the modes whose later steps read the bases on the host: the flank trimmer of -x / -A, the .jct / .ind files of -A / -a,
+    // -c's and -r5's records - there the read store stays whole)
+    const bool host_reads_bases = o.ml_mode == 5 || o.micro_indel || o.splice_len || o.min_chim || o.min_flank;
+    const bool may_drop_bases = inputs_regular && !host_reads_bases && pk_job.pk_words != nullptr && sam_prep != nullptr && !a.has("j") && !a.has("J") && !a.has("O") && o.snp.min_reads <= 0;
     if (nr)
         S.release_packed_in_background(pk_job.pk_words != nullptr ? sam_prep : nullptr,
                                        may_drop_bases ? std::function<void()>([&rs, &bases_dropped]() { bk::RawVec<uint8_t> none; rs.bases.swap(none); bases_dropped = true; })

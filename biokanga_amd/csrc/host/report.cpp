@@ -542,12 +542,13 @@ int report_text(Report &R)
             st.n = (size_t)(w - st.d);
             return true;
         };
-        // Plain records - one segment, no end trims, one record per read - are formatted on the device (bk_sam_format): the host
-        // hands over reads, names, records and the output order, and copies the text it gets back, slice by slice, into the file.
-        // Whatever the device path cannot take, or fails on, is formatted below by the host threads.
+        // The records are formatted on the device (bk_sam_format): the host hands over reads, names, records and the output order -
+        // and, where the run has them, the records' end trims (-x, -A, -c), the reads' second segments (-a, -A) and -r5's record -> read
+        // table - and copies the text it gets back, slice by slice, into the file.  format_rec above says what a line is; whatever
+        // the device path cannot take (gzip'd output, pipes), or fails on, is formatted below by the host threads.
         bool device_done = false;
         const size_t dev_min = (size_t)bk::env::sam_device_min(100000ULL);       // (records from which the device formats: tests set it to 1, a huge value keeps the host path)
-        if (R.ctx != nullptr && !out.gz && !out.pipe && R.src.empty() && R.seg2.empty() && R.trims.empty() && nr >= dev_min) {
+        if (R.ctx != nullptr && !out.gz && !out.pipe && nr >= dev_min) {
             const bool timing0 = bk::env::timing();
             timespec t0s; clock_gettime(CLOCK_MONOTONIC, &t0s);
             out.flush();
@@ -610,6 +611,12 @@ int report_text(Report &R)
             if (R.pk_words == nullptr) { job.bases = rs.bases.data(); job.n_bases = rs.bases.size(); job.offs = rs.offs.data(); job.lens = rs.lens.data(); }
             job.names = rs.names.data(); job.n_name_bytes = rs.names.size(); job.name_ofs = rs.name_ofs.data();
             job.hits = hits.data(); job.n_reads = nr; job.order = order.data(); job.n_order = nr;
+            // (index spaces: src, the trims, hits and order go by record; seg2 and everything of the read store by read)
+            const size_t n_rd = rs.lens.size();
+            bool job_ok = R.src.empty() ? n_rd == nr : R.src.size() == nr;
+            if (!R.src.empty()) { job.src = R.src.data(); job.n_src_reads = n_rd; }
+            if (!R.seg2.empty()) { job.seg2 = R.seg2.data(); job_ok = job_ok && R.seg2.size() == n_rd; }
+            if (!R.trims.empty()) { job.trim_left = R.trims.left.data(); job.trim_right = R.trims.right.data(); job_ok = job_ok && R.trims.left.size() == nr && R.trims.right.size() == nr; }
             job.report_unaligned = fmt == 6 ? 1 : 0; job.pe_mode = pe_mode;
             job.pk_words = R.pk_words; job.n_pk_words = R.n_pk_words; job.pk_lens16 = R.pk_lens16; job.pk_exc = R.pk_exc; job.n_pk_exc = R.n_pk_exc;
             job.prep = R.sam_prep;
@@ -617,7 +624,8 @@ int report_text(Report &R)
             uint64_t n_rep = 0, n_bytes = 0;
             int drc = BK_ERR_PARAMS;
             if (bk::env::sam_device_fail()) { if (job.prep) bk_sam_prep_free(job.prep); }       // (tests: the device declines after its head start)
-            else if (rs.lens.size() == nr) drc = bk_sam_format(R.ctx, &job, sink, &st, &n_rep, &n_bytes);
+            else if (job_ok) drc = bk_sam_format(R.ctx, &job, sink, &st, &n_rep, &n_bytes);
+            else if (job.prep) bk_sam_prep_free(job.prep);
             if (drc == BK_OK) {
                 out.pos += (off_t)n_bytes;
                 timespec ta; clock_gettime(CLOCK_MONOTONIC, &ta);

@@ -495,10 +495,24 @@ int  bk_snp_centroid_insts(bk_ctx *ctx, uint32_t chrom_id, int32_t min_reads, ui
  * CAligner::ReportBAMread (biokanga/Aligner.cpp:5768-6126; CSAMfile::AddAlignment, SAMfile.cpp:2100-2283) prints one text line per
  * read; for tens of millions of reads that is byte-parallel work.  bk_sam_format() takes the reads, their names, their records and
  * the order the lines are wanted in (the reference's sort order is the host's business) and hands the lines back as text, in
- * slices: a lane per record measures its line, a prefix sum places it, the lane writes it.  Plain records only - one segment, no
- * end trims (no -a / -A / -c / -x); with pe_mode the reads are interleaved PE1, PE2 and carry the flags bk_pair_batch left.
+ * slices: a lane per record measures its line, a prefix sum places it, the lane writes it.  With pe_mode the reads are interleaved
+ * PE1, PE2 and carry the flags bk_pair_batch left.
  * The sink is called once per slice with the slice's text and its offset within the whole text; up to two calls may run at the
- * same time (on threads of the library), each must return 0.  Lines are those of the reference's SAM body, byte for byte. */
+ * same time (on threads of the library), each must return 0.  Lines are those of the reference's SAM body, byte for byte.
+ *
+ * Two index spaces.  A READ is an entry of the read store; a RECORD is one line to write.  Without `src` they are the same thing:
+ * record i is read i, and n_reads counts both.  With `src` (-r5: a read owns a record per reported locus) n_reads counts the
+ * RECORDS and n_src_reads the reads; record i belongs to read src[i].
+ *   by read:   bases / offs / lens, names / name_ofs, pk_*, seg2 and the head start (`prep`, given the reads alone)
+ *   by record: hits, the entries of order, trim_left / trim_right, src
+ * What a record may carry besides its bk_hit:
+ *   trim_left / trim_right - end trims in read orientation (-x, -A, -c: tsSegLoci.TrimLeft / TrimRight): POS moves to AdjStartLoci,
+ *                            the M run shrinks to AdjHitLen and the trimmed ends are written as soft clips, swapped on the '-' strand;
+ *   seg2 of its read       - a second segment (flags & 5: microInDel or splice junction) adds <gap>N, <n>I or <gap>D and <len2>M
+ *                            to the CIGAR, as CAligner::ReportBAMread does (Aligner.cpp:5986-6033).  Flag bit 3 (chimeric trims
+ *                            travelling in match_len / read_ofs) is NOT read here: hand those over in trim_left / trim_right.
+ * In a paired record PNEXT and TLEN come from the mate's trimmed start and length.  `src` together with pe_mode is BK_ERR_PARAMS
+ * (the reference refuses -r with -U). */
 struct bk_sam_prep;
 typedef struct bk_sam_job {
     const uint8_t  *bases;        /* all reads, 1 byte/base as CAligner holds them (quality in bits 4-7 when loaded)      */
@@ -509,8 +523,8 @@ typedef struct bk_sam_job {
     uint64_t        n_name_bytes;
     const uint64_t *name_ofs;     /* n_reads: start of name i in names                                                     */
     const bk_hit   *hits;         /* n_reads records                                                                       */
-    uint64_t        n_reads;
-    const uint32_t *order;        /* n_order read numbers: the lines in output order                                       */
+    uint64_t        n_reads;      /* reads = records; with `src`: records (the reads are n_src_reads)                      */
+    const uint32_t *order;        /* n_order record numbers: the lines in output order                                     */
     uint64_t        n_order;
     int32_t         report_unaligned;   /* -M6: reads without an accepted alignment get a line too (FLAG 4, YU:Z:<reason>) */
     int32_t         pe_mode;            /* 0, or the -U mode the records were paired under                                 */
@@ -523,6 +537,12 @@ typedef struct bk_sam_job {
     const uint16_t *pk_lens16;
     const bk_nbase *pk_exc;
     uint64_t        n_pk_exc;
+    /* (all NULL / 0 in a job of plain records: one segment, no end trims, a record per read) */
+    const uint32_t *src;          /* NULL, or n_reads entries: record -> read                                              */
+    uint64_t        n_src_reads;  /* with `src`: reads in the read store (ignored without)                                 */
+    const bk_seg2  *seg2;         /* NULL, or one per READ, as bk_batch_seg2() returns them                                */
+    const uint16_t *trim_left;    /* NULL (both), or one per RECORD, read orientation                                      */
+    const uint16_t *trim_right;
 } bk_sam_job;
 /* Optional head start: everything of a job that is known once the reads are aligned - the read store, the names, the buffers the
  * text leaves the device through - can travel while the host still sorts.  bk_sam_prepare() returns at once (a thread of the library
