@@ -19,6 +19,7 @@ EXPORTED_SYMBOLS = [
     "bk_stream_batch_seg2", "bk_stream_release", "bk_stream_drain", "bk_stream_get_stats", "bk_stream_destroy",
     "bk_packed_words", "bk_pack_reads", "bk_align_batch_packed", "bk_stream_submit_packed", "bk_sam_format", "bk_batch_loci_trims", "bk_stream_batch_loci_trims", "bk_stream_submit_device", "bk_sam_prepare", "bk_sam_prep_free",
     "bk_host_register", "bk_host_unregister", "bk_ctx_reserve", "bk_stream_create_packed", "bk_align_batch_device_async", "bk_ctx_create_ex", "bk_ctx_set_chrom_filter", "bk_sam_prep_wait", "bk_debug_intervals", "bk_image_policy",
+    "bk_contam_create", "bk_contam_destroy", "bk_contam_match",
 ]
 
 
@@ -263,6 +264,12 @@ def load_library():
     lib.bk_stream_destroy.restype = None
     lib.bk_sam_format.argtypes = [vp, ctypes.POINTER(_SamJob), _SAM_SINK, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.bk_sam_format.restype = i32
+    lib.bk_contam_create.argtypes = [ctypes.POINTER(vp), i32, vp, u32]
+    lib.bk_contam_create.restype = i32
+    lib.bk_contam_destroy.argtypes = [vp]
+    lib.bk_contam_destroy.restype = None
+    lib.bk_contam_match.argtypes = [vp, vp, vp, vp, u64, vp, i32, i32, i32, vp]
+    lib.bk_contam_match.restype = i32
     _lib = lib
     return lib
 
@@ -331,6 +338,56 @@ def pack_reads(bases, offs, lens, pinned=False):
         pe[:] = exc
         exc = pe
     return words[:nw], lens16[:n], exc
+
+
+class _ContamEntry(ctypes.Structure):
+    _fields_ = [("bases", ctypes.c_void_p), ("len", ctypes.c_uint32), ("use", ctypes.c_uint32)]
+
+
+class ContamMatcher:
+    """bk_contam_*: the contaminant (adaptor) overlaps of `align -H` on a device.  entries: (bases uint8 0..4, use 1..4) pairs."""
+
+    def __init__(self, entries, device=0):
+        lib = load_library()
+        self._seqs = [np.ascontiguousarray(b, dtype=np.uint8) for b, _ in entries]
+        arr = (_ContamEntry * max(len(entries), 1))()
+        for k, (b, (_, use)) in enumerate(zip(self._seqs, entries)):
+            arr[k].bases, arr[k].len, arr[k].use = b.ctypes.data, len(b), int(use)
+        self.h = ctypes.c_void_p()
+        rc = lib.bk_contam_create(ctypes.byref(self.h), device, ctypes.cast(arr, ctypes.c_void_p), len(entries))
+        if rc:
+            self.h = None
+            raise BkError(rc, "bk_contam_create")
+
+    def match(self, bases, offs, lens, is_pe2=None, all_pe2=0, trim5=0, trim3=0):
+        """(n, 2) uint16: bases to cut from the 5' / 3' end of every read beyond the fixed trims.  offs None: reads back to back."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        offs = None if offs is None else np.ascontiguousarray(offs, dtype=np.uint64)
+        pe2 = None if is_pe2 is None else np.ascontiguousarray(is_pe2, dtype=np.uint8)
+        out = np.zeros((len(lens), 2), dtype=np.uint16)
+        rc = load_library().bk_contam_match(self.h, bases.ctypes.data, None if offs is None else offs.ctypes.data, lens.ctypes.data, len(lens),
+                                            None if pe2 is None else pe2.ctypes.data, int(all_pe2), int(trim5), int(trim3), out.ctypes.data)
+        if rc:
+            raise BkError(rc, "bk_contam_match")
+        return out
+
+    def close(self):
+        if self.h:
+            load_library().bk_contam_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def build_sa_device(d_seq_ptr, concat_len, d_sa_ptr, el_size=4, device=0):

@@ -7,7 +7,7 @@
 //
 //   biokanga index -i genome.fa[.gz] [-i more.fa] -o genome.sfx -r name [-l minseqlen] [-d descr] [-t title] [-T threads] [--device n]
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
-//                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-M 0|5|6] [-O stats.csv]
+//                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
 //                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-T host threads] [-F logfile] [--device n | --devices 0-7]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
@@ -49,6 +49,7 @@
 #include "post_filters.h"
 #include "snp.h"
 #include "read_loader.h"
+#include "contaminants.h"
 #include "report.h"
 
 namespace {
@@ -180,6 +181,28 @@ struct HostClock {
     static double now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
     static double wall() { timespec ts; clock_gettime(CLOCK_REALTIME, &ts); return (double)(ts.tv_sec % 60) + 1e-9 * (double)ts.tv_nsec; }      // (the log's seconds)
     void lap(const char *what) { if (!on) return; const double t = now(); fprintf(stderr, "bk timing: host: %-40s %7.1f ms   (done at :%06.3f)\n", what, 1e3 * (t - t0), wall()); t0 = t; }
+};
+
+// The loaders' contaminant matcher (read_loader.h) on a device: bk_contam_* of the library.  A file without a single sequence makes a matcher
+// that cuts nothing (the reference then still prints its count lines).
+struct DeviceContam : ContamMatcher {
+    bk_contam *h = nullptr;
+    ~DeviceContam() override { destroy(); }
+    void destroy() { if (h) bk_contam_destroy(h); h = nullptr; }
+    int create(int device, const std::vector<ContamEntry> &entries)
+    {
+        if (entries.empty()) return BK_OK;
+        std::vector<bk_contam_entry> e(entries.size());
+        for (size_t i = 0; i < entries.size(); i++) { e[i].bases = entries[i].bases.data(); e[i].len = (uint32_t)entries[i].bases.size(); e[i].use = (uint32_t)entries[i].use; }
+        return bk_contam_create(&h, device, e.data(), (uint32_t)e.size());
+    }
+    int match(const uint8_t *bases, const uint32_t *lens, size_t n, bool pe2, int trim5, int trim3, uint16_t *out) override
+    {
+        if (!h) { memset(out, 0, 4 * n); return 0; }
+        const int rc = bk_contam_match(h, bases, nullptr, lens, n, nullptr, pe2 ? 1 : 0, trim5, trim3, out);
+        if (rc) diag("Load: the contaminant matcher failed: %s", bk_strerror(rc));
+        return rc;
+    }
 };
 
 // Everything `biokanga align` was asked for, validated the way kanga.cpp:298-1066 validates it
@@ -809,8 +832,8 @@ int cmd_align(int argc, char **argv, int first)
         {"quality", "g"}, {"device", "device"}, {"devices", "devices"}, {"window-array", "window-array"}, {"index-image", "index-image"}, {"rptsamseqsthres", "4"}, {"pair", "u"}, {"pairminlen", "d"}, {"pairmaxlen", "D"},
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
-        {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7", "EXN", a, err)) {
+        {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
@@ -823,6 +846,24 @@ int cmd_align(int argc, char **argv, int first)
     diag("Subprocess align Version %s starting", kProgVer);
     AlignOpts o;
     if (read_align_opts(a, o)) return 1;
+    // -H: the contaminants file is read and its matcher made on the first device before anything else (CAligner::Align loads it in front of
+    // the index, Aligner.cpp:253-270); the matcher needs no index, so it trims the reads while the index image is still travelling
+    DeviceContam contam;
+    ContamTrimming contam_trims;
+    const bool with_contam = a.has("H") && !a.str("H").empty();
+    if (with_contam) {
+        const std::string cf = a.str("H");
+        char line[4200];
+        snprintf(line, sizeof(line), "Contaminant sequences file: '%s'\n", cf.c_str());      // (a parameter line: no time stamp in front)
+        fputs(line, stdout);
+        if (g_logfile) fputs(line, g_logfile);
+        std::vector<ContamEntry> entries;
+        if (load_contaminants(cf, entries)) { diag("Unable to load contaminate sequences file '%s'", cf.c_str()); return 1; }
+        if (const int crc = contam.create(o.devices[0], entries)) { diag("Fatal: unable to set up the contaminant matcher on device %d: %s", o.devices[0], bk_strerror(crc)); return 1; }
+        contam_trims.matcher = &contam;
+        contam_trims.keep = true;
+    }
+    ContamTrimming *const ct = with_contam ? &contam_trims : nullptr;
 
     // index images travel to the devices (one loader thread each) while this thread parses the reads: the two longest serial steps
     // of a run overlap (the reference loads its reads in the background of the alignment instead, Aligner.cpp:4820-4860)
@@ -888,8 +929,9 @@ int cmd_align(int argc, char **argv, int first)
     // (the index loader's threads - the HIP runtime coming up, four feeding the upload - the page-locking of the packed reads' buffers and
     // the output file's pages run meanwhile: the parser leaves them their share of the cores, or a CPU quota stalls all of them in turn)
     const int parse_threads = std::max(std::min(o.nthreads, 4), o.nthreads - 6);
-    if (o.pe_mode) rc = load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs);
-    else rc = load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs);
+    if (o.pe_mode) rc = load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs, ct);
+    else rc = load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs, ct);
+    contam.destroy();                               // (its staging and device buffers have served)
     // .. and, still behind the index load: the reads packed for the boundary, the result array page-locked
     AlignedSet A;
     // (declared after the read store and A: runs before either goes - the releaser thread may still be giving the read store's bases back)
@@ -1000,8 +1042,11 @@ int cmd_align(int argc, char **argv, int first)
         if (!bases_dropped) return 0;
         diag("The device declined the SAM records: loading the reads again for the host's formatter");
         ReadStore again;
-        const int rl = o.pe_mode ? load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again)
-                                 : load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again);
+        // (-H: the cuts the first load found are used again, nothing is matched a second time)
+        contam_trims.matcher = nullptr;
+        contam_trims.replay_at = 0;
+        const int rl = o.pe_mode ? load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again, ct)
+                                 : load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again, ct);
         if (rl || again.size() != rs.size()) return 1;
         rs.bases.swap(again.bases); rs.offs.swap(again.offs); rs.used_bases = again.used_bases;
         bases_dropped = false;

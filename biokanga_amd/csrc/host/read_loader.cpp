@@ -12,6 +12,26 @@ namespace bkcli {
 
 namespace {
 
+// The contaminant cuts of `n` reads lying back to back (two per read): matched now, or - a load repeated - the next of the record
+int contam_cuts(ContamTrimming &ct, const uint8_t *bases, const uint32_t *lens, size_t n, bool pe2, int trim5, int trim3, uint16_t *out)
+{
+    if (ct.matcher) return n ? ct.matcher->match(bases, lens, n, pe2, trim5, trim3, out) : 0;
+    if (ct.replay_at + 2 * n > ct.trims.size()) { diag("Load: the read files hold more reads than when they were first loaded"); return -63; }
+    if (n) memcpy(out, ct.trims.data() + ct.replay_at, 4 * n);
+    ct.replay_at += 2 * n;
+    return 0;
+}
+
+// the reference's count lines (Aligner.cpp:11403-11407,11420-11424), worded as it words them
+void contam_lines(const uint64_t n[4], bool pairs)
+{
+    diag("Load: total of %d sequences PE1 sequences were 5' contaminate trimmed", (int)n[0]);
+    diag("Load: total of %d sequences PE1 sequences were 3' contaminate trimmed", (int)n[1]);
+    if (!pairs) return;
+    diag("Load: total of %d sequences PE1 sequences were 5' contaminant trimmed", (int)n[2]);
+    diag("Load: total of %d sequences PE1 sequences were 3' contaminant trimmed", (int)n[3]);
+}
+
 // The acceptance rules of load_reads() applied to a file that was parsed whole (fasta.h, ParsedChunk): every
 // chunk is filtered and measured by its own thread, a prefix sum gives each chunk its place in the read
 // store, and the threads copy their accepted records there.  Same records, same order, same log lines.
@@ -19,7 +39,7 @@ namespace {
 // offsets point there - no placement pass over the 5 GB of a 50 M-read file; only the names are laid back to back.  A second input
 // file is appended to the store by copy.
 int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int trim3, int min_len, int max_len,
-                  int nthreads, ReadStore &rs)
+                  int nthreads, ReadStore &rs, ContamTrimming *ct)
 {
     std::vector<bk::ParsedChunk> &chunks = file.chunks;
     const size_t nc = chunks.size();
@@ -31,8 +51,30 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
             sim = dl >= 14 && (!strncmp(c.descr, "lcl|usimreads|", 14) || !strncmp(c.descr, "lcr|usimreads|", 14));
             break;
         }
-    struct Tot { uint64_t n_acc = 0, n_bases = 0, n_names = 0, n_under = 0, n_over = 0, n_rec = 0; long bad_at = -1; };
+    struct Tot { uint64_t n_acc = 0, n_bases = 0, n_names = 0, n_under = 0, n_over = 0, n_rec = 0, n_c5 = 0, n_c3 = 0; long bad_at = -1; };
     std::vector<Tot> tot(nc);
+    // -H: the cuts of every record (two each), chunk after chunk - all of them before anything is decided, like the reference matches every
+    // read in front of its length rules
+    std::vector<uint64_t> rec0(nc + 1, 0);
+    bk::RawVec<uint16_t> cut;
+    uint16_t *cutp = nullptr;
+    if (ct) {
+        for (size_t ci = 0; ci < nc; ci++) rec0[ci + 1] = rec0[ci] + chunks[ci].lens.size();
+        // (a load that keeps its cuts for a reload matches straight into that record, a reload reads them where they lie: one copy)
+        const size_t kept_at = ct->matcher ? ct->trims.size() : ct->replay_at;
+        const bool in_record = !ct->matcher || ct->keep;
+        if (ct->matcher && ct->keep) ct->trims.resize(kept_at + 2 * rec0[nc]);
+        if (!in_record) cut.resize(2 * rec0[nc]);
+        else if (kept_at + 2 * rec0[nc] > ct->trims.size()) { diag("Load: the read files hold more reads than when they were first loaded"); return -63; }
+        cutp = in_record ? ct->trims.data() + kept_at : cut.data();
+        if (ct->matcher)
+            for (size_t ci = 0; ci < nc; ci++) {
+                const int rc = contam_cuts(*ct, chunks[ci].bases, chunks[ci].lens.data(), chunks[ci].lens.size(), false, trim5, trim3, cutp + 2 * rec0[ci]);
+                if (rc) return rc;
+            }
+        else
+            ct->replay_at += 2 * rec0[nc];
+    }
     std::vector<std::vector<uint32_t>> keep_name_len(nc);       // per record: accepted name length + 1, or 0 when sloughed
     auto name_len = [](const char *d, size_t dl, bool sim_) {
         if (dl > 127) dl = 127;
@@ -59,6 +101,7 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         const uint32_t *lens_ = c.lens.data(), *dlens_ = c.descr_lens.data();
         const char *descr_ = c.descr;
         Tot t;
+        const uint16_t *cut_ = ct ? cutp + 2 * rec0[ci] : nullptr;
         auto &kn_v = keep_name_len[ci];
         kn_v.assign(n_rec, 0);
         uint32_t *kn = kn_v.data();
@@ -66,16 +109,19 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         for (size_t i = 0; i < n_rec; i++) {
             const int len = (int)lens_[i];
             const size_t dl = dlens_[i];
+            const int c5 = cut_ ? (int)cut_[2 * i] : 0, c3 = cut_ ? (int)cut_[2 * i + 1] : 0;
             t.n_rec++;
             if (len < 1 || len > 0x30000) { if (t.bad_at < 0) t.bad_at = (long)i; }
-            else if (t5 + t3 + mn > len) t.n_under++;
-            else if (t5 + t3 + mx < len) t.n_over++;
+            else if (t5 + t3 + c5 + c3 + mn > len) t.n_under++;
+            else if (t5 + t3 + c5 + c3 + mx < len) t.n_over++;
             else {
                 size_t nl = name_len(descr_ + dofs, dl, sim_);
                 kn[i] = (uint32_t)nl + 1;
                 t.n_acc++;
-                t.n_bases += (uint64_t)(len - t5 - t3);
+                t.n_bases += (uint64_t)(len - t5 - t3 - c5 - c3);
                 t.n_names += nl + 1;
+                t.n_c5 += c5 > 0;
+                t.n_c3 += c3 > 0;
             }
             dofs += dl;
         }
@@ -90,8 +136,9 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         if (tot[ci].bad_at >= 0 || (n_under < 10 && tot[ci].n_under) || (n_over < 10 && tot[ci].n_over))
             for (size_t i = 0; i < upto; i++) {
                 const int len = (int)c.lens[i];
-                if (trim5 + trim3 + min_len > len) { if (++n_under <= 10) diag("Load: under length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str()); }
-                else if (trim5 + trim3 + max_len < len) { if (++n_over <= 10) diag("Load: over length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str()); }
+                const int cc = ct ? (int)cutp[2 * (rec0[ci] + i)] + (int)cutp[2 * (rec0[ci] + i) + 1] : 0;
+                if (trim5 + trim3 + cc + min_len > len) { if (++n_under <= 10) diag("Load: under length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str()); }
+                else if (trim5 + trim3 + cc + max_len < len) { if (++n_over <= 10) diag("Load: over length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str()); }
             }
         else { n_under += tot[ci].n_under; n_over += tot[ci].n_over; }
         if (tot[ci].bad_at >= 0) { diag("Problem parsing sequence after %llu reads parsed", (unsigned long long)(n_descr + tot[ci].bad_at + 1)); return -63; }
@@ -118,6 +165,7 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         const bool adopt_ = adopt;
         const uint8_t *cbases = c.bases;
         const char *descr_ = c.descr;
+        const uint16_t *cut_ = ct ? cutp + 2 * rec0[ci] : nullptr;
         const uint64_t chunk_at = adopt_ ? (uint64_t)(c.bases - file.bases.data()) : 0;
         uint32_t *o_lens = rs.lens.data();
         uint64_t *o_offs = rs.offs.data(), *o_nofs = rs.name_ofs.data();
@@ -128,12 +176,13 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         for (size_t i = 0; i < n_rec; i++) {
             const uint32_t len = lens_[i];
             if (kn[i]) {
-                const uint32_t keep = len - t5 - t3, nl = kn[i] - 1;
+                const uint32_t c5 = cut_ ? cut_[2 * i] : 0u, c3 = cut_ ? cut_[2 * i + 1] : 0u;
+                const uint32_t keep = len - t5 - t3 - c5 - c3, nl = kn[i] - 1;
                 o_lens[r] = keep;
-                if (adopt_) o_offs[r] = chunk_at + sofs + (uint64_t)t5;
+                if (adopt_) o_offs[r] = chunk_at + sofs + (uint64_t)t5 + c5;
                 else {
                     o_offs[r] = bo;
-                    memcpy(o_bases + bo, cbases + sofs + t5, keep);
+                    memcpy(o_bases + bo, cbases + sofs + t5 + c5, keep);
                 }
                 o_nofs[r] = mo;                                // (the names - a tenth of the bases - are laid back to back)
                 memcpy(o_names + mo, descr_ + dofs, nl);
@@ -151,6 +200,11 @@ int accept_chunks(bk::ParsedFile &file, const std::string &fn, int trim5, int tr
         rs.used_bases = 0;
     diag("Load: %llu reads parsed, %llu accepted, %llu under length, %llu over length from '%s'", (unsigned long long)n_descr,
          (unsigned long long)n_acc, (unsigned long long)n_under, (unsigned long long)n_over, fn.c_str());
+    if (ct) {
+        uint64_t nct[4] = {0, 0, 0, 0};
+        for (const Tot &t : tot) { nct[0] += t.n_c5; nct[1] += t.n_c3; }
+        contam_lines(nct, false);
+    }
     g_whole_file_loads++;
     return 0;
 }
@@ -162,7 +216,35 @@ int g_qual_mode = 3;
 int g_sample_nth = 1;
 int g_whole_file_loads = 0;
 
-int load_reads(const std::vector<std::string> &files, int trim5, int trim3, int min_len, int max_len, int nthreads, ReadStore &rs)
+namespace {
+
+// Records of the record-by-record loops waiting for their contaminant cuts: the matcher works on many reads at a time, so the loops put what
+// they read aside - bases and descriptors copied, the reader's buffers do not last - and accept a batch at a time, in file order.
+struct PendingReads {
+    std::vector<uint8_t> bases;
+    std::vector<char> descr;
+    std::vector<uint32_t> lens, dlens;
+    std::vector<uint16_t> cut;
+    void add(const char *d, size_t dl, const uint8_t *b, size_t bl)
+    {
+        bases.insert(bases.end(), b, b + bl);
+        descr.insert(descr.end(), d, d + dl);
+        lens.push_back((uint32_t)bl);
+        dlens.push_back((uint32_t)dl);
+    }
+    size_t size() const { return lens.size(); }
+    void clear() { bases.clear(); descr.clear(); lens.clear(); dlens.clear(); }
+    int cuts(ContamTrimming &ct, bool pe2, int trim5, int trim3)
+    {
+        cut.resize(2 * lens.size());
+        return contam_cuts(ct, bases.data(), lens.data(), lens.size(), pe2, trim5, trim3, cut.data());
+    }
+};
+constexpr size_t kPendingReads = 1u << 16;
+
+}  // namespace
+
+int load_reads(const std::vector<std::string> &files, int trim5, int trim3, int min_len, int max_len, int nthreads, ReadStore &rs, ContamTrimming *ct)
 {
     for (const std::string &fn : files) {
         bk::RecordStream rd;
@@ -172,7 +254,7 @@ int load_reads(const std::vector<std::string> &files, int trim5, int trim3, int 
         if (rc) { diag("Load: %s", err.c_str()); return rc; }
         diag("Loading reads from '%s'", fn.c_str());
         if (rd.parsed() && g_sample_nth <= 1) {
-            rc = accept_chunks(rd.file(), fn, trim5, trim3, min_len, max_len, nthreads, rs);
+            rc = accept_chunks(rd.file(), fn, trim5, trim3, min_len, max_len, nthreads, rs, ct);
             if (rc) return rc;
             continue;
         }
@@ -181,7 +263,49 @@ int load_reads(const std::vector<std::string> &files, int trim5, int trim3, int 
         size_t dl, bl;
         bool sim = false;
         uint32_t n_descr = 0, n_under = 0, n_over = 0, n_acc = 0;
+        uint64_t nct[4] = {0, 0, 0, 0};
         int nxt_sample = g_sample_nth;
+        // the length rules and the store, for a read whose contaminant cuts (0 without -H) are known
+        auto accept = [&](const char *d, size_t dl, const uint8_t *b, int len, int c5, int c3) {
+            if (trim5 + trim3 + c5 + c3 + min_len > len) {
+                if (++n_under <= 10) diag("Load: under length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str());
+                return;
+            }
+            if (trim5 + trim3 + c5 + c3 + max_len < len) {
+                if (++n_over <= 10) diag("Load: over length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str());
+                return;
+            }
+            if (!sim) {                                                   // cut at first whitespace, < cMaxDescrIDLen
+                size_t k = 0;
+                while (k < 79 && k < dl && !isspace((unsigned char)d[k])) k++;
+                dl = k;
+            }
+            int keep = len - trim5 - trim3 - c5 - c3;
+            rs.offs.push_back(rs.bases.size());
+            rs.lens.push_back((uint32_t)keep);
+            rs.bases.insert(rs.bases.end(), b + trim5 + c5, b + trim5 + c5 + keep);
+            rs.name_ofs.push_back(rs.names.size());
+            rs.names.insert(rs.names.end(), d, d + dl);
+            rs.names.push_back('\0');
+            n_acc++;
+            nct[0] += c5 > 0;
+            nct[1] += c3 > 0;
+        };
+        PendingReads pend;
+        auto flush = [&]() -> int {
+            if (!pend.size()) return 0;
+            const int mrc = pend.cuts(*ct, false, trim5, trim3);
+            if (mrc) return mrc;
+            if (ct->matcher && ct->keep) ct->trims.insert(ct->trims.end(), pend.cut.begin(), pend.cut.end());
+            size_t bo = 0, dofs = 0;
+            for (size_t i = 0; i < pend.size(); i++) {
+                accept(pend.descr.data() + dofs, pend.dlens[i], pend.bases.data() + bo, (int)pend.lens[i], pend.cut[2 * i], pend.cut[2 * i + 1]);
+                bo += pend.lens[i];
+                dofs += pend.dlens[i];
+            }
+            pend.clear();
+            return 0;
+        };
         while ((rc = rd.next(d, dl, b, bl)) > 0) {
             n_descr++;
             if (dl > 127) dl = 127;                                       // cMaxDescrLen-1
@@ -191,32 +315,19 @@ int load_reads(const std::vector<std::string> &files, int trim5, int trim3, int 
                 if (g_sample_nth > nxt_sample) continue;
                 nxt_sample = 0;
             }
-            int len = (int)bl;
-            if (bl < 1 || bl > 0x30000) { diag("Problem parsing sequence after %u reads parsed", n_descr); return -63; }
-            if (trim5 + trim3 + min_len > len) {
-                if (++n_under <= 10) diag("Load: under length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str());
-                continue;
+            if (bl < 1 || bl > 0x30000) {
+                if (ct && (rc = flush())) return rc;
+                diag("Problem parsing sequence after %u reads parsed", n_descr);
+                return -63;
             }
-            if (trim5 + trim3 + max_len < len) {
-                if (++n_over <= 10) diag("Load: over length (%d) sequence in '%s' after end trims has been sloughed..", len, fn.c_str());
-                continue;
-            }
-            if (!sim) {                                                   // cut at first whitespace, < cMaxDescrIDLen
-                size_t k = 0;
-                while (k < 79 && k < dl && !isspace((unsigned char)d[k])) k++;
-                dl = k;
-            }
-            int keep = len - trim5 - trim3;
-            rs.offs.push_back(rs.bases.size());
-            rs.lens.push_back((uint32_t)keep);
-            rs.bases.insert(rs.bases.end(), b + trim5, b + trim5 + keep);
-            rs.name_ofs.push_back(rs.names.size());
-            rs.names.insert(rs.names.end(), d, d + dl);
-            rs.names.push_back('\0');
-            n_acc++;
+            if (!ct) { accept(d, dl, b, (int)bl, 0, 0); continue; }
+            pend.add(d, dl, b, bl);
+            if (pend.size() >= kPendingReads && (rc = flush())) return rc;
         }
+        if (ct) { const int frc = flush(); if (frc) return frc; }
         if (rc < 0) { diag("Load: errors whilst parsing '%s'", fn.c_str()); return rc; }
         diag("Load: %u reads parsed, %u accepted, %u under length, %u over length from '%s'", n_descr, n_acc, n_under, n_over, fn.c_str());
+        if (ct) contam_lines(nct, false);
     }
     return 0;
 }
@@ -232,7 +343,7 @@ namespace {
 // Returns 0, a negative code after the message the serial loop would have printed, or 1 when the files are not eligible (then the
 // serial loop runs).
 int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, const std::string &nb, int trim5, int trim3, int min_len, int max_len,
-                 int nthreads, ReadStore &rs)
+                 int nthreads, ReadStore &rs, ContamTrimming *ct)
 {
     bk::ParsedFile *F[2] = {&fa, &fb};
     size_t nc[2], N[2];
@@ -258,6 +369,32 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
     bk::RawVec<uint8_t> st[2], nl[2];
     bk::RawVec<uint32_t> kl[2];
     for (int e = 0; e < 2; e++) { st[e].resize(P); nl[e].resize(P); kl[e].resize(P); }
+    // -H: the cuts of either file's first P records (two each), every one of them in front of the length rules
+    bk::RawVec<uint16_t> cut[2];
+    if (ct) {
+        for (int e = 0; e < 2; e++) cut[e].resize(2 * P);
+        if (ct->matcher) {
+            for (int e = 0; e < 2; e++)
+                for (size_t c = 0; c < nc[e] && r0[e][c] < P; c++) {
+                    const bk::ParsedChunk &pc = F[e]->chunks[c];
+                    const size_t n = std::min<size_t>(pc.lens.size(), P - r0[e][c]);
+                    const int rc = contam_cuts(*ct, pc.bases, pc.lens.data(), n, e == 1, trim5, trim3, cut[e].data() + 2 * r0[e][c]);
+                    if (rc) return rc;
+                }
+            if (ct->keep) {
+                const size_t at = ct->trims.size();
+                ct->trims.resize(at + 4 * P);
+                for (size_t g = 0; g < P; g++)
+                    for (int e = 0; e < 2; e++) { ct->trims[at + 4 * g + 2 * e] = cut[e][2 * g]; ct->trims[at + 4 * g + 2 * e + 1] = cut[e][2 * g + 1]; }
+            }
+        } else {
+            if (ct->replay_at + 4 * P > ct->trims.size()) { diag("Load: the read files hold more reads than when they were first loaded"); return -63; }
+            const uint16_t *t = ct->trims.data() + ct->replay_at;
+            for (size_t g = 0; g < P; g++)
+                for (int e = 0; e < 2; e++) { cut[e][2 * g] = t[4 * g + 2 * e]; cut[e][2 * g + 1] = t[4 * g + 2 * e + 1]; }
+            ct->replay_at += 4 * P;
+        }
+    }
     auto run = [&](size_t n_items, auto fn_) {
         std::vector<std::thread> th;
         std::atomic<size_t> next{0};
@@ -277,21 +414,23 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
         const char *descr_ = c.descr;
         uint8_t *st_ = st[e].data(), *nl_ = nl[e].data();
         uint32_t *kl_ = kl[e].data();
+        const uint16_t *cut_ = ct ? cut[e].data() : nullptr;
         const size_t n_rec = c.lens.size(), pairs = P;
         size_t dofs = 0;
         for (size_t i = 0; i < n_rec && g0 + i < pairs; i++) {
             const int len = (int)lens_[i];
             size_t dl = dlens_[i];
+            const int cc = cut_ ? (int)cut_[2 * (g0 + i)] + (int)cut_[2 * (g0 + i) + 1] : 0;
             uint8_t s = 0;
             if (len < 1 || len > 0x30000) s = 3;
-            else if (t5 + t3 + mn > len) s = 1;
-            else if (t5 + t3 + mx < len) s = 2;
+            else if (t5 + t3 + cc + mn > len) s = 1;
+            else if (t5 + t3 + cc + mx < len) s = 2;
             if (dl > 127) dl = 127;
             size_t q = dl;
             if (!sim_) { q = 0; while (q < 79 && q < dl && !isspace((unsigned char)descr_[dofs + q])) q++; }
             st_[g0 + i] = s;
             nl_[g0 + i] = (uint8_t)(q + 1);
-            kl_[g0 + i] = s == 0 ? (uint32_t)(len - t5 - t3) : 0u;
+            kl_[g0 + i] = s == 0 ? (uint32_t)(len - t5 - t3 - cc) : 0u;
             dofs += dlens_[i];
         }
     });
@@ -340,6 +479,7 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
         const uint8_t *cbases = c.bases;
         const char *descr_ = c.descr;
         const uint32_t t5 = (uint32_t)trim5;
+        const uint16_t *cut_ = ct ? cut[e].data() : nullptr;
         uint32_t *o_lens = rs.lens.data() + rd_at;
         uint64_t *o_offs = rs.offs.data() + rd_at, *o_nofs = rs.name_ofs.data() + rd_at;
         uint8_t *o_bases = rs.bases.data();
@@ -359,7 +499,7 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
                 const uint32_t keep = e ? kb[g] : ka[g], nlen = (uint32_t)(e ? lb[g] : la[g]) - 1;
                 o_lens[r] = keep;
                 o_offs[r] = my_b;
-                memcpy(o_bases + my_b, cbases + sofs + t5, keep);
+                memcpy(o_bases + my_b, cbases + sofs + t5 + (cut_ ? cut_[2 * g] : 0u), keep);
                 o_nofs[r] = my_m;
                 memcpy(o_names + my_m, descr_ + dofs, nlen);
                 o_names[my_m + nlen] = '\0';
@@ -370,6 +510,13 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
         }
     });
     diag("Load: %u pairs parsed, %u accepted, %u under length, %u over length", (uint32_t)P, (uint32_t)K, (uint32_t)n_under, (uint32_t)n_over);
+    if (ct) {
+        uint64_t nct[4] = {0, 0, 0, 0};
+        for (size_t g = 0; g < P; g++)
+            if (st[0][g] == 0 && st[1][g] == 0)
+                for (int e = 0; e < 2; e++) { nct[2 * e] += cut[e][2 * g] > 0; nct[2 * e + 1] += cut[e][2 * g + 1] > 0; }
+        contam_lines(nct, true);
+    }
     (void)na; (void)nb;
     g_whole_file_loads += 2;
     return 0;
@@ -378,7 +525,7 @@ int accept_pairs(bk::ParsedFile &fa, bk::ParsedFile &fb, const std::string &na, 
 }  // namespace
 
 int load_reads_pe(const std::vector<std::string> &f1, const std::vector<std::string> &f2, int trim5, int trim3, int min_len, int max_len,
-                  int nthreads, ReadStore &rs)
+                  int nthreads, ReadStore &rs, ContamTrimming *ct)
 {
     for (size_t k = 0; k < f1.size(); k++) {
         bk::RecordStream rd[2];
@@ -401,7 +548,7 @@ int load_reads_pe(const std::vector<std::string> &f1, const std::vector<std::str
         if (rc || rc2) { diag("Load: %s", err.c_str()); return rc ? rc : rc2; }
         diag("Loading paired end reads from '%s' and '%s'", f1[k].c_str(), f2[k].c_str());
         if (rd[0].parsed() && rd[1].parsed() && g_sample_nth <= 1) {
-            rc = accept_pairs(rd[0].file(), rd[1].file(), f1[k], f2[k], trim5, trim3, min_len, max_len, nthreads, rs);
+            rc = accept_pairs(rd[0].file(), rd[1].file(), f1[k], f2[k], trim5, trim3, min_len, max_len, nthreads, rs, ct);
             if (rc < 0) return rc;
             if (rc == 0) continue;
         }
@@ -410,7 +557,66 @@ int load_reads_pe(const std::vector<std::string> &f1, const std::vector<std::str
         size_t dl[2], bl[2];
         bool sim[2] = {false, false};
         uint32_t n_descr = 0, n_under = 0, n_over = 0, n_acc = 0;
+        uint64_t nct[4] = {0, 0, 0, 0};
         int nxt_sample = g_sample_nth;
+        // the length rules and the store, for a pair whose contaminant cuts (0 without -H) are known: cuts[e] = {5', 3'} of mate e
+        auto accept = [&](const char *const d_[2], size_t dl_[2], const uint8_t *const b_[2], const size_t bl_[2], const uint16_t cuts[2][2]) {
+            for (int e = 0; e < 2; e++) {
+                const int len = (int)bl_[e], cc = (int)cuts[e][0] + (int)cuts[e][1];
+                if (trim5 + trim3 + cc + min_len > len) { n_under++; return; }
+                if (trim5 + trim3 + cc + max_len < len) { n_over++; return; }
+            }
+            for (int e = 0; e < 2; e++) {
+                if (!sim[e]) {
+                    size_t q = 0;
+                    while (q < 79 && q < dl_[e] && !isspace((unsigned char)d_[e][q])) q++;
+                    dl_[e] = q;
+                }
+                const int c5 = (int)cuts[e][0], keep = (int)bl_[e] - trim5 - trim3 - c5 - (int)cuts[e][1];
+                rs.offs.push_back(rs.bases.size());
+                rs.lens.push_back((uint32_t)keep);
+                rs.bases.insert(rs.bases.end(), b_[e] + trim5 + c5, b_[e] + trim5 + c5 + keep);
+                rs.name_ofs.push_back(rs.names.size());
+                rs.names.insert(rs.names.end(), d_[e], d_[e] + dl_[e]);
+                rs.names.push_back('\0');
+                nct[2 * e] += cuts[e][0] > 0;
+                nct[2 * e + 1] += cuts[e][1] > 0;
+            }
+            n_acc++;
+        };
+        const uint16_t no_cuts[2][2] = {{0, 0}, {0, 0}};
+        PendingReads pend[2];
+        auto flush = [&]() -> int {
+            const size_t np = pend[0].size();
+            if (!np) return 0;
+            if (ct->matcher) {
+                for (int e = 0; e < 2; e++) { const int mrc = pend[e].cuts(*ct, e == 1, trim5, trim3); if (mrc) return mrc; }
+                if (ct->keep)
+                    for (size_t i = 0; i < np; i++)
+                        for (int e = 0; e < 2; e++) { ct->trims.push_back(pend[e].cut[2 * i]); ct->trims.push_back(pend[e].cut[2 * i + 1]); }
+            } else {
+                if (ct->replay_at + 4 * np > ct->trims.size()) { diag("Load: the read files hold more reads than when they were first loaded"); return -63; }
+                for (int e = 0; e < 2; e++) pend[e].cut.resize(2 * np);
+                for (size_t i = 0; i < np; i++)
+                    for (int e = 0; e < 2; e++) { pend[e].cut[2 * i] = ct->trims[ct->replay_at + 4 * i + 2 * e]; pend[e].cut[2 * i + 1] = ct->trims[ct->replay_at + 4 * i + 2 * e + 1]; }
+                ct->replay_at += 4 * np;
+            }
+            size_t bo[2] = {0, 0}, dofs[2] = {0, 0};
+            for (size_t i = 0; i < np; i++) {
+                const char *d_[2];
+                const uint8_t *b_[2];
+                size_t dl_[2], bl_[2];
+                uint16_t cuts[2][2];
+                for (int e = 0; e < 2; e++) {
+                    d_[e] = pend[e].descr.data() + dofs[e]; dl_[e] = pend[e].dlens[i]; b_[e] = pend[e].bases.data() + bo[e]; bl_[e] = pend[e].lens[i];
+                    cuts[e][0] = pend[e].cut[2 * i]; cuts[e][1] = pend[e].cut[2 * i + 1];
+                    bo[e] += pend[e].lens[i]; dofs[e] += pend[e].dlens[i];
+                }
+                accept(d_, dl_, b_, bl_, cuts);
+            }
+            pend[0].clear(); pend[1].clear();
+            return 0;
+        };
         for (;;) {
             int rc1 = rd[0].next(d[0], dl[0], b[0], bl[0]);
             if (rc1 < 0) { diag("Load: errors whilst parsing '%s'", f1[k].c_str()); return rc1; }
@@ -418,7 +624,6 @@ int load_reads_pe(const std::vector<std::string> &f1, const std::vector<std::str
             int rc2 = rd[1].next(d[1], dl[1], b[1], bl[1]);
             if (rc2 <= 0) { diag("Load: '%s' has fewer reads than '%s'", f2[k].c_str(), f1[k].c_str()); return -63; }
             n_descr++;
-            bool skip = false;
             for (int e = 0; e < 2; e++) {
                 if (dl[e] > 127) dl[e] = 127;
                 if (n_descr == 1) sim[e] = dl[e] >= 14 && (!strncmp(d[e], "lcl|usimreads|", 14) || !strncmp(d[e], "lcr|usimreads|", 14));
@@ -429,29 +634,13 @@ int load_reads_pe(const std::vector<std::string> &f1, const std::vector<std::str
                 if (g_sample_nth > nxt_sample) continue;
                 nxt_sample = 0;
             }
-            for (int e = 0; e < 2 && !skip; e++) {
-                int len = (int)bl[e];
-                if (trim5 + trim3 + min_len > len) { n_under++; skip = true; }
-                else if (trim5 + trim3 + max_len < len) { n_over++; skip = true; }
-            }
-            if (skip) continue;
-            for (int e = 0; e < 2; e++) {
-                if (!sim[e]) {
-                    size_t q = 0;
-                    while (q < 79 && q < dl[e] && !isspace((unsigned char)d[e][q])) q++;
-                    dl[e] = q;
-                }
-                int keep = (int)bl[e] - trim5 - trim3;
-                rs.offs.push_back(rs.bases.size());
-                rs.lens.push_back((uint32_t)keep);
-                rs.bases.insert(rs.bases.end(), b[e] + trim5, b[e] + trim5 + keep);
-                rs.name_ofs.push_back(rs.names.size());
-                rs.names.insert(rs.names.end(), d[e], d[e] + dl[e]);
-                rs.names.push_back('\0');
-            }
-            n_acc++;
+            if (!ct) { accept(d, dl, b, bl, no_cuts); continue; }
+            for (int e = 0; e < 2; e++) pend[e].add(d[e], dl[e], b[e], bl[e]);
+            if (pend[0].size() >= kPendingReads) { const int frc = flush(); if (frc) return frc; }
         }
+        if (ct) { const int frc = flush(); if (frc) return frc; }
         diag("Load: %u pairs parsed, %u accepted, %u under length, %u over length", n_descr, n_acc, n_under, n_over);
+        if (ct) contam_lines(nct, true);
     }
     return 0;
 }

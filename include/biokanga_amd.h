@@ -580,6 +580,30 @@ int  bk_debug_intervals(bk_ctx *ctx, uint32_t cap_reads, uint32_t *n_act, uint32
 int  bk_build_sa_device(const void *d_seq, uint64_t concat_len, void *d_sa_out, int sfx_el_size,
                         int device_id);
 
+/* ---- contaminant (adaptor) overlaps of raw reads: `align -H` (CContaminants::MatchContaminants, Contaminants.cpp:1227-1309) ----
+ * Independent of bk_ctx: a matcher needs a device, not an index, and can work while an index image is still on its way to the same device.
+ * An entry is one (sequence, use) of a contaminants file as the reference keeps it: bases 0..3 a,c,g,t and 4 N, 4..200 of them, already reverse
+ * complemented where the file asks for that; use 1 = 5' end of SE/PE1 reads, 2 = 5' of PE2, 3 = 3' of SE/PE1, 4 = 3' of PE2.  At most 1600.
+ * bk_contam_match: for every read (1 byte/base as the loaders hold them - bits 0..2 the base, the rest ignored; offs == NULL: the reads lie back
+ * to back) out[2i] / out[2i+1] = the bases the reference's loader would cut from its 5' / 3' end beyond the fixed trims: with L the largest
+ * overlap length, trim + 1 <= L <= min(read, longest entry of the use), at which an entry of at least L bases differs in at most one
+ * position from the read's first L bases (its own last L; 5') or the read's last L (its own first L; 3') - a read N always differs, an entry N never -
+ * L - trim, and 0 without such an L, without entries of the use, and for reads shorter than 20 or longer than 2000 bases.  is_pe2: per read,
+ * non-zero = a PE2 read (uses 2 and 4); NULL: all_pe2 (0 | 1) holds for every read.
+ * The reads cross in chunks of at most 64 MB of bases / 2^20 reads through page-locked staging on a stream of the matcher's own, two in flight:
+ * under 160 MB of device memory and as much page-locked host memory (allocated by the first match call) whatever the number of reads.
+ * Calls on one matcher must not overlap.  BK_ERR_PARAMS: a NULL array, an entry outside the limits above, a negative trim, all_pe2 not 0 | 1. */
+typedef struct bk_contam bk_contam;
+typedef struct bk_contam_entry {
+    const uint8_t *bases;
+    uint32_t len;
+    uint32_t use;
+} bk_contam_entry;
+int  bk_contam_create(bk_contam **out, int device_id, const bk_contam_entry *entries, uint32_t n_entries);
+void bk_contam_destroy(bk_contam *c);
+int  bk_contam_match(bk_contam *c, const uint8_t *bases, const uint64_t *offs, const uint32_t *lens, uint64_t nreads, const uint8_t *is_pe2,
+                     int all_pe2, int trim5, int trim3, uint16_t *out);
+
 #ifdef __cplusplus
 }
 #endif
