@@ -363,8 +363,10 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                     HIP_TRY(dev_malloc(&c->d_slist_stage, (lanes + (kListStripes + 2) * 1024) * 4));     // its striped form (StripeSet)
                     c->cap_slist = lanes;
                 }
-                // interval counts of the slots this phase can use, zeroed (empty search results store nothing)
-                launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, s);
+                // (no clearing of the interval records: pass A stores the slot of every core a read has, empty results included, or hands
+                // it to pass B, which stores it on every path; the consumers never look at a core the read does not have.  "iv_poison"
+                // puts ones into the slots this phase can use, so that a slot read without having been written shows.)
+                if (c->iv_poison) launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
                 hipEvent_t ea = tm.begin(s);
                 launch_search_a(c->ix, c->cfg, b, c->d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, c->d_slist, ctl_p + 2,
                                 c->d_slist_stage, c->d_stripe_cnt, s);
@@ -1147,10 +1149,20 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
     if (!act || !first || !count || ctl.n_act > cap_reads || ctl.n_act > c->dbg_n) return BK_ERR_PARAMS;
     const uint32_t na = ctl.n_act, stride = c->dbg_n, planes = 2 * c->dbg_ivc;
     HIP_TRY(hipMemcpy(act, c->d_act[c->dbg_cur], (size_t)na * 4, hipMemcpyDeviceToHost));
+    // cores of every listed read in that phase: the search writes no slot beyond them, and like the kernels behind it this reads none
+    std::vector<uint32_t> meta(c->dbg_n), nc(na);
+    HIP_TRY(hipMemcpy(meta.data(), c->d_rmeta, (size_t)c->dbg_n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t a = 0; a < na; a++) {
+        if (act[a] >= c->dbg_n) return BK_ERR_INTERNAL;
+        const int len = (int)(meta[act[a]] & kReadLenMask);
+        const ReadPlan p = make_plan(len, c->cfg);
+        int mm, cl, cd, dummy[1];
+        phase_params(p, c->cfg, c->dbg_phase, mm, cl, cd);
+        const int n = core_offsets(len, cl, cd, p.max_slides, dummy, 0);
+        nc[a] = n <= kMaxCoresFast ? (uint32_t)n : 0u;
+    }
     std::vector<uint2> h2;
-    std::vector<uint32_t> hn;
     if (c->d_iv2) h2.resize(na);
-    else hn.resize(na);
     for (uint32_t pl = 0; pl < planes; pl++) {
         uint64_t *f = first + (size_t)pl * na;
         uint32_t *q = count + (size_t)pl * na;
@@ -1161,6 +1173,8 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
             HIP_TRY(hipMemcpy(f, c->d_iv_first + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(q, c->d_iv_n + (size_t)pl * stride, (size_t)na * 4, hipMemcpyDeviceToHost));
         }
+        for (uint32_t a = 0; a < na; a++)
+            if (pl % c->dbg_ivc >= nc[a]) { f[a] = 0; q[a] = 0; }
     }
     return BK_OK;
 }

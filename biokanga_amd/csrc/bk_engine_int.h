@@ -74,7 +74,7 @@ void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
                      hipStream_t s);
 void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int phase, int lazy, const uint32_t *list, const uint32_t *sorted,
                      uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, hipStream_t s);
-void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, hipStream_t s);
+void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s);
 void launch_pe(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int pe_mode, int min_len, int max_len, int pair_strand,
                bk_hit *hits, uint32_t n_pairs, uint32_t *orphans, uint32_t *counters, uint32_t *h_count, bk_seg2 *seg2, int min_chim,
                int long_reads, const uint8_t *accept, uint32_t n_accept, hipStream_t s);

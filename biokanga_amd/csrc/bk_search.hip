@@ -238,7 +238,11 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
     }
     PROFS(3);
     // work-list appends, one global atomic per block.  The interval records are stored after them: the barriers of the append
-    // wait for every store the wave has issued.
+    // wait for every store the wave has issued.  Every slot of a core the read has is stored, an empty result as a zero count:
+    // nothing clears the records in front of this kernel, and what a slot held (the previous phase's longer list, the previous
+    // batch) must not reach a consumer.  A lane that appends its slot to pass B's list stores the work item (bucket and kind) in
+    // it, and pass B stores the result over that on every path it has.  Slots of cores a read does not have stay as they were:
+    // every consumer looks at the cores below the read's own count only.
     const int lane = threadIdx.x & 63;
     uint32_t my_off[ILP];
 #pragma unroll
@@ -261,7 +265,7 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
         if (push[u]) stripe_put_tile(out, 0, s_base + my_off[u], (uint32_t)slot[u], tile);
-        if (on[u] && nval[u] != 0) iv_put(b, slot[u], first[u], nval[u]);
+        if (on[u]) iv_put(b, slot[u], first[u], nval[u]);
     }
     __syncthreads();                                        // (s_cnt / s_base are the next tile's, too)
   }
@@ -467,8 +471,11 @@ void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
     else hipLaunchKernelGGL(k_search_b<false>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list);
 }
 
-// the interval records of the slots a phase can use, zeroed: [strand][core][position in the active list] for every core below cmax
-__global__ void __launch_bounds__(256) k_clear_iv(DevBatch b, const uint32_t *__restrict__ p_n_act, int cmax, int st0, int st1)
+// the interval records of the slots a phase can use - [strand][core][position in the active list] for every core below cmax - set
+// to one word (0: cleared).  Pass A and pass B store every slot they own, so the phase loop does not launch this; "iv_poison" (bk_ctx_tune)
+// fills the records with ones in front of the search, which makes any slot a consumer reads without its having been written in
+// that phase show in the results.
+__global__ void __launch_bounds__(256) k_clear_iv(DevBatch b, const uint32_t *__restrict__ p_n_act, int cmax, int st0, int st1, uint32_t word)
 {
     const uint32_t n_act = *p_n_act;
     const uint64_t per_strand = (uint64_t)cmax * n_act, total = per_strand * (uint64_t)(st1 - st0 + 1);
@@ -476,17 +483,17 @@ __global__ void __launch_bounds__(256) k_clear_iv(DevBatch b, const uint32_t *__
         const int st = st0 + (int)(i / per_strand);
         const uint64_t q = i % per_strand;
         const uint64_t slot = iv_slot(b, (uint32_t)(q % n_act), st, (int)(q / n_act));
-        if (b.iv2) b.iv2[slot] = make_uint2(0, 0);
-        else b.iv_n[slot] = 0;
+        if (b.iv2) b.iv2[slot] = make_uint2(word, word);
+        else { b.iv_first[slot] = word ? ~0ULL : 0ULL; b.iv_n[slot] = word; }
     }
 }
 
-void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, hipStream_t s)
+void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s)
 {
     const uint64_t total = (uint64_t)n_act_bound * (uint64_t)cmax * (uint64_t)(st1 - st0 + 1);
     if (!total) return;
     const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 16384);
-    hipLaunchKernelGGL(k_clear_iv, dim3(blocks), dim3(256), 0, s, b, p_n_act, cmax, st0, st1);
+    hipLaunchKernelGGL(k_clear_iv, dim3(blocks), dim3(256), 0, s, b, p_n_act, cmax, st0, st1, word);
 }
 
 }  // namespace bk

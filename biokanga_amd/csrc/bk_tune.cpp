@@ -196,6 +196,11 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->lazy_search = value ? 1 : 0;
         return old;
     }
+    if (n == "iv_poison") {               // test hook: every phase's interval records are filled with ones in front of its search
+        int64_t old = c->iv_poison;
+        c->iv_poison = value ? 1 : 0;
+        return old;
+    }
     if (n == "use_wave") {
         int64_t old = c->use_wave;
         c->use_wave = value ? 1 : 0;
