@@ -121,6 +121,8 @@ __device__ __forceinline__ uint32_t lset_bucket(uint32_t key)
 __device__ __forceinline__ bool lset_contains(const uint32_t *set, uint32_t key)
 {
 #if BK_LDS_SET_BUCKETS
+    // (the key that looks like an empty slot is never in the set - k_wave keeps it in the HBM table - and would match every free slot)
+    if (key == kLdsEmpty) return false;
     uint32_t b = lset_bucket(key);
     for (;;) {
         const lset_u32x4 v = *reinterpret_cast<const volatile lset_u32x4 *>(set + 4 * b);

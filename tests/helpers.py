@@ -120,6 +120,39 @@ def oracle_lib():
     return lib
 
 
+_devtest = None
+
+
+def devtest_lib():
+    """biokanga_amd/lib/libbk_devtest.so: test-only kernels around the device helpers (tests/hip/devtest.hip), built by
+    biokanga_amd/csrc/Makefile with everything else.  A missing library is an error.  Every launcher takes raw device pointers
+    (torch tensors' data_ptr()) and returns the hipError_t."""
+    global _devtest
+    if _devtest is not None:
+        return _devtest
+    so = os.path.join(ROOT, "biokanga_amd", "lib", "libbk_devtest.so")
+    if not os.path.exists(so):
+        raise RuntimeError(f"{so} is missing: build it (make -C biokanga_amd/csrc)")
+    lib = ctypes.CDLL(so)
+    vp, u32, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+    lib.bkdt_consts.argtypes = [ctypes.POINTER(u32)]
+    lib.bkdt_consts.restype = None
+    for name, args in (("bkdt_lset_bucket", [vp, u32, vp]),
+                       ("bkdt_lset_rounds", [vp, vp, u32, vp, vp]),
+                       ("bkdt_htab_rounds", [vp, u32, u32, vp, vp, vp, u32, vp]),
+                       ("bkdt_same_key", [vp, vp, u32, vp]),
+                       ("bkdt_window2i", [i32, i32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp]),
+                       ("bkdt_window_rare", [i32, vp, u32, i32, vp, vp, vp, u32, vp, vp, vp, vp])):
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ctypes.c_int
+    c = (u32 * 4)()
+    lib.bkdt_consts(c)
+    lib.kLdsSet, lib.kLdsSetFill, lib.kLdsEmpty, lib.kTombBit = (int(x) for x in c)
+    _devtest = lib
+    return lib
+
+
 class OracleSfx:
     def __init__(self, path=None, *, seq=None, sa=None, el_size=4, entries=None):
         """path: a .sfx file; or seq (uint8, 1 B/base incl. EOS) + sa (raw little-endian element bytes or

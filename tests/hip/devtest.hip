@@ -1,0 +1,185 @@
+// devtest.hip - test-only kernels around the device helpers of biokanga_amd/csrc (bk_dev_sets.h, bk_dev_window.h), included as they
+// stand.  Built as biokanga_amd/lib/libbk_devtest.so (csrc/Makefile); tests/helpers.py devtest_lib() loads it.  Every launcher takes raw
+// device pointers, launches on the null stream, synchronises and returns the hipError_t.  The helpers' probe loops end only at a free
+// slot: the caller keeps an LDS set within kLdsSetFill keys and an HBM table at most half full (tombstones counted), epochs in
+// [1, kTombBit).
+#include "../../biokanga_amd/csrc/bk_dev_sets.h"
+#include "../../biokanga_amd/csrc/bk_dev_window.h"
+
+using namespace bk;
+
+namespace {
+
+constexpr uint8_t kLook = 1, kInsert = 2;                                      // lset rounds: flag bits of a lane
+constexpr uint8_t kOpContains = 1, kOpInsert = 2, kOpFind = 3, kOpFindRetract = 4;   // htab rounds: what a lane does
+
+__global__ void __launch_bounds__(64) k_lset_bucket(const uint32_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = lset_bucket(keys[i]);
+}
+
+// k_wave's order: every lane looks up, wave barrier, every lane inserts, wave barrier
+__global__ void __launch_bounds__(64) k_lset_rounds(const uint32_t *__restrict__ keys, const uint8_t *__restrict__ flags, uint32_t rounds,
+                                                    uint8_t *__restrict__ found, uint32_t *__restrict__ set_out)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lset[kLdsSet];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = lane; i < kLdsSet; i += 64) lset[i] = kLdsEmpty;
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint32_t key = keys[r * 64 + lane];
+        const uint8_t f = flags[r * 64 + lane];
+        found[r * 64 + lane] = (f & kLook) ? (lset_contains(lset, key) ? 1 : 0) : 0;
+        __builtin_amdgcn_wave_barrier();
+        if (f & kInsert) lset_insert(lset, key);
+        __builtin_amdgcn_wave_barrier();
+    }
+    for (uint32_t i = lane; i < kLdsSet; i += 64) set_out[i] = lset[i];
+}
+
+// one wave per block, block b on its own table slice (tab + b * tab_size) with its own rounds, as wave_slot in k_wave / k_heavy.
+// A round: contains / find_or_insert of every lane, wave barrier, insert / retract of every lane, wave barrier
+__global__ void __launch_bounds__(64) k_htab_rounds(unsigned long long *__restrict__ tabs, uint32_t tab_size, const uint32_t *__restrict__ keys,
+                                                    const uint8_t *__restrict__ ops, const uint32_t *__restrict__ epochs, uint32_t rounds,
+                                                    uint8_t *__restrict__ out)
+{
+    unsigned long long *tab = tabs + (uint64_t)blockIdx.x * tab_size;
+    const uint32_t mask = tab_size - 1, lane = threadIdx.x;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const uint64_t at = ((uint64_t)blockIdx.x * rounds + r) * 64 + lane;
+        const uint32_t key = keys[at], epoch = epochs[(uint64_t)blockIdx.x * rounds + r];
+        const uint8_t op = ops[at];
+        uint32_t slot = 0xFFFFFFFFu;
+        bool res = false;
+        if (op == kOpContains) res = htab_contains(tab, mask, epoch, key);
+        else if (op == kOpFind || op == kOpFindRetract) res = htab_find_or_insert(tab, mask, epoch, key, slot);
+        out[at] = res ? 1 : 0;
+        __builtin_amdgcn_wave_barrier();
+        if (op == kOpInsert) htab_insert(tab, mask, epoch, key);
+        else if (op == kOpFindRetract && slot != 0xFFFFFFFFu) htab_retract(tab, slot, epoch);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+__global__ void __launch_bounds__(64) k_same_key(const uint32_t *__restrict__ keys, const uint8_t *__restrict__ cand, uint32_t rounds,
+                                                 uint8_t *__restrict__ out)
+{
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t r = 0; r < rounds; r++)
+        out[r * 64 + lane] = same_key_earlier_in_round(cand[r * 64 + lane] != 0, keys[r * 64 + lane], (int)lane) ? 1 : 0;
+}
+
+// one candidate per lane: rows r2w[n][NW / 2], rni[n][NW / 4]; results im[n][NW / 4], mm[n], eos[n]
+template <int NW, bool WIDE>
+__global__ void __launch_bounds__(64) k_window2i(const uint64_t *__restrict__ r2w_all, const uint64_t *__restrict__ rni_all, const int *__restrict__ len,
+                                                 const uint64_t *__restrict__ t, const uint64_t *__restrict__ tgt2, const uint64_t *__restrict__ tgt2s, uint32_t n,
+                                                 uint64_t *__restrict__ im, int *__restrict__ mm, uint8_t *__restrict__ eos)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    uint64_t r2w[NW / 2], rni[NW / 4];
+    load_read_words2<NW>(r2w_all + (uint64_t)i * (NW / 2), r2w);
+#pragma unroll
+    for (int k = 0; k < NW / 4; k++) rni[k] = rni_all[(uint64_t)i * (NW / 4) + k];
+    IWindow<NW> w;
+    eval_window2i<NW, WIDE>(r2w, rni, len[i], tgt2, tgt2s, t[i], w);
+#pragma unroll
+    for (int k = 0; k < NW / 4; k++) im[(uint64_t)i * (NW / 4) + k] = w.im[k];
+    mm[i] = w.mm;
+    eos[i] = w.eos ? 1 : 0;
+}
+
+// rows[n][row_words]: 4 bit/base words (four) or 2 bit/base words; results: the Window (bm, mm, eos) and window_to_iwindow of it (im)
+template <int NW>
+__global__ void __launch_bounds__(64) k_window_rare(const uint64_t *__restrict__ rows, uint32_t row_words, int four, const int *__restrict__ len,
+                                                    const uint64_t *__restrict__ t, const uint64_t *__restrict__ tgt4, uint32_t n,
+                                                    uint64_t *__restrict__ bm, uint64_t *__restrict__ im, int *__restrict__ mm, uint8_t *__restrict__ eos)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    RdRow row;
+    row.p = rows + (uint64_t)i * row_words;
+    row.four = four != 0;
+    Window<NW> w4;
+    eval_window_rare<NW>(row, len[i], tgt4, t[i], w4);
+    IWindow<NW> w;
+    window_to_iwindow<NW>(w4, w);
+#pragma unroll
+    for (int k = 0; k < NW / 4; k++) { bm[(uint64_t)i * (NW / 4) + k] = w4.bm[k]; im[(uint64_t)i * (NW / 4) + k] = w.im[k]; }
+    mm[i] = (w.mm == w4.mm && w.eos == w4.eos) ? w.mm : -1;
+    eos[i] = w4.eos ? 1 : 0;
+}
+
+int finish()
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+// {kLdsSet, kLdsSetFill, kLdsEmpty, kTombBit}: the caps and special values the tests stay within
+void bkdt_consts(uint32_t *out4)
+{
+    out4[0] = kLdsSet; out4[1] = kLdsSetFill; out4[2] = kLdsEmpty; out4[3] = kTombBit;
+}
+
+int bkdt_lset_bucket(const uint32_t *keys, uint32_t n, uint32_t *out)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_lset_bucket, dim3((n + 63) / 64), dim3(64), 0, 0, keys, n, out);
+    return finish();
+}
+
+// keys, flags (bit 0 look up, bit 1 insert), found: rounds * 64; set_out: kLdsSet words
+int bkdt_lset_rounds(const uint32_t *keys, const uint8_t *flags, uint32_t rounds, uint8_t *found, uint32_t *set_out)
+{
+    hipLaunchKernelGGL(k_lset_rounds, dim3(1), dim3(64), 0, 0, keys, flags, rounds, found, set_out);
+    return finish();
+}
+
+// tabs: blocks * tab_size entries (tab_size a power of two); keys, ops (1 contains, 2 insert, 3 find_or_insert, 4 find_or_insert and
+// retract the slot it took), out: blocks * rounds * 64; epochs: blocks * rounds
+int bkdt_htab_rounds(unsigned long long *tabs, uint32_t tab_size, uint32_t blocks, const uint32_t *keys, const uint8_t *ops, const uint32_t *epochs,
+                     uint32_t rounds, uint8_t *out)
+{
+    if (blocks == 0 || tab_size == 0 || (tab_size & (tab_size - 1))) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_htab_rounds, dim3(blocks), dim3(64), 0, 0, tabs, tab_size, keys, ops, epochs, rounds, out);
+    return finish();
+}
+
+int bkdt_same_key(const uint32_t *keys, const uint8_t *cand, uint32_t rounds, uint8_t *out)
+{
+    hipLaunchKernelGGL(k_same_key, dim3(1), dim3(64), 0, 0, keys, cand, rounds, out);
+    return finish();
+}
+
+int bkdt_window2i(int nw, int wide, const uint64_t *r2w, const uint64_t *rni, const int *len, const uint64_t *t, const uint64_t *tgt2, const uint64_t *tgt2s,
+                  uint32_t n, uint64_t *im, int *mm, uint8_t *eos)
+{
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    if (nw == 8 && !wide) hipLaunchKernelGGL((k_window2i<8, false>), grid, block, 0, 0, r2w, rni, len, t, tgt2, tgt2s, n, im, mm, eos);
+    else if (nw == 8) hipLaunchKernelGGL((k_window2i<8, true>), grid, block, 0, 0, r2w, rni, len, t, tgt2, tgt2s, n, im, mm, eos);
+    else if (nw == 16 && !wide) hipLaunchKernelGGL((k_window2i<16, false>), grid, block, 0, 0, r2w, rni, len, t, tgt2, tgt2s, n, im, mm, eos);
+    else if (nw == 16) hipLaunchKernelGGL((k_window2i<16, true>), grid, block, 0, 0, r2w, rni, len, t, tgt2, tgt2s, n, im, mm, eos);
+    else return (int)hipErrorInvalidValue;
+    return finish();
+}
+
+int bkdt_window_rare(int nw, const uint64_t *rows, uint32_t row_words, int four, const int *len, const uint64_t *t, const uint64_t *tgt4, uint32_t n,
+                     uint64_t *bm, uint64_t *im, int *mm, uint8_t *eos)
+{
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    if (nw == 8) hipLaunchKernelGGL((k_window_rare<8>), grid, block, 0, 0, rows, row_words, four, len, t, tgt4, n, bm, im, mm, eos);
+    else if (nw == 16) hipLaunchKernelGGL((k_window_rare<16>), grid, block, 0, 0, rows, row_words, four, len, t, tgt4, n, bm, im, mm, eos);
+    else return (int)hipErrorInvalidValue;
+    return finish();
+}
+
+}  // extern "C"

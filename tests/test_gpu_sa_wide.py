@@ -100,6 +100,26 @@ def test_suffix_sort_of_more_than_2_32_bases():
             seq[p0 + (1 << 32):p0 + (1 << 32) + 600] = w1
             planted_long.append(p0)
     assert len(planted_long) > 50
+    # the 100-mer whose forward-strand target start is 2^32 - 2: its key in the set of seen targets, start + 1 truncated to 32 bits, is
+    # 0xFFFFFFFF - the word a free slot of the wave kernel's LDS set holds.  Six more copies of it elsewhere, three exact and three with
+    # one substitution, so that a strand pass over it has other keys in its set
+    key_pos = (1 << 32) - 2
+    kw = seq[key_pos:key_pos + 100]
+    fill = torch.from_numpy(np.random.default_rng(17).integers(0, 4, 100).astype(np.uint8)).to(dev)
+    seq[key_pos:key_pos + 100] = torch.where(kw == 4, fill, kw)                  # (an N gap here would keep the reads from aligning)
+    kw = seq[key_pos:key_pos + 100].clone()
+    assert int(kw.max()) < 4                                                     # no sequence end inside
+    key_copies = []
+    for i in range(40):
+        p0 = 2_000_000_123 + i * 50_000_017
+        if len(key_copies) < 6 and int(seq[p0:p0 + 100].max()) < 4:
+            w = kw.clone()
+            if len(key_copies) >= 3:
+                q = (10, 50, 90)[len(key_copies) - 3]
+                w[q] = (w[q] + len(key_copies) - 2) & 3                         # (+1, +2, +3: another base)
+            seq[p0:p0 + 100] = w
+            key_copies.append(p0)
+    assert len(key_copies) == 6
     d_sa = torch.zeros(n * 5, dtype=torch.uint8, device=dev)
     bk.build_sa_device(seq.data_ptr(), n, d_sa.data_ptr(), 5, 0)
     v = d_sa.view(n, 5)
@@ -149,8 +169,18 @@ def test_suffix_sort_of_more_than_2_32_bases():
         for q in rng.choice(100, size=int(rng.integers(0, 4)), replace=False):
             w[q] = (w[q] + 1 + rng.integers(0, 3)) & 3
         extra.append(w if rng.integers(0, 2) else (3 - w[::-1]).astype(np.uint8))
-    bases = np.concatenate([rb.cpu().numpy()] + extra)
-    nreads += len(extra)
+    # + reads of the 100-mer at 2^32 - 2 (0..3 substitutions, either strand)
+    key_reads = []
+    kw_np = kw.cpu().numpy()
+    krng = np.random.default_rng(18)                     # (its own generator: the reads above and below stay what they were)
+    for i in range(52):
+        w = kw_np.copy()
+        for q in krng.choice(100, size=i % 4, replace=False):
+            w[q] = (w[q] + 1 + krng.integers(0, 3)) & 3
+        key_reads.append(w if i & 4 else (3 - w[::-1]).astype(np.uint8))
+    n_sampled = nreads
+    bases = np.concatenate([rb.cpu().numpy()] + extra + key_reads)
+    nreads += len(extra) + len(key_reads)
     offs = np.arange(nreads, dtype=np.uint64) * 100
     lens = np.full(nreads, 100, dtype=np.uint32)
     with bk.Aligner(None, bk.AlignParams(max_subs=3), d_seq=seq.data_ptr(), concat_len=n, d_sa=d_sa.data_ptr(), el_size=5, entries=ent) as al:
@@ -161,16 +191,17 @@ def test_suffix_sort_of_more_than_2_32_bases():
     ora.close()
     for f in ("chrom_id", "match_loci", "match_len", "low_hit_instances", "rslt", "nar", "strand", "low_mm", "nxt_low_mm", "num_hits", "mismatches"):
         bad = np.nonzero(got[f] != exp[f])[0]
-        assert len(bad) == 0, (f, len(bad), [(int(i), int(i) - (nreads - len(extra)), got[int(i)], exp[int(i)]) for i in bad[:6]])
+        assert len(bad) == 0, (f, len(bad), [(int(i), int(i) - n_sampled, got[int(i)], exp[int(i)]) for i in bad[:6]])
     assert (ctr["n_search"], ctr["n_cand"]) == (octr.n_search, octr.n_cand)
     assert int((got["nar"] == 1).sum()) > nreads // 2
     # the planted reads: two true instances, one seen - accepted as unique
-    tail = got[-len(extra):]
+    tail = got[n_sampled:n_sampled + len(extra)]
     assert int((tail["nar"] == 1).sum()) > len(extra) * 3 // 4
     # the planted reads on their own, every read through the hash-set wave kernel (heavy_thresh 0)
-    pl_bases = np.concatenate(extra)
-    pl_offs = np.arange(len(extra), dtype=np.uint64) * 100
-    pl_lens = np.full(len(extra), 100, dtype=np.uint32)
+    tail = got[n_sampled:]
+    pl_bases = np.concatenate(extra + key_reads)
+    pl_offs = np.arange(len(extra) + len(key_reads), dtype=np.uint64) * 100
+    pl_lens = np.full(len(extra) + len(key_reads), 100, dtype=np.uint32)
     # reads of 300 and 600 bases from the planted 600-mers (0..3 substitutions, either strand): beyond the register kernels
     long_reads = []
     for p0 in planted_long:

@@ -190,3 +190,44 @@ def test_packed_read_helpers_against_brute_force(tmp_path):
     subprocess.check_call(helpers.cxx() + ["-o", exe, src])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
+
+
+SETS_SHIM = r'''// stands in for bk_dev_util.h when bk_dev_sets.h is compiled for the host: one thread, the atomics as plain accesses that count their steps
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#define __device__
+#define __forceinline__ inline
+#define __HIP_MEMORY_SCOPE_WORKGROUP 3
+#define __HIP_MEMORY_SCOPE_AGENT 4
+static unsigned long long g_steps = 0;
+constexpr unsigned long long kMaxSteps = 1000000;          // between two resets by the harness: no probe sequence of a sound helper is that long
+static inline void twin_step() { if (++g_steps > kMaxSteps) { printf("FAIL: a probe loop does not end\n"); exit(2); } }
+template <typename T> static inline T twin_load(const T *p) { twin_step(); return *p; }
+template <typename T, typename V> static inline void twin_store(T *p, V v) { twin_step(); *p = (T)v; }
+#define __hip_atomic_load(p, order, scope) twin_load(p)
+#define __hip_atomic_store(p, v, order, scope) twin_store(p, v)
+template <typename T, typename V> static inline T atomicCAS(T *p, T expect, V v) { twin_step(); const T old = *p; if (old == expect) *p = (T)v; return old; }
+static inline uint64_t __ballot(bool b) { return b ? 1ULL : 0ULL; }       // a wave of one lane
+'''
+
+
+def sets_twin(tmp_path, header_text):
+    """bk_dev_sets.h (the text given, unchanged) beside the shims, under tests/cpp/dev_sets_host.cpp -> the finished run"""
+    d = tmp_path / "twin"
+    d.mkdir()
+    (d / "bk_dev_sets.h").write_text(header_text)
+    (d / "bk_dev_util.h").write_text(SETS_SHIM)
+    exe = str(d / "dev_sets_host")
+    flags = os.environ.get("BK_TEST_CXXFLAGS", "-O2").split()
+    # (ext_vector_type is a clang extension: the ROCm compiler as the host compiler, as tests/test_host_report.py has it)
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "c++"] + flags + ["-std=c++17", "-I" + str(d), "-o", exe, os.path.join(helpers.ROOT, "tests", "cpp", "dev_sets_host.cpp")])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=300)
+
+
+def test_seen_key_sets_on_the_host_against_std_set(tmp_path):
+    """lset_* and htab_* of bk_dev_sets.h as they stand, single-threaded against std::set: random keys up to the caps, the keys of one
+    bucket, 0xFFFFFFFF (the key an empty LDS slot holds) looked up in an empty set, after one insert and at the fill cap, retract, epochs"""
+    out = sets_twin(tmp_path, open(os.path.join(CSRC, "bk_dev_sets.h")).read())
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
