@@ -1,5 +1,9 @@
 // bk_ctx_int.h - internal: the context behind the C ABI (include/biokanga_amd.h), shared by bk_engine.cpp (batch driver)
 // and bk_stream.cpp (overlapped host <-> device pipeline).  Not part of the boundary.
+// Who owns what: the index image (d_tgt4 .. d_swmap, the grow_* set) and the small fixed buffers (d_small, d_ctl, the counters, the SNP
+// planes) are raw pointers of bk_ctx, allocated by bk_image.cpp and freed by name in bk_ctx_destroy.  Everything the batch driver and the
+// entry points grow on demand is a bk::DevBuf in bk_ctx::buf (BatchBufs): its capacity is the buffer's own, and bk_ctx_destroy releases
+// the lot with release_batch_buffers().  POD structs that travel to kernels (HeavyScratch, DevBatch) carry raw pointers into them.
 #pragma once
 #include <atomic>
 #include <thread>
@@ -10,6 +14,7 @@
 #include <vector>
 
 #include "bk_device.h"
+#include "bk_devbuf.h"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -19,6 +24,34 @@
             return e__ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL;                      \
         }                                                                                          \
     } while (0)
+
+namespace bk {
+// the context's device buffers that are grown on demand (capacities in elements: DevBuf::cap)
+struct BatchBufs {
+    // batch scratch (ensure_batch_scratch: sized together by cap_reads / cap_wpr / cap_rd2w / cap_iv_cores of the context)
+    DevBuf<uint64_t> rd4, rd2, iv_first;  // packed read rows (4 bit, 2 bit: DevBatch::rd4, rd2), interval records of an index beyond 2^32
+    DevBuf<uint2> iv2, iv32;              // DevBatch::iv2, iv32
+    DevBuf<uint32_t> iv_n, rmeta;         // DevBatch::iv_n, rmeta
+    DevBuf<uint32_t> act[2], heavy, wave, wave_work;      // the phases' work lists (DevBatch::wave_work)
+    DevBuf<uint32_t> stage[3], stripe_cnt;                // their striped forms (bk::StripeSet)
+    DevBuf<uint32_t> slist, slist_stage;  // work list of the two-pass search and its striped form (ensure_slist)
+    DevBuf<uint32_t> sort[3];             // keys in, keys out, list out of sort_work (ensure_sort_scratch)
+    DevBuf<uint8_t> sort_tmp, scan_tmp;   // the sort's temporary; the offset scan's of packed batches
+    DevBuf<bk_seg2> seg2;                 // -a / -A / -c: second segments of a chunk (ensure_seg2)
+    // staging for host-buffer batches: the bases, the per-read group (ensure_in_reads), the packed form's words and exceptions
+    DevBuf<uint8_t> in_bases;
+    DevBuf<uint64_t> in_offs;
+    DevBuf<uint32_t> in_lens;
+    DevBuf<bk_hit> in_out;
+    DevBuf<uint16_t> in_lens16;           // (packed batches only: empty, or as long as the rest of the group)
+    DevBuf<uint32_t> in_words;
+    DevBuf<bk_nbase> in_exc;
+    DevBuf<bk_snp_site> snp_sites;        // site list of the last bk_snp_sites call
+    DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
+    DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
+    DevBuf<uint32_t> slot_epoch;
+};
+}  // namespace bk
 
 struct bk_ctx {
     int device = 0;
@@ -37,22 +70,14 @@ struct bk_ctx {
     uint64_t *d_tgt2 = nullptr;           // 2 bit/base target copy (DevIndex::tgt2)
     uint64_t *d_tgt2s = nullptr;          // the same, stored 32 bytes later (DevIndex::tgt2s)
     uint8_t *d_nflag = nullptr;
-    uint64_t *d_rd2 = nullptr;            // 2-bit read rows
-    uint32_t *d_rmeta = nullptr;          // DevBatch::rmeta
     uint64_t n_tgt4_words = 0;
     uint32_t cap_rd2w = 0;
     int use_tgt2 = 2;        // 0: 4-bit windows only, 1: 2-bit copy, 2: 2-bit copy stored twice (32 bytes apart)
     uint32_t *d_k2 = nullptr;             // second-level search keys (DevIndex::k2)
     uint32_t *d_kx[bk::kMoreKeys] = {nullptr, nullptr};   // third-, fourth-level search keys (DevIndex::kx)
-    uint32_t *d_slist = nullptr;          // work list of the two-pass search
-    uint32_t *d_sort[3] = {nullptr, nullptr, nullptr};   // keys in, keys out, list out of sort_work
-    void *d_sort_tmp = nullptr;
-    uint64_t cap_sort = 0;
-    size_t sort_tmp_bytes = 0;
     int sort_lists = 7;      // bit 0: search work list grouped by index position; bit 1: wave list sorted, by index position or (bit 2) longest read first
     bool sort_lists_set = false;   // .. as the caller's knob left it; else bit 0 follows the index: off where it has third-level keys (tables_end)
     int sort_shift = 0;      // keys = suffix array index >> sort_shift (fits 32 bits)
-    uint64_t cap_slist = 0;
     int use_k2 = 1;
     int use_k3 = bk::kMoreKeys;  // key arrays behind the second-level keys (DevIndex::kx): at most this many, where the HBM has the room
     // BK_CTX_GROW_IMAGE: the tables that only pay over long runs (key arrays behind the second-level keys, k-mer table entries with their
@@ -95,21 +120,15 @@ struct bk_ctx {
     uint64_t tot_seq_len = 0;
     std::string dataset;
     std::vector<bk_entry_info> entries;
-    // SNP pile-up: 6 count planes over the concatenated target, site list of the last bk_snp_sites call
+    // SNP pile-up: 6 count planes over the concatenated target, site list of the last bk_snp_sites call (device side: buf.snp_sites)
     uint32_t *d_snp_planes = nullptr;
     unsigned long long *d_snp_tot = nullptr;
-    bk_snp_site *d_snp_sites = nullptr;
-    uint32_t cap_snp_sites = 0;
     std::vector<bk_snp_site> snp_sites;
 
-    // batch scratch (grown on demand)
+    bk::BatchBufs buf;                    // every device buffer that is grown on demand
+    void release_batch_buffers() { buf = bk::BatchBufs{}; }
+    // what the batch scratch was sized for (scratch_bytes_per_read, maybe_build_swin)
     uint32_t cap_reads = 0, cap_wpr = 0, cap_iv_cores = 0;
-    uint64_t *d_rd4 = nullptr, *d_iv_first = nullptr;
-    uint2 *d_iv2 = nullptr;
-    uint32_t *d_iv_n = nullptr, *d_act[2] = {nullptr, nullptr}, *d_heavy = nullptr, *d_wave = nullptr;
-    uint2 *d_iv32 = nullptr;              // DevBatch::iv32
-    uint32_t *d_wave_work = nullptr;      // DevBatch::wave_work
-    uint32_t *d_stage[3] = {nullptr, nullptr, nullptr}, *d_stripe_cnt = nullptr, *d_slist_stage = nullptr;       // striped work lists (bk::StripeSet)
     uint32_t *d_small = nullptr;          // [0] act_cnt [1] next_cnt [2] heavy_cnt [3] cmax [4] cursor [5] maxlen [6] wave_cnt [7] wave cursor
     uint32_t *h_small = nullptr;          // pinned mirror (two PhaseCtl lines when the phase loop reads its counts back)
     bk::PhaseCtl *d_ctl = nullptr;        // kMaxPhases + 2 lines: the counts of a chunk's phases (bk_device.h)
@@ -126,7 +145,7 @@ struct bk_ctx {
     bool force_rccl = false;                      // .. through RCCL even on one device ("force_rccl")
     uint64_t rccl_allreduces = 0;                 // .. how many of this context's reductions went through RCCL, the ranks of the last one's communicator
     int rccl_ranks = 0;
-    // heavy path scratch
+    // heavy path scratch (owned by buf.htab, buf.slot_epoch)
     bk::HeavyScratch hs{};
     int max_read_len = 500;
     uint32_t last_maxlen = 0;    // longest read of the last align call
@@ -136,31 +155,13 @@ struct bk_ctx {
     bool dbg_valid = false;
     bool debug = false;      // BK_DEBUG in the environment when the context was created: per-phase counts on stderr
     uint32_t chunk_reads = 64u << 20;
-    // staging for host-buffer batches
-    uint8_t *d_in_bases = nullptr;
-    uint64_t *d_in_offs = nullptr;
-    uint32_t *d_in_lens = nullptr;
-    bk_hit *d_in_out = nullptr;
-    bk_seg2 *d_seg2 = nullptr;            // -a / -A / -c: second segments of a chunk (kept with the batch scratch)
-    // packed host batches (bk_align_batch_packed) and the offset scan of packed batches
-    uint32_t *d_in_words = nullptr;
-    uint16_t *d_in_lens16 = nullptr;
-    bk_nbase *d_in_exc = nullptr;
-    uint64_t cap_in_words = 0, cap_in_exc = 0;
-    uint32_t cap_in_lens16 = 0;
-    void *d_scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    uint32_t cap_seg2 = 0;
-    uint64_t cap_in_bases = 0;
-    uint32_t cap_in_reads = 0;
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)
     bool tables_built = false;            // k-mer table, second-level keys, inverse suffix array exist (made behind the suffix array's upload)
     void *sam_text[2] = {nullptr, nullptr};   // bk_sam_format's page-locked text buffers, kept for the next call (giving page-locked memory back costs 0.1 s per GB)
     uint64_t sam_text_cap = 0;
-    uint8_t *d_chrom_accept = nullptr;    // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
-    uint32_t n_chrom_accept = 0;
+    uint32_t n_chrom_accept = 0;          // entries of buf.chrom_accept (bk_ctx_set_chrom_filter)
     bk_timing timing{};
     std::vector<hipEvent_t> ev_pool;
     // multi-loci modes: loci lists of the last align call (host side, see bk_batch_loci)
@@ -185,6 +186,7 @@ struct DevReads {
 // active counts back between phases)
 int engine_align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known = 0);
 void release_swin(bk_ctx *c);
+void drop_swin(bk_ctx *c);
 int engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_hit *d_hits, uint32_t maxlen, const bk_pe_params *pe, hipStream_t s,
                        bk_seg2 *seg2_host = nullptr, bk_seg2 *seg2_dev = nullptr);
 // packed batches: lens16 -> d_lens32, word offsets of the reads -> d_offs (scan), the batch checked (word count, read lengths,

@@ -3,6 +3,8 @@
 // Compiled with hipcc; device code lives in the kernel files (bk_prep / bk_search / bk_extend / bk_wave / bk_heavy / bk_rescue .hip); the index
 // image and the context's life are bk_image.cpp, knobs bk_tune.cpp, the exchange step bk_exchange.cpp.  No CPU fallback exists: every
 // compute entry point needs a HIP device and fails with BK_ERR_NODEVICE otherwise.
+// Ownership: every buffer this file grows is a bk::DevBuf of bk_ctx::buf (bk_devbuf.h, bk_ctx_int.h) and is grown by one ensure_* function
+// here; a chunk's temporaries are local DevBufs, so an early return frees them.  Nothing here frees device memory by hand.
 #include "bk_engine_int.h"
 
 namespace bk {
@@ -17,66 +19,140 @@ int size_heavy_scratch(bk_ctx *c)
     uint32_t slots = 4096;                  // one per resident wave of the hash-set forms (four blocks of four waves a CU: 40 KB of LDS each) when they fit in 16 GB
     while ((uint64_t)slots * ts * 8 > (16ULL << 30) && slots > 64) slots >>= 1;
     if (c->hs.htab && c->hs.tab_size == ts && c->hs.n_slots == slots) return BK_OK;
-    free_dev(c->hs.htab);
-    free_dev(c->hs.slot_epoch);
+    BatchBufs &m = c->buf;
+    m.htab.reset();
+    m.slot_epoch.reset();
     c->hs = HeavyScratch{};
-    HIP_TRY(dev_malloc(&c->hs.htab, (size_t)slots * ts * 8));
-    HIP_TRY(dev_malloc(&c->hs.slot_epoch, (size_t)slots * 4));
-    launch_fill_u64(c->hs.htab, (uint64_t)slots * ts, 0ULL, c->stream);
+    HIP_TRY(m.htab.ensure((size_t)slots * ts));
+    HIP_TRY(m.slot_epoch.ensure(slots));
+    launch_fill_u64(m.htab.get(), (uint64_t)slots * ts, 0ULL, c->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(c->hs.slot_epoch, 0, (size_t)slots * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(m.slot_epoch.get(), 0, (size_t)slots * 4, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->hs.tab_size = ts;
-    c->hs.n_slots = slots;
+    c->hs = HeavyScratch{m.htab.get(), m.slot_epoch.get(), ts, slots};
     return BK_OK;
 }
 
 
+// (all of the scratch is freed before any of it is allocated: the old and the new never lie in HBM side by side)
 int ensure_batch_scratch(bk_ctx *c, uint32_t n_reads, uint32_t wpr, uint32_t rd2w, uint32_t iv_cores)
 {
     if (n_reads <= c->cap_reads && wpr <= c->cap_wpr && rd2w <= c->cap_rd2w && iv_cores <= c->cap_iv_cores) return BK_OK;
-    uint32_t nr = std::max(n_reads, c->cap_reads), w = std::max(wpr, c->cap_wpr), w2 = std::max(rd2w, c->cap_rd2w);
-    const uint32_t ivc = std::max(iv_cores, c->cap_iv_cores);
-    free_dev(c->d_rd4); free_dev(c->d_iv_first); free_dev(c->d_iv_n); free_dev(c->d_rd2); free_dev(c->d_iv2); free_dev(c->d_rmeta);
-    c->d_rmeta = nullptr;
-    free_dev(c->d_act[0]); free_dev(c->d_act[1]); free_dev(c->d_heavy); free_dev(c->d_wave); free_dev(c->d_iv32); free_dev(c->d_wave_work);
-    c->d_iv32 = nullptr;
-    c->d_wave_work = nullptr;
-    c->d_rd4 = nullptr; c->d_iv_first = nullptr; c->d_iv_n = nullptr; c->d_rd2 = nullptr; c->d_iv2 = nullptr;
-    c->d_act[0] = c->d_act[1] = c->d_heavy = c->d_wave = nullptr;
-    for (int i = 0; i < 3; i++) { free_dev(c->d_stage[i]); c->d_stage[i] = nullptr; }
+    const size_t nr = std::max(n_reads, c->cap_reads), w = std::max(wpr, c->cap_wpr), w2 = std::max(rd2w, c->cap_rd2w);
+    const size_t ivc = std::max(iv_cores, c->cap_iv_cores);
+    BatchBufs &m = c->buf;
+    m.rd4.reset(); m.iv_first.reset(); m.iv_n.reset(); m.rd2.reset(); m.iv2.reset(); m.rmeta.reset();
+    m.act[0].reset(); m.act[1].reset(); m.heavy.reset(); m.wave.reset(); m.iv32.reset(); m.wave_work.reset();
+    for (auto &st : m.stage) st.reset();
     c->cap_reads = 0;
-    HIP_TRY(dev_malloc(&c->d_rd4, (size_t)nr * 2 * w * 8));
-    if (w2) HIP_TRY(dev_malloc(&c->d_rd2, (size_t)nr * 2 * w2 * 8 + 64));        // (+ the words a 32-base fetch at a row's end runs into)
-    HIP_TRY(dev_malloc(&c->d_rmeta, ((size_t)nr + 2) / 2 * 8));
+    HIP_TRY(m.rd4.ensure(nr * 2 * w));
+    if (w2) HIP_TRY(m.rd2.ensure(nr * 2 * w2 + 8));        // (+ the words a 32-base fetch at a row's end runs into)
+    HIP_TRY(m.rmeta.ensure((nr + 2) / 2 * 2));
     if (c->d_sa_hi == nullptr && c->ix.n < (1ULL << 32))
-        HIP_TRY(dev_malloc(&c->d_iv2, (size_t)nr * 2 * ivc * 8));
+        HIP_TRY(m.iv2.ensure(nr * 2 * ivc));
     else {
-        HIP_TRY(dev_malloc(&c->d_iv_first, (size_t)nr * 2 * ivc * 8));
-        HIP_TRY(dev_malloc(&c->d_iv_n, (size_t)nr * 2 * ivc * 4));
+        HIP_TRY(m.iv_first.ensure(nr * 2 * ivc));
+        HIP_TRY(m.iv_n.ensure(nr * 2 * ivc));
     }
-    HIP_TRY(dev_malloc(&c->d_act[0], (size_t)nr * 4));
-    HIP_TRY(dev_malloc(&c->d_act[1], (size_t)nr * 4));
-    HIP_TRY(dev_malloc(&c->d_heavy, (size_t)nr * 4));
-    HIP_TRY(dev_malloc(&c->d_wave, (size_t)nr * 4));
-    for (int i = 0; i < 3; i++) HIP_TRY(dev_malloc(&c->d_stage[i], ((size_t)nr + (kListStripes + 2) * 1024) * 4));      // striped forms of the lists (StripedList)
-    if (!c->d_stripe_cnt) {
-        HIP_TRY(dev_malloc(&c->d_stripe_cnt, (size_t)2 * kListStripes * 16 * 4));
-        HIP_TRY(dev_zero_now(c->d_stripe_cnt, (size_t)2 * kListStripes * 16 * 4));
+    HIP_TRY(m.act[0].ensure(nr));
+    HIP_TRY(m.act[1].ensure(nr));
+    HIP_TRY(m.heavy.ensure(nr));
+    HIP_TRY(m.wave.ensure(nr));
+    for (auto &st : m.stage) HIP_TRY(st.ensure(nr + (kListStripes + 2) * 1024));      // striped forms of the lists (StripedList)
+    if (!m.stripe_cnt.get()) {
+        HIP_TRY(m.stripe_cnt.ensure((size_t)2 * kListStripes * 16));
+        HIP_TRY(dev_zero_now(m.stripe_cnt.get(), (size_t)2 * kListStripes * 16 * 4));
     }
-    if (c->d_iv2) HIP_TRY(dev_malloc(&c->d_iv32, (size_t)nr * 2 * 8));
-    HIP_TRY(dev_malloc(&c->d_wave_work, (size_t)nr * 4));
-    c->cap_reads = nr;
-    c->cap_wpr = w;
-    c->cap_rd2w = w2;
-    c->cap_iv_cores = ivc;
+    if (m.iv2.get()) HIP_TRY(m.iv32.ensure(nr * 2));
+    HIP_TRY(m.wave_work.ensure(nr));
+    c->cap_reads = (uint32_t)nr;
+    c->cap_wpr = (uint32_t)w;
+    c->cap_rd2w = (uint32_t)w2;
+    c->cap_iv_cores = (uint32_t)ivc;
     return BK_OK;
 }
+
+// The groups below grow together: every member is freed before any is allocated, and the member allocated last speaks for the group (it
+// is there only when the ones before it are).
+// pass B's work list (at most one item per read, strand and core) and its striped form (StripeSet)
+int ensure_slist(bk_ctx *c, uint64_t lanes, hipStream_t s)
+{
+    BatchBufs &m = c->buf;
+    if (m.slist_stage.get() && lanes <= m.slist.cap()) return BK_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    m.slist.reset();
+    m.slist_stage.reset();
+    HIP_TRY(m.slist.ensure(lanes));
+    HIP_TRY(m.slist_stage.ensure(lanes + (kListStripes + 2) * 1024));
+    return BK_OK;
+}
+
+// the per-read group of a host batch: offsets, lengths, result records, and for a packed batch the 16-bit lengths
+int ensure_in_reads(bk_ctx *c, uint32_t n, bool packed)
+{
+    BatchBufs &m = c->buf;
+    if (n > m.in_out.cap()) {
+        m.in_offs.reset(); m.in_lens.reset(); m.in_out.reset(); m.in_lens16.reset();
+        HIP_TRY(m.in_offs.ensure(n));
+        HIP_TRY(m.in_lens.ensure(n));
+        HIP_TRY(m.in_out.ensure(n));
+    }
+    if (packed) HIP_TRY(m.in_lens16.ensure(m.in_out.cap()));
+    return BK_OK;
+}
+
+HostExtent host_extent(const uint64_t *offs, const uint32_t *lens, uint32_t nreads)
+{
+    HostExtent x;
+    for (uint32_t i = 0; i < nreads; i++) {
+        x.lo = std::min(x.lo, offs[i]);
+        x.hi = std::max(x.hi, offs[i] + lens[i]);
+        x.maxlen = std::max(x.maxlen, lens[i]);
+    }
+    x.rel.resize(nreads);
+    for (uint32_t i = 0; i < nreads; i++) x.rel[i] = offs[i] - x.lo;
+    return x;
+}
+
+// a host batch into the context's staging buffers: bases of the extent, relative offsets, lengths - enqueued on the context's stream
+// (x.rel is their source until the caller has synchronised)
+static int stage_host_batch(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const uint32_t *lens, uint32_t nreads, HostExtent &x, DevReads &in)
+{
+    x = host_extent(offs, lens, nreads);
+    if (x.maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
+    const uint64_t nbytes = x.hi - x.lo;
+    BatchBufs &m = c->buf;
+    HIP_TRY(m.in_bases.ensure(nbytes + 16));
+    int rc = ensure_in_reads(c, nreads, false);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(m.in_bases.get(), bases + x.lo, nbytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(m.in_offs.get(), x.rel.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(m.in_lens.get(), lens, (size_t)nreads * 4, hipMemcpyHostToDevice, c->stream));
+    in.bases = m.in_bases.get(); in.offs = m.in_offs.get(); in.lens = m.in_lens.get();
+    return BK_OK;
+}
+
+// the DevBatch of reads first .. first + n of `in` over the scratch ensure_batch_scratch has sized; what only the phase loop uses (rd2,
+// wave_work, iv32, nw, iv_stride, act) is left empty
+static DevBatch make_batch(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t wpr, uint32_t iv_cores, bk_hit *d_out)
+{
+    const BatchBufs &m = c->buf;
+    DevBatch b{};
+    b.bases = in.bases; b.offs = in.offs + first; b.lens = in.lens + first;
+    b.pk_words = in.words; b.pk_exc = in.exc; b.pk_nexc = in.words ? in.n_exc : 0; b.pk_read0 = first;
+    b.rd4 = m.rd4.get(); b.iv_first = m.iv_first.get(); b.iv_n = m.iv_n.get(); b.iv2 = m.iv2.get();
+    b.rmeta = m.rmeta.get();
+    b.out = d_out; b.seq_counts = c->d_seq_counts; b.ctr = c->d_ctr;
+    b.wpr = wpr; b.n_reads = n; b.iv_cores = iv_cores;
+    return b;
+}
+
+enum class Span { Search, Extend, Heavy, Other, SearchA, SearchSort, SearchB, Prep };      // what a timed span counts into (align_device)
 
 struct EvTimer {
     bk_ctx *c;
     bool on = true;                     // off: no events (a call that returns before its kernels have run cannot read them)
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;   // kind, (start, stop)
+    std::vector<std::pair<Span, std::pair<hipEvent_t, hipEvent_t>>> spans;   // kind, (start, stop)
     size_t next_ev = 0;
     hipEvent_t get()
     {
@@ -94,7 +170,7 @@ struct EvTimer {
         if (e) (void)hipEventRecord(e, s);
         return e;
     }
-    void end(int kind, hipEvent_t b, hipStream_t s)
+    void end(Span kind, hipEvent_t b, hipStream_t s)
     {
         hipEvent_t e = get();
         if (!e) return;
@@ -110,97 +186,122 @@ struct EvTimer {
 // (L2 hits instead of HBM misses).  Results do not depend on the order.
 int ensure_sort_scratch(bk_ctx *c, uint32_t n, hipStream_t s)
 {
-    if (n <= c->cap_sort) return BK_OK;
+    BatchBufs &m = c->buf;
+    if (m.sort_tmp.get() && n <= m.sort[2].cap()) return BK_OK;
     HIP_TRY(hipStreamSynchronize(s));
-    for (auto &p : c->d_sort) { free_dev(p); p = nullptr; }
-    free_dev(c->d_sort_tmp);
-    c->d_sort_tmp = nullptr;
-    c->cap_sort = 0;
+    for (auto &p : m.sort) p.reset();
+    m.sort_tmp.reset();
     const uint64_t cap = (uint64_t)n + n / 4;
-    for (auto &p : c->d_sort) HIP_TRY(dev_malloc(&p, cap * 4));
+    for (auto &p : m.sort) HIP_TRY(p.ensure(cap));
     size_t tb = 0;
     if (sort_list_by_key(nullptr, nullptr, nullptr, nullptr, (uint32_t)cap, nullptr, &tb, s)) return BK_ERR_INTERNAL;
-    HIP_TRY(dev_malloc(&c->d_sort_tmp, tb));
-    c->sort_tmp_bytes = tb;
-    c->cap_sort = cap;
+    HIP_TRY(m.sort_tmp.ensure(tb));
     return BK_OK;
 }
 
-// keys are expected in d_sort[0]; returns the reordered list (d_sort[2])
+// keys are expected in buf.sort[0]; returns the reordered list (buf.sort[2])
 int sort_work(bk_ctx *c, const uint32_t *list, uint32_t n, hipStream_t s, const uint32_t **out)
 {
-    size_t tb = c->sort_tmp_bytes;
-    if (sort_list_by_key(c->d_sort[0], c->d_sort[1], list, c->d_sort[2], n, c->d_sort_tmp, &tb, s)) return BK_ERR_INTERNAL;
-    *out = c->d_sort[2];
+    const BatchBufs &m = c->buf;
+    size_t tb = m.sort_tmp.cap();
+    if (sort_list_by_key(m.sort[0].get(), m.sort[1].get(), list, m.sort[2].get(), n, m.sort_tmp.get(), &tb, s)) return BK_ERR_INTERNAL;
+    *out = m.sort[2].get();
     return BK_OK;
 }
+
+// What the multi-loci modes share: per-read counts -> offsets (scan) -> the chunk's loci appended to the context's host vectors.
+// begin() makes the zeroed counts, which the caller's kernels fill; scan() leaves the offsets on the device and the host, `total`, and
+// room for that many loci, which the caller's kernels fill (and `trims`, when it allocated them); finish() appends them.
+struct LociChunk {
+    bk_ctx *c;
+    uint32_t n;
+    hipStream_t s;
+    DevBuf<unsigned long long> cnt, offs;
+    DevBuf<uint8_t> tmp;
+    DevBuf<bk_loci> loci;
+    DevBuf<bk_loci_trims> trims;
+    size_t base = 0;                    // reads of earlier chunks
+    uint64_t loci_base = 0, total = 0;
+    int begin()
+    {
+        HIP_TRY(cnt.ensure((size_t)n + 1));
+        HIP_TRY(offs.ensure((size_t)n + 1));
+        HIP_TRY(hipMemsetAsync(cnt.get(), 0, ((size_t)n + 1) * 8, s));
+        return BK_OK;
+    }
+    int scan()
+    {
+        size_t tb = 0;
+        if (scan_counts_u64(nullptr, nullptr, n + 1, nullptr, &tb, s)) return BK_ERR_INTERNAL;
+        HIP_TRY(tmp.ensure(tb ? tb : 16));
+        if (scan_counts_u64(cnt.get(), offs.get(), n + 1, tmp.get(), &tb, s)) return BK_ERR_INTERNAL;
+        base = c->loci_offs.empty() ? 0 : c->loci_offs.size() - 1;
+        loci_base = c->loci.size();
+        if (c->loci_offs.empty()) c->loci_offs.push_back(0);
+        c->loci_offs.resize(base + n + 1);
+        HIP_TRY(hipMemcpyAsync(c->loci_offs.data() + base, offs.get(), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        total = c->loci_offs[base + n];
+        HIP_TRY(loci.ensure((size_t)total));
+        return BK_OK;
+    }
+    int finish()
+    {
+        if (total) {
+            c->loci.resize(loci_base + total);
+            HIP_TRY(hipMemcpyAsync(c->loci.data() + loci_base, loci.get(), (size_t)total * sizeof(bk_loci), hipMemcpyDeviceToHost, s));
+            if (trims.get()) {
+                c->loci_trims.resize(loci_base + total);
+                HIP_TRY(hipMemcpyAsync(c->loci_trims.data() + loci_base, trims.get(), (size_t)total * sizeof(bk_loci_trims), hipMemcpyDeviceToHost, s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (loci_base)
+            for (size_t i = 0; i <= n; i++) c->loci_offs[base + i] += loci_base;
+        return BK_OK;
+    }
+};
 
 // Multi-loci modes: the loci lists of one chunk (reads whose AlignReads returned eHRhits own LowHitInstances
 // entries each).  Counts -> offsets (scan) -> single loci copied from the result records, the others replayed
 // by the ENUM form of the wave-per-read kernel; appended to the context's host vectors.
 int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipStream_t s)
 {
-    unsigned long long *d_cnt = nullptr, *d_offs = nullptr;
-    void *d_tmp = nullptr;
-    bk_loci *d_loci = nullptr;
-    bk_loci_trims *d_trims = nullptr;
-    const bool chim = c->params.min_chimeric_len > 0 && c->d_seg2 != nullptr;       // every locus carries its end trims
-    int rc = BK_OK;
-    auto cleanup = [&]() { free_dev(d_cnt); free_dev(d_offs); free_dev(d_tmp); free_dev(d_loci); free_dev(d_trims); };
-#define LOCI_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return e_ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL; } } while (0)
-    LOCI_TRY(dev_malloc(&d_cnt, ((size_t)n + 1) * 8));
-    LOCI_TRY(dev_malloc(&d_offs, ((size_t)n + 1) * 8));
-    LOCI_TRY(hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * 8, s));
-    launch_loci_count(b.out, n, c->params.clamp_ml ? c->cfg.max_hits : 0, d_cnt, s);
-    size_t tb = 0;
-    if (scan_counts_u64(nullptr, nullptr, n + 1, nullptr, &tb, s)) { cleanup(); return BK_ERR_INTERNAL; }
-    LOCI_TRY(dev_malloc(&d_tmp, tb ? tb : 16));
-    if (scan_counts_u64(d_cnt, d_offs, n + 1, d_tmp, &tb, s)) { cleanup(); return BK_ERR_INTERNAL; }
-    const size_t base = c->loci_offs.empty() ? 0 : c->loci_offs.size() - 1;      // reads of earlier chunks
-    const uint64_t loci_base = c->loci.size();
-    if (c->loci_offs.empty()) c->loci_offs.push_back(0);
-    c->loci_offs.resize(base + n + 1);
-    LOCI_TRY(hipMemcpyAsync(c->loci_offs.data() + base, d_offs, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-    LOCI_TRY(hipStreamSynchronize(s));
-    const uint64_t total = c->loci_offs[base + n];
-    if (total) {
+    bk_seg2 *d_seg2 = c->params.min_chimeric_len > 0 ? c->buf.seg2.get() : nullptr;       // there: every locus carries its end trims
+    LociChunk lc{c, n, s};
+    int rc = lc.begin();
+    if (rc) return rc;
+    launch_loci_count(b.out, n, c->params.clamp_ml ? c->cfg.max_hits : 0, lc.cnt.get(), s);
+    rc = lc.scan();
+    if (rc) return rc;
+    uint32_t n_multi = 0;
+    if (lc.total) {
         uint32_t *sm = c->d_small;
-        LOCI_TRY(dev_malloc(&d_loci, (size_t)total * sizeof(bk_loci)));
-        if (chim) {
-            LOCI_TRY(dev_malloc(&d_trims, (size_t)total * sizeof(bk_loci_trims)));
-            LOCI_TRY(clear_dev(d_trims, (size_t)total * sizeof(bk_loci_trims), s));
+        if (d_seg2) {
+            HIP_TRY(lc.trims.ensure((size_t)lc.total));
+            HIP_TRY(clear_dev(lc.trims.get(), (size_t)lc.total * sizeof(bk_loci_trims), s));
         }
-        LOCI_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
-        uint32_t *list = c->d_act[0];                  // the phase work lists are free by now
-        launch_loci_single(b.out, n, d_offs, d_loci, list, sm + 0, chim ? c->d_seg2 : nullptr, d_trims, s);
-        LOCI_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
-        LOCI_TRY(hipStreamSynchronize(s));
-        const uint32_t n_multi = c->h_small[0];
+        HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
+        uint32_t *list = c->buf.act[0].get();          // the phase work lists are free by now
+        launch_loci_single(b.out, n, lc.offs.get(), lc.loci.get(), list, sm + 0, d_seg2, lc.trims.get(), s);
+        HIP_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_multi = c->h_small[0];
         if (n_multi) {
             rc = size_heavy_scratch(c);
-            if (rc) { cleanup(); return rc; }
-            launch_loci_enum(c->ix, c->cfg, b, c->hs, list, n_multi, sm + 1, d_offs, d_loci, sm + 2, chim ? c->params.min_chimeric_len : 0, maxlen > 512 ? 1 : 0,
-                             chim ? c->d_seg2 : nullptr, d_trims, s);
-            LOCI_TRY(hipGetLastError());
-            LOCI_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
-        }
-        c->loci.resize(loci_base + total);
-        LOCI_TRY(hipMemcpyAsync(c->loci.data() + loci_base, d_loci, (size_t)total * sizeof(bk_loci), hipMemcpyDeviceToHost, s));
-        if (chim) {
-            c->loci_trims.resize(loci_base + total);
-            LOCI_TRY(hipMemcpyAsync(c->loci_trims.data() + loci_base, d_trims, (size_t)total * sizeof(bk_loci_trims), hipMemcpyDeviceToHost, s));
-        }
-        LOCI_TRY(hipStreamSynchronize(s));
-        if (n_multi && c->h_small[2] != 0) {           // a replay that did not reproduce LowHitInstances: never ignore
-            fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small[2]);
-            cleanup();
-            return BK_ERR_INTERNAL;
+            if (rc) return rc;
+            launch_loci_enum(c->ix, c->cfg, b, c->hs, list, n_multi, sm + 1, lc.offs.get(), lc.loci.get(), sm + 2, d_seg2 ? c->params.min_chimeric_len : 0,
+                             maxlen > 512 ? 1 : 0, d_seg2, lc.trims.get(), s);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
         }
     }
-    if (loci_base)
-        for (size_t i = 0; i <= n; i++) c->loci_offs[base + i] += loci_base;
-#undef LOCI_TRY
-    cleanup();
+    rc = lc.finish();
+    if (rc) return rc;
+    if (n_multi && c->h_small[2] != 0) {               // a replay that did not reproduce LowHitInstances: never ignore
+        fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small[2]);
+        return BK_ERR_INTERNAL;
+    }
     return BK_OK;
 }
 
@@ -208,53 +309,29 @@ int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipS
 // loci per read compacted into the same host-side lists the other multi-loci modes return
 int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t *d_list, uint32_t n_list, hipStream_t s)
 {
-    unsigned long long *d_cnt = nullptr, *d_offs = nullptr;
-    void *d_tmp = nullptr;
-    bk_loci *d_dense = nullptr, *d_loci = nullptr;
     const uint32_t width = (uint32_t)c->cfg.max_hits;
-    auto cleanup = [&]() { free_dev(d_cnt); free_dev(d_offs); free_dev(d_tmp); free_dev(d_dense); free_dev(d_loci); };
-#define BEST_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return e_ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL; } } while (0)
-    BEST_TRY(dev_malloc(&d_cnt, ((size_t)n + 1) * 8));
-    BEST_TRY(dev_malloc(&d_offs, ((size_t)n + 1) * 8));
-    BEST_TRY(dev_malloc(&d_dense, (size_t)n * width * sizeof(bk_loci)));
-    BEST_TRY(hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * 8, s));
-    int rc = size_heavy_scratch(c);
-    if (rc) { cleanup(); return rc; }
+    DevBuf<bk_loci> dense;
+    LociChunk lc{c, n, s};
+    int rc = lc.begin();
+    if (rc) return rc;
+    HIP_TRY(dense.ensure((size_t)n * width));
+    rc = size_heavy_scratch(c);
+    if (rc) return rc;
     uint32_t *sm = c->d_small;
-    BEST_TRY(hipMemsetAsync(sm + 4, 0, 4, s));
-    launch_best(c->ix, c->cfg, b, c->hs, d_list, n_list, sm + 4, d_cnt, d_dense, s);
-    BEST_TRY(hipGetLastError());
-    size_t tb = 0;
-    if (scan_counts_u64(nullptr, nullptr, n + 1, nullptr, &tb, s)) { cleanup(); return BK_ERR_INTERNAL; }
-    BEST_TRY(dev_malloc(&d_tmp, tb ? tb : 16));
-    if (scan_counts_u64(d_cnt, d_offs, n + 1, d_tmp, &tb, s)) { cleanup(); return BK_ERR_INTERNAL; }
-    const size_t base = c->loci_offs.empty() ? 0 : c->loci_offs.size() - 1;
-    const uint64_t loci_base = c->loci.size();
-    if (c->loci_offs.empty()) c->loci_offs.push_back(0);
-    c->loci_offs.resize(base + n + 1);
-    BEST_TRY(hipMemcpyAsync(c->loci_offs.data() + base, d_offs, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-    BEST_TRY(hipStreamSynchronize(s));
-    const uint64_t total = c->loci_offs[base + n];
-    if (total) {
-        BEST_TRY(dev_malloc(&d_loci, (size_t)total * sizeof(bk_loci)));
-        launch_loci_compact(d_dense, width, d_offs, n, d_loci, s);
-        BEST_TRY(hipGetLastError());
-        c->loci.resize(loci_base + total);
-        BEST_TRY(hipMemcpyAsync(c->loci.data() + loci_base, d_loci, (size_t)total * sizeof(bk_loci), hipMemcpyDeviceToHost, s));
-        BEST_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemsetAsync(sm + 4, 0, 4, s));
+    launch_best(c->ix, c->cfg, b, c->hs, d_list, n_list, sm + 4, lc.cnt.get(), dense.get(), s);
+    HIP_TRY(hipGetLastError());
+    rc = lc.scan();
+    if (rc) return rc;
+    if (lc.total) {
+        launch_loci_compact(dense.get(), width, lc.offs.get(), n, lc.loci.get(), s);
+        HIP_TRY(hipGetLastError());
     }
-    if (loci_base)
-        for (size_t i = 0; i <= n; i++) c->loci_offs[base + i] += loci_base;
-#undef BEST_TRY
-    cleanup();
-    return BK_OK;
+    return lc.finish();
 }
 
 int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
 {
-    const uint8_t *d_bases = in.bases;
-    const uint64_t *d_offs = in.offs + first;
-    const uint32_t *d_lens = in.lens + first;
     uint32_t *sm = c->d_small, *hm = c->h_small;
     HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
     const uint32_t wpr = words_per_read(maxlen);
@@ -271,18 +348,15 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     }
     if (rc) return rc;
 
-    DevBatch b{};
-    b.bases = d_bases; b.offs = d_offs; b.lens = d_lens;
-    b.pk_words = in.words; b.pk_exc = in.exc; b.pk_nexc = in.words ? in.n_exc : 0; b.pk_read0 = first;
-    b.rd4 = c->d_rd4; b.iv_first = c->d_iv_first; b.iv_n = c->d_iv_n; b.iv2 = c->d_iv2;
-    b.rd2 = two_bit ? c->d_rd2 : nullptr;
-    b.rmeta = c->d_rmeta;
+    BatchBufs &m = c->buf;
+    uint32_t *const d_act[2] = {m.act[0].get(), m.act[1].get()}, *const d_heavy = m.heavy.get(), *const d_wave = m.wave.get();
+    uint32_t *const d_stage[3] = {m.stage[0].get(), m.stage[1].get(), m.stage[2].get()}, *const d_stripe_cnt = m.stripe_cnt.get();
+    DevBatch b = make_batch(c, in, first, n, wpr, ivc, d_out);
+    b.rd2 = two_bit ? m.rd2.get() : nullptr;
     // (the wave list's job sizes come from k_flat only when every read on that list went through it)
-    b.wave_work = (reg_path && c->cfg.heavy_thresh <= 100) ? c->d_wave_work : nullptr;
-    b.iv32 = (c->use_iv32 && c->ix.k2) ? c->d_iv32 : nullptr;      // (written by k_search_a_ilp and pass B in phase 0)
+    b.wave_work = (reg_path && c->cfg.heavy_thresh <= 100) ? m.wave_work.get() : nullptr;
+    b.iv32 = (c->use_iv32 && c->ix.k2) ? m.iv32.get() : nullptr;      // (written by k_search_a_ilp and pass B in phase 0)
     b.nw = reg_path ? (uint32_t)nw16 : 0u;       // the fused prep kernel packs reads of the register-kernel path
-    b.out = d_out; b.seq_counts = c->d_seq_counts; b.ctr = c->d_ctr;
-    b.wpr = wpr; b.n_reads = n; b.iv_cores = ivc;
     const int nstr = c->cfg.align_strand == 0 ? 2 : 1;
 
     // ---- the phase loop ---------------------------------------------------------------------------------------------------------
@@ -314,11 +388,11 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     const bool no_readback = reg_path && c->cfg.heavy_thresh <= 100 && c->ix.k2 != nullptr && cores_fit && !c->params.best_matches &&
                              !c->debug && c->async_phases;
     const bool check_maxlen = !tm.on;                 // (a call that only enqueues: its caller named the longest read, nobody has looked)
-    if (check_maxlen) launch_max_len(d_lens, n, P(kMaxPhases + 1) + 0, s);
+    if (check_maxlen) launch_max_len(b.lens, n, P(kMaxPhases + 1) + 0, s);
     hipEvent_t e0 = tm.begin(s);
-    launch_prep(c->cfg, b, c->d_act[0], P(0) + 0, P(0) + 1, c->d_stage[0], c->d_stripe_cnt, s);
+    launch_prep(c->cfg, b, d_act[0], P(0) + 0, P(0) + 1, d_stage[0], d_stripe_cnt, s);
     HIP_TRY(hipGetLastError());
-    tm.end(7, e0, s);
+    tm.end(Span::Prep, e0, s);
     uint32_t n_act = n;
     int cmax = cmax_bound[0];
     auto read_ctl = [&](int ph) -> int {           // ctl[ph], ctl[ph + 1] -> hm[0..31]
@@ -335,15 +409,15 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     int cur = 0;
     if (c->params.best_matches) {
         hipEvent_t eb = tm.begin(s);
-        int rb = best_matches_chunk(c, b, n, c->d_act[0], n_act, s);
+        int rb = best_matches_chunk(c, b, n, d_act[0], n_act, s);
         if (rb) return rb;
-        tm.end(2, eb, s);
+        tm.end(Span::Heavy, eb, s);
         n_act = 0;
     }
     b.iv_stride = n;                               // interval records and the wave list go by position in the phase's active list
     if (no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe of the wave kernel
     for (int phase = 0; no_readback ? phase < max_phases : n_act > 0; phase++) {
-        const uint32_t *ext_list = c->d_act[cur];
+        const uint32_t *ext_list = d_act[cur];
         b.act = ext_list;
         if (no_readback) cmax = cmax_bound[phase];
         const uint32_t n_bound = n_act;            // (no read-back: the chunk's size; else the list's length)
@@ -353,25 +427,17 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
             hipEvent_t e1 = tm.begin(s);
             if (c->ix.k2) {
                 const uint64_t lanes = (uint64_t)n_bound * (uint64_t)(cmax * nstr);
-                if (lanes > c->cap_slist) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    free_dev(c->d_slist);
-                    free_dev(c->d_slist_stage);
-                    c->d_slist = c->d_slist_stage = nullptr;
-                    c->cap_slist = 0;
-                    HIP_TRY(dev_malloc(&c->d_slist, lanes * 4));
-                    HIP_TRY(dev_malloc(&c->d_slist_stage, (lanes + (kListStripes + 2) * 1024) * 4));     // its striped form (StripeSet)
-                    c->cap_slist = lanes;
-                }
+                { int rs = ensure_slist(c, lanes, s); if (rs) return rs; }
+                uint32_t *const d_slist = m.slist.get();
                 // (no clearing of the interval records: pass A stores the slot of every core a read has, empty results included, or hands
                 // it to pass B, which stores it on every path; the consumers never look at a core the read does not have.  "iv_poison"
                 // puts ones into the slots this phase can use, so that a slot read without having been written shows.)
                 if (c->iv_poison) launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
                 hipEvent_t ea = tm.begin(s);
-                launch_search_a(c->ix, c->cfg, b, c->d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, c->d_slist, ctl_p + 2,
-                                c->d_slist_stage, c->d_stripe_cnt, s);
+                launch_search_a(c->ix, c->cfg, b, d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, d_slist, ctl_p + 2,
+                                m.slist_stage.get(), d_stripe_cnt, s);
                 HIP_TRY(hipGetLastError());
-                tm.end(4, ea, s);
+                tm.end(Span::SearchA, ea, s);
                 // pass B's work list, grouped by k-mer bucket: the sort's size is the list's length when that was read back, else what
                 // the previous chunk's phase needed (plus a margin; capped at the sort buffers)
                 uint64_t n_slist_bound = lanes;
@@ -385,27 +451,27 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                     const double f = c->hist_valid ? c->hist_slist[phase] * 1.05 : 0.30;
                     n_sort = (uint32_t)std::min<uint64_t>({(uint64_t)(f * n) + 4096, lanes, (uint64_t)0x7FFFFFF0});
                 }
-                if (no_readback && c->cap_sort >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, c->cap_sort);      // (no growing - it waits for the stream - for a guess)
+                if (no_readback && m.sort[2].cap() >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, m.sort[2].cap());      // (no growing - it waits for the stream - for a guess)
                 const uint32_t *sorted = nullptr;
                 if ((c->sort_lists & 1) && n_sort >= 4096) {
                     int rs = ensure_sort_scratch(c, n_sort, s);
                     if (rs) return rs;
                     hipEvent_t es = tm.begin(s);
-                    launch_keys_search(b, c->d_slist, ctl_p + 2, n_sort, c->sort_shift, c->d_sort[0], s);
-                    rs = sort_work(c, c->d_slist, n_sort, s, &sorted);
+                    launch_keys_search(b, d_slist, ctl_p + 2, n_sort, c->sort_shift, m.sort[0].get(), s);
+                    rs = sort_work(c, d_slist, n_sort, s, &sorted);
                     if (rs) return rs;
-                    tm.end(5, es, s);
+                    tm.end(Span::SearchSort, es, s);
                 } else
                     n_sort = 0;
                 if (n_slist_bound) {
                     hipEvent_t eb = tm.begin(s);
-                    launch_search_b(c->ix, c->cfg, b, phase, lazy, c->d_slist, sorted, n_sort, ctl_p + 2, n_slist_bound, s);
-                    tm.end(6, eb, s);
+                    launch_search_b(c->ix, c->cfg, b, phase, lazy, d_slist, sorted, n_sort, ctl_p + 2, n_slist_bound, s);
+                    tm.end(Span::SearchB, eb, s);
                 }
             } else
-                launch_search(c->ix, c->cfg, b, c->d_act[cur], n_act, phase, cmax, nstr, lazy, s);
+                launch_search(c->ix, c->cfg, b, d_act[cur], n_act, phase, cmax, nstr, lazy, s);
             HIP_TRY(hipGetLastError());
-            tm.end(0, e1, s);
+            tm.end(Span::Search, e1, s);
         }
         if (phase == c->dbg_stop_phase) {
             // (test hook, bk_debug_intervals: the interval records the search of this phase wrote stay where they are; nothing of the
@@ -422,12 +488,12 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         if (c->ix.n > (1ULL << 32)) cfg_lane.heavy_thresh = 0;            // (below that the truncated keys are the exact ones)
         if (n_bound == 0) {}
         else if (reg_path && c->cfg.heavy_thresh <= 100)
-            launch_flat(c->ix, c->cfg, b, ext_list, ctl_p + 0, n_bound, phase, nstr * std::max(cmax, 1), c->d_act[cur ^ 1], ctl_n + 0, c->d_heavy, ctl_p + 4,
-                        c->d_wave, ctl_p + 3, ctl_n + 1, c->d_stage, c->d_stripe_cnt, nw16, s);
+            launch_flat(c->ix, c->cfg, b, ext_list, ctl_p + 0, n_bound, phase, nstr * std::max(cmax, 1), d_act[cur ^ 1], ctl_n + 0, d_heavy, ctl_p + 4,
+                        d_wave, ctl_p + 3, ctl_n + 1, d_stage, d_stripe_cnt, nw16, s);
         else
-            launch_extend(c->ix, cfg_lane, b, ext_list, n_act, phase, c->d_act[cur ^ 1], ctl_n + 0, c->d_heavy, ctl_p + 4, ctl_n + 1, s);
+            launch_extend(c->ix, cfg_lane, b, ext_list, n_act, phase, d_act[cur ^ 1], ctl_n + 0, d_heavy, ctl_p + 4, ctl_n + 1, s);
         HIP_TRY(hipGetLastError());
-        tm.end(1, e2, s);
+        tm.end(Span::Extend, e2, s);
         uint32_t n_heavy = 0, n_wave = n_bound;    // (no read-back: any read of the list may have gone to the wave kernel)
         if (!no_readback) {
             int rr = read_ctl(phase);
@@ -442,28 +508,28 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
             if (no_readback) {
                 const double f = c->hist_valid ? c->hist_wave[phase] * 1.05 : 0.25;
                 n_sort = (uint32_t)std::min<uint64_t>((uint64_t)(f * n) + 4096, n_wave);
-                if (c->cap_sort >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, c->cap_sort);
+                if (m.sort[2].cap() >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, m.sort[2].cap());
             }
             if ((c->sort_lists & 2) && n_sort >= 4096) {
                 int rs = ensure_sort_scratch(c, n_sort, s);
                 if (rs) return rs;
-                launch_keys_wave(c->cfg, b, phase, c->d_wave, ctl_p + 3, n_sort, (c->sort_lists & 4) ? -1 : c->sort_shift, c->d_sort[0], b.wave_work, s);
-                rs = sort_work(c, c->d_wave, n_sort, s, &wsorted);
+                launch_keys_wave(c->cfg, b, phase, d_wave, ctl_p + 3, n_sort, (c->sort_lists & 4) ? -1 : c->sort_shift, m.sort[0].get(), b.wave_work, s);
+                rs = sort_work(c, d_wave, n_sort, s, &wsorted);
                 if (rs) return rs;
             } else
                 n_sort = 0;
             if (!no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe
-            launch_wave(c->ix, c->cfg, b, c->hs, c->d_wave, wsorted, n_sort, ctl_p + 3, n_wave, phase, ctl_p + 5, c->d_act[cur ^ 1], ctl_n + 0, ctl_n + 1,
+            launch_wave(c->ix, c->cfg, b, c->hs, d_wave, wsorted, n_sort, ctl_p + 3, n_wave, phase, ctl_p + 5, d_act[cur ^ 1], ctl_n + 0, ctl_n + 1,
                         nw16, c->wave_waves, s);
             HIP_TRY(hipGetLastError());
-            tm.end(2, e3, s);
+            tm.end(Span::Heavy, e3, s);
         }
         if (n_heavy) {
             hipEvent_t e3 = tm.begin(s);
             { int rh = size_heavy_scratch(c); if (rh) return rh; }
-            launch_heavy(c->ix, c->cfg, b, c->hs, c->d_heavy, n_heavy, phase, ctl_p + 6, c->d_act[cur ^ 1], ctl_n + 0, ctl_n + 1, s);
+            launch_heavy(c->ix, c->cfg, b, c->hs, d_heavy, n_heavy, phase, ctl_p + 6, d_act[cur ^ 1], ctl_n + 0, ctl_n + 1, s);
             HIP_TRY(hipGetLastError());
-            tm.end(2, e3, s);
+            tm.end(Span::Heavy, e3, s);
         }
         if (!no_readback) {
             if (n_wave || n_heavy) { int rr = read_ctl(phase); if (rr) return rr; }
@@ -492,20 +558,14 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         // AlignReads' branches for what is still unaligned (SfxArrayV2.cpp:7722-7757): microInDels, then splice junctions, then the
         // chimeric (end-trimmed) placement
         hipEvent_t ei = tm.begin(s);
-        if (n > c->cap_seg2) {                                     // kept with the batch scratch, grown on demand
-            free_dev(c->d_seg2);
-            c->d_seg2 = nullptr;
-            c->cap_seg2 = 0;
-            HIP_TRY(dev_malloc(&c->d_seg2, (size_t)n * sizeof(bk_seg2)));
-            c->cap_seg2 = n;
-        }
-        bk_seg2 *d_seg2 = c->d_seg2;
+        { int r2 = ensure_seg2(c, n); if (r2) return r2; }
+        bk_seg2 *d_seg2 = m.seg2.get();
         hipError_t eh = clear_dev(d_seg2, (size_t)n * sizeof(bk_seg2), s);
         int rc2 = BK_OK;
         if (eh == hipSuccess && (c->params.micro_indel_len > 0 || c->params.splice_junct_len > 0)) {
             eh = hipMemsetAsync(sm, 0, 16 * 4, s);
             if (eh == hipSuccess) {
-                launch_indel(c->ix, c->cfg, b, n, c->params.micro_indel_len, c->params.splice_junct_len, c->params.min_chimeric_len > 0 ? 1 : 0, c->d_act[0], sm + 0,
+                launch_indel(c->ix, c->cfg, b, n, c->params.micro_indel_len, c->params.splice_junct_len, c->params.min_chimeric_len > 0 ? 1 : 0, d_act[0], sm + 0,
                              hm + 0, sm + 1, d_seg2, s);
                 eh = hipGetLastError();
             }
@@ -515,12 +575,12 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
             if (rc2 == BK_OK) {
                 eh = hipMemsetAsync(sm, 0, 16 * 4, s);
                 if (eh == hipSuccess) {
-                    launch_unaligned_list(b.out, n, c->d_act[0], sm + 0, s);
+                    launch_unaligned_list(b.out, n, d_act[0], sm + 0, s);
                     eh = hipMemcpyAsync(hm, sm, 4, hipMemcpyDeviceToHost, s);
                 }
                 if (eh == hipSuccess) eh = hipStreamSynchronize(s);
                 if (eh == hipSuccess && hm[0]) {
-                    launch_chimeric(c->ix, c->cfg, b, c->hs, c->d_act[0], hm[0], c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, sm + 1, d_seg2, s);
+                    launch_chimeric(c->ix, c->cfg, b, c->hs, d_act[0], hm[0], c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, sm + 1, d_seg2, s);
                     eh = hipGetLastError();
                 }
             }
@@ -534,12 +594,12 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         if (c->params.min_chimeric_len > 0 && c->cfg.max_hits > 1)          // (the chimeric call's note to the loci replay, see k_heavy)
             for (size_t i = at; i < at + n; i++)
                 if (c->seg2[i].flags == 0x40) c->seg2[i] = bk_seg2{};
-        tm.end(2, ei, s);
+        tm.end(Span::Heavy, ei, s);
     }
     hipEvent_t e4 = tm.begin(s);
     launch_count_seqs(d_out, n, c->d_id2idx, c->ix.n_ent, c->d_seq_counts, s);
     HIP_TRY(hipGetLastError());
-    tm.end(3, e4, s);
+    tm.end(Span::Other, e4, s);
     if (c->cfg.max_hits > 1 && !c->params.best_matches) {
         int rl = collect_loci(c, b, n, maxlen, s);
         if (rl) return rl;
@@ -589,7 +649,7 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
         const bool plain = c->cfg.max_hits == 1 && !c->params.best_matches && !c->params.micro_indel_len && !c->params.splice_junct_len && !c->params.min_chimeric_len;
         const bool fits = ml >= 1 && ml <= 16u * (uint32_t)kNwLongest && nreads <= c->cap_reads && nreads <= c->chunk_reads && words_per_read(ml) <= c->cap_wpr &&
                           iv_cores_for(c, ml) <= c->cap_iv_cores && rd2w_for(ml) <= c->cap_rd2w &&
-                          (uint64_t)nreads * iv_cores_for(c, ml) * (c->cfg.align_strand == 0 ? 2u : 1u) <= c->cap_slist && (c->ix.isa != nullptr || c->hs.htab != nullptr);
+                          (uint64_t)nreads * iv_cores_for(c, ml) * (c->cfg.align_strand == 0 ? 2u : 1u) <= c->buf.slist.cap() && (c->ix.isa != nullptr || c->hs.htab != nullptr);
         const bool main_path = c->use_wave && c->cfg.heavy_thresh <= 100 && c->ix.k2 != nullptr && c->ix.tgt2 != nullptr && !c->debug && c->async_phases;
         if (!plain || !fits || !main_path) return BK_ERR_PARAMS;
     }
@@ -652,14 +712,14 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
         float m = 0;
         (void)hipEventElapsedTime(&m, sp.second.first, sp.second.second);
         switch (sp.first) {
-        case 0: c->timing.ms_search += m; c->timing.n_search_launches++; break;
-        case 1: c->timing.ms_extend += m; c->timing.n_extend_launches++; break;
-        case 2: c->timing.ms_heavy += m; c->timing.n_heavy_launches++; break;
-        case 4: c->timing.ms_search_a += m; break;           // (inside a span of kind 0)
-        case 5: c->timing.ms_search_sort += m; break;
-        case 6: c->timing.ms_search_b += m; c->timing.n_search_b_launches++; break;
-        case 7: c->timing.ms_prep += m; c->timing.ms_other += m; break;
-        default: c->timing.ms_other += m; break;
+        case Span::Search: c->timing.ms_search += m; c->timing.n_search_launches++; break;
+        case Span::Extend: c->timing.ms_extend += m; c->timing.n_extend_launches++; break;
+        case Span::Heavy: c->timing.ms_heavy += m; c->timing.n_heavy_launches++; break;
+        case Span::SearchA: c->timing.ms_search_a += m; break;           // (inside a span of Span::Search)
+        case Span::SearchSort: c->timing.ms_search_sort += m; break;
+        case Span::SearchB: c->timing.ms_search_b += m; c->timing.n_search_b_launches++; break;
+        case Span::Prep: c->timing.ms_prep += m; c->timing.ms_other += m; break;
+        case Span::Other: c->timing.ms_other += m; break;
         }
     }
     return BK_OK;
@@ -689,16 +749,12 @@ int bk::engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nrea
     HIP_TRY(hipGetLastError());
     size_t need = 0;
     HIP_TRY(bk::prim::exclusive_sum(nullptr, need, (unsigned long long *)d_offs, (unsigned long long *)d_offs, (size_t)nreads, s));
-    if (need > c->scan_tmp_bytes) {
+    if (need > c->buf.scan_tmp.cap()) {
         HIP_TRY(hipStreamSynchronize(s));
-        free_dev(c->d_scan_tmp);
-        c->d_scan_tmp = nullptr;
-        c->scan_tmp_bytes = 0;
-        HIP_TRY(dev_malloc(&c->d_scan_tmp, need + 256));
-        c->scan_tmp_bytes = need + 256;
+        HIP_TRY(c->buf.scan_tmp.ensure(need + 256));
     }
-    size_t tb = c->scan_tmp_bytes;
-    HIP_TRY(bk::prim::exclusive_sum(c->d_scan_tmp, tb, (unsigned long long *)d_offs, (unsigned long long *)d_offs, (size_t)nreads, s));
+    size_t tb = c->buf.scan_tmp.cap();
+    HIP_TRY(bk::prim::exclusive_sum(c->buf.scan_tmp.get(), tb, (unsigned long long *)d_offs, (unsigned long long *)d_offs, (size_t)nreads, s));
     // [0] max over reads of (first word + words) = the batch's word count, [1] longest read; exceptions in range and ascending
     HIP_TRY(hipMemsetAsync(c->d_ctr_aux, 0, 32, s));
     launch_packed_extent(d_offs, d_lens32, nreads, c->d_ctr_aux, s);
@@ -719,9 +775,6 @@ int bk::engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nrea
 int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_hit *d_hits, uint32_t maxlen, const bk_pe_params *pe, hipStream_t s,
                            bk_seg2 *seg2_host, bk_seg2 *seg2_dev)
 {
-    const uint8_t *d_bases = in.bases;
-    const uint64_t *d_offs = in.offs;
-    const uint32_t *d_lens = in.lens;
     const uint32_t nreads = 2 * n_pairs;
     const uint32_t wpr = words_per_read(maxlen);
     // (launch_pe never touches the interval records: the slots keep whatever core count the SE pass sized them for)
@@ -733,29 +786,18 @@ int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_h
         rc = ensure_batch_scratch(c, nreads, wpr, 0, ivc);
     }
     if (rc) return rc;
-    DevBatch b{};
-    b.bases = d_bases; b.offs = d_offs; b.lens = d_lens;
-    b.pk_words = in.words; b.pk_exc = in.exc; b.pk_nexc = in.words ? in.n_exc : 0; b.pk_read0 = 0;
-    b.rd4 = c->d_rd4; b.iv_first = c->d_iv_first; b.iv_n = c->d_iv_n; b.iv2 = c->d_iv2;
-    b.rmeta = c->d_rmeta;
-    b.out = d_hits; b.seq_counts = c->d_seq_counts; b.ctr = c->d_ctr;
-    b.wpr = wpr; b.n_reads = nreads; b.iv_cores = c->cap_iv_cores ? c->cap_iv_cores : kMaxCoresFast;
+    const DevBatch b = make_batch(c, in, 0, nreads, wpr, c->cap_iv_cores, d_hits);
     if (c->params.min_chimeric_len > 0 && !seg2_host && !seg2_dev) return BK_ERR_PARAMS;
     bk_seg2 *d_seg2 = seg2_dev;
     if (!d_seg2 && seg2_host) {
-        if (nreads > c->cap_seg2) {
-            free_dev(c->d_seg2);
-            c->d_seg2 = nullptr;
-            c->cap_seg2 = 0;
-            HIP_TRY(dev_malloc(&c->d_seg2, (size_t)nreads * sizeof(bk_seg2)));
-            c->cap_seg2 = nreads;
-        }
-        d_seg2 = c->d_seg2;
+        rc = ensure_seg2(c, nreads);
+        if (rc) return rc;
+        d_seg2 = c->buf.seg2.get();
         HIP_TRY(hipMemcpyAsync(d_seg2, seg2_host, (size_t)nreads * sizeof(bk_seg2), hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipMemsetAsync(c->d_small, 0, 16 * 4, s));
     launch_pe(c->ix, c->cfg, b, pe->pe_mode, pe->pair_min_len, pe->pair_max_len, pe->pair_strand ? 1 : 0, d_hits, n_pairs,
-              c->d_heavy, c->d_small, c->h_small, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->d_chrom_accept, c->n_chrom_accept, s);
+              c->buf.heavy.get(), c->d_small, c->h_small, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
     HIP_TRY(hipGetLastError());
     if (seg2_host && !seg2_dev) HIP_TRY(hipMemcpyAsync(seg2_host, d_seg2, (size_t)nreads * sizeof(bk_seg2), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -852,41 +894,15 @@ int bk_align_batch(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const 
     if (!c || (nreads && (!bases || !offs || !lens || !out))) return BK_ERR_PARAMS;
     if (!nreads) return BK_OK;
     HIP_TRY(hipSetDevice(c->device));
-    // the reads need not be contiguous in `bases`: find the extent referenced
-    uint64_t lo = ~0ULL, hi = 0;
-    for (uint32_t i = 0; i < nreads; i++) {
-        if (lens[i] > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
-        lo = std::min(lo, offs[i]);
-        hi = std::max(hi, offs[i] + lens[i]);
-    }
-    uint64_t nbytes = hi - lo;
-    if (nbytes + 16 > c->cap_in_bases) {
-        free_dev(c->d_in_bases);
-        c->d_in_bases = nullptr;
-        c->cap_in_bases = 0;
-        HIP_TRY(dev_malloc(&c->d_in_bases, nbytes + 16));
-        c->cap_in_bases = nbytes + 16;
-    }
-    if (nreads > c->cap_in_reads) {
-        free_dev(c->d_in_offs); free_dev(c->d_in_lens); free_dev(c->d_in_out);
-        c->d_in_offs = nullptr; c->d_in_lens = nullptr; c->d_in_out = nullptr;
-        c->cap_in_reads = 0;
-        HIP_TRY(dev_malloc(&c->d_in_offs, (size_t)nreads * 8));
-        HIP_TRY(dev_malloc(&c->d_in_lens, (size_t)nreads * 4));
-        HIP_TRY(dev_malloc(&c->d_in_out, (size_t)nreads * sizeof(bk_hit)));
-        c->cap_in_reads = nreads;
-    }
-    std::vector<uint64_t> rel(nreads);
-    for (uint32_t i = 0; i < nreads; i++) rel[i] = offs[i] - lo;
-    HIP_TRY(hipMemcpyAsync(c->d_in_bases, bases + lo, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_in_offs, rel.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_in_lens, lens, (size_t)nreads * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HostExtent x;
     DevReads in;
-    in.bases = c->d_in_bases; in.offs = c->d_in_offs; in.lens = c->d_in_lens;
-    int rc = align_device(c, in, nreads, c->d_in_out, c->stream);
+    int rc = stage_host_batch(c, bases, offs, lens, nreads, x, in);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, c->d_in_out, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    bk_hit *d_out = c->buf.in_out.get();
+    rc = align_device(c, in, nreads, d_out, c->stream);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out, d_out, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
 
@@ -1002,46 +1018,22 @@ int bk_align_batch_packed(bk_ctx *c, const uint32_t *words, uint64_t n_words, co
     // (k_prep_fused<NW, PACKED> loads NW words from a read's first one whatever its length - up to kNwLongest for a batch whose
     // longest read has 257 .. 512 bases - so the buffer is padded by that many words behind the last read)
     static_assert(kPackedPadWords >= kNwLongest, "packed read words must be padded by the widest register-window family");
-    if (n_words + kPackedPadWords > c->cap_in_words) {
-        free_dev(c->d_in_words);
-        c->d_in_words = nullptr;
-        c->cap_in_words = 0;
-        HIP_TRY(dev_malloc(&c->d_in_words, (n_words + kPackedPadWords) * 4));
-        c->cap_in_words = n_words + kPackedPadWords;
-    }
-    if (n_exc > c->cap_in_exc) {
-        free_dev(c->d_in_exc);
-        c->d_in_exc = nullptr;
-        c->cap_in_exc = 0;
-        HIP_TRY(dev_malloc(&c->d_in_exc, n_exc * sizeof(bk_nbase)));
-        c->cap_in_exc = n_exc;
-    }
-    if (nreads > c->cap_in_reads) {
-        free_dev(c->d_in_offs); free_dev(c->d_in_lens); free_dev(c->d_in_out); free_dev(c->d_in_lens16);
-        c->d_in_offs = nullptr; c->d_in_lens = nullptr; c->d_in_out = nullptr; c->d_in_lens16 = nullptr;
-        c->cap_in_reads = 0;
-        HIP_TRY(dev_malloc(&c->d_in_offs, (size_t)nreads * 8));
-        HIP_TRY(dev_malloc(&c->d_in_lens, (size_t)nreads * 4));
-        HIP_TRY(dev_malloc(&c->d_in_out, (size_t)nreads * sizeof(bk_hit)));
-        c->cap_in_reads = nreads;
-    }
-    if (!c->d_in_lens16 || nreads > c->cap_in_lens16) {
-        free_dev(c->d_in_lens16);
-        c->d_in_lens16 = nullptr;
-        HIP_TRY(dev_malloc(&c->d_in_lens16, (size_t)std::max(nreads, c->cap_in_reads) * 2));
-        c->cap_in_lens16 = std::max(nreads, c->cap_in_reads);
-    }
-    if (n_words) HIP_TRY(hipMemcpyAsync(c->d_in_words, words, n_words * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_in_lens16, lens, (size_t)nreads * 2, hipMemcpyHostToDevice, s));
-    if (n_exc) HIP_TRY(hipMemcpyAsync(c->d_in_exc, exc, n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s));
+    BatchBufs &m = c->buf;
+    HIP_TRY(m.in_words.ensure(n_words + kPackedPadWords));
+    HIP_TRY(m.in_exc.ensure(n_exc));
+    int rc = ensure_in_reads(c, nreads, true);
+    if (rc) return rc;
+    if (n_words) HIP_TRY(hipMemcpyAsync(m.in_words.get(), words, n_words * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.in_lens16.get(), lens, (size_t)nreads * 2, hipMemcpyHostToDevice, s));
+    if (n_exc) HIP_TRY(hipMemcpyAsync(m.in_exc.get(), exc, n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s));
     uint32_t maxlen = 0;
-    int rc = engine_prepare_packed(c, c->d_in_lens16, nreads, n_words, c->d_in_exc, n_exc, c->d_in_lens, c->d_in_offs, &maxlen, s);
+    rc = engine_prepare_packed(c, m.in_lens16.get(), nreads, n_words, m.in_exc.get(), n_exc, m.in_lens.get(), m.in_offs.get(), &maxlen, s);
     if (rc) return rc;
     DevReads in;
-    in.offs = c->d_in_offs; in.lens = c->d_in_lens; in.words = c->d_in_words; in.exc = c->d_in_exc; in.n_exc = n_exc;
-    rc = align_device(c, in, nreads, c->d_in_out, s);
+    in.offs = m.in_offs.get(); in.lens = m.in_lens.get(); in.words = m.in_words.get(); in.exc = m.in_exc.get(); in.n_exc = n_exc;
+    rc = align_device(c, in, nreads, m.in_out.get(), s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, c->d_in_out, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, m.in_out.get(), (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
 
@@ -1061,44 +1053,17 @@ int bk_pair_batch_seg2(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, co
     if (n_pairs > 0x7fffffffu) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t nreads = 2 * n_pairs;
-    uint64_t lo = ~0ULL, hi = 0;
-    uint32_t maxlen = 0;
-    for (uint32_t i = 0; i < nreads; i++) {
-        if (lens[i] > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
-        lo = std::min(lo, offs[i]);
-        hi = std::max(hi, offs[i] + lens[i]);
-        maxlen = std::max(maxlen, lens[i]);
-    }
-    uint64_t nbytes = hi - lo;
-    if (nbytes + 16 > c->cap_in_bases) {
-        free_dev(c->d_in_bases);
-        c->d_in_bases = nullptr;
-        c->cap_in_bases = 0;
-        HIP_TRY(dev_malloc(&c->d_in_bases, nbytes + 16));
-        c->cap_in_bases = nbytes + 16;
-    }
-    if (nreads > c->cap_in_reads) {
-        free_dev(c->d_in_offs); free_dev(c->d_in_lens); free_dev(c->d_in_out);
-        c->d_in_offs = nullptr; c->d_in_lens = nullptr; c->d_in_out = nullptr;
-        c->cap_in_reads = 0;
-        HIP_TRY(dev_malloc(&c->d_in_offs, (size_t)nreads * 8));
-        HIP_TRY(dev_malloc(&c->d_in_lens, (size_t)nreads * 4));
-        HIP_TRY(dev_malloc(&c->d_in_out, (size_t)nreads * sizeof(bk_hit)));
-        c->cap_in_reads = nreads;
-    }
-    std::vector<uint64_t> rel(nreads);
-    for (uint32_t i = 0; i < nreads; i++) rel[i] = offs[i] - lo;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(c->d_in_bases, bases + lo, nbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_in_offs, rel.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_in_lens, lens, (size_t)nreads * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_in_out, hits, (size_t)nreads * sizeof(bk_hit), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HostExtent x;
     DevReads in;
-    in.bases = c->d_in_bases; in.offs = c->d_in_offs; in.lens = c->d_in_lens;
-    int rc = engine_pair_device(c, in, n_pairs, c->d_in_out, maxlen, pe, s, seg2, nullptr);
+    int rc = stage_host_batch(c, bases, offs, lens, nreads, x, in);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(hits, c->d_in_out, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
+    hipStream_t s = c->stream;
+    bk_hit *d_hits = c->buf.in_out.get();
+    HIP_TRY(hipMemcpyAsync(d_hits, hits, (size_t)nreads * sizeof(bk_hit), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    rc = engine_pair_device(c, in, n_pairs, d_hits, x.maxlen, pe, s, seg2, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(hits, d_hits, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
 
@@ -1148,10 +1113,10 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
     if (!act && !first && !count) return BK_OK;
     if (!act || !first || !count || ctl.n_act > cap_reads || ctl.n_act > c->dbg_n) return BK_ERR_PARAMS;
     const uint32_t na = ctl.n_act, stride = c->dbg_n, planes = 2 * c->dbg_ivc;
-    HIP_TRY(hipMemcpy(act, c->d_act[c->dbg_cur], (size_t)na * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(act, c->buf.act[c->dbg_cur].get(), (size_t)na * 4, hipMemcpyDeviceToHost));
     // cores of every listed read in that phase: the search writes no slot beyond them, and like the kernels behind it this reads none
     std::vector<uint32_t> meta(c->dbg_n), nc(na);
-    HIP_TRY(hipMemcpy(meta.data(), c->d_rmeta, (size_t)c->dbg_n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(meta.data(), c->buf.rmeta.get(), (size_t)c->dbg_n * 4, hipMemcpyDeviceToHost));
     for (uint32_t a = 0; a < na; a++) {
         if (act[a] >= c->dbg_n) return BK_ERR_INTERNAL;
         const int len = (int)(meta[act[a]] & kReadLenMask);
@@ -1162,16 +1127,16 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
         nc[a] = n <= kMaxCoresFast ? (uint32_t)n : 0u;
     }
     std::vector<uint2> h2;
-    if (c->d_iv2) h2.resize(na);
+    if (c->buf.iv2.get()) h2.resize(na);
     for (uint32_t pl = 0; pl < planes; pl++) {
         uint64_t *f = first + (size_t)pl * na;
         uint32_t *q = count + (size_t)pl * na;
-        if (c->d_iv2) {
-            HIP_TRY(hipMemcpy(h2.data(), c->d_iv2 + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
+        if (c->buf.iv2.get()) {
+            HIP_TRY(hipMemcpy(h2.data(), c->buf.iv2.get() + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
             for (uint32_t a = 0; a < na; a++) { f[a] = h2[a].x; q[a] = h2[a].y; }
         } else {
-            HIP_TRY(hipMemcpy(f, c->d_iv_first + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(q, c->d_iv_n + (size_t)pl * stride, (size_t)na * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(f, c->buf.iv_first.get() + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(q, c->buf.iv_n.get() + (size_t)pl * stride, (size_t)na * 4, hipMemcpyDeviceToHost));
         }
         for (uint32_t a = 0; a < na; a++)
             if (pl % c->dbg_ivc >= nc[a]) { f[a] = 0; q[a] = 0; }

@@ -32,7 +32,6 @@
 
 namespace bk {
 // launchers defined in the kernel files (*.hip)
-// launchers defined in the kernel files (*.hip)
 void launch_pack_target(const uint8_t *seq, uint64_t n, uint64_t *tgt4, uint64_t nwords, hipStream_t s);
 void launch_pack_target2(const uint64_t *tgt4, uint64_t nwords4, uint64_t *tgt2, unsigned int *nflag32, int flag_shift, hipStream_t s);
 void launch_split_sa5(const uint8_t *sa5, uint64_t n, uint32_t *lo, uint8_t *hi, hipStream_t s);
@@ -178,5 +177,14 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
 int size_heavy_scratch(bk_ctx *c);
 int ensure_batch_scratch(bk_ctx *c, uint32_t n_reads, uint32_t wpr, uint32_t rd2w = 0, uint32_t iv_cores = kMaxCoresFast);
 int ensure_sort_scratch(bk_ctx *c, uint32_t n, hipStream_t s);
+int ensure_slist(bk_ctx *c, uint64_t lanes, hipStream_t s);          // (waits for `s` before it frees)
+inline int ensure_seg2(bk_ctx *c, uint32_t n) { HIP_TRY(c->buf.seg2.ensure(n)); return BK_OK; }      // second segments of a chunk, of a pair batch
+// host batches need not be contiguous in their `bases`: the extent lo .. hi the reads reference, their offsets relative to lo, the longest
+struct HostExtent {
+    uint64_t lo = ~0ULL, hi = 0;
+    uint32_t maxlen = 0;
+    std::vector<uint64_t> rel;
+};
+HostExtent host_extent(const uint64_t *offs, const uint32_t *lens, uint32_t nreads);
 int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known = 0, bool enqueue_only = false);
 }  // namespace bk

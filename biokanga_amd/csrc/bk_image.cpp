@@ -562,13 +562,9 @@ int adopt_device_image(bk_ctx *c, const uint8_t *d_seq, uint64_t n, const uint8_
 // (bk_index.hip, k_swin_cover: a tenth of a 3.1 Gbp index), within a budget of the HBM that is free next to this batch's scratch.
 }  // namespace bk
 
-// frees the suffix-ordered window array (and does not build it again): called when something else needs the HBM
-void bk::release_swin(bk_ctx *c)
+// the window array and its map given back (the caller has waited for whatever reads them)
+void bk::drop_swin(bk_ctx *c)
 {
-    if (!c || !c->d_swin) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipDeviceSynchronize();
     free_dev(c->d_swin);
     free_dev(c->d_swmap);
     c->d_swin = nullptr;
@@ -576,6 +572,16 @@ void bk::release_swin(bk_ctx *c)
     c->ix.swin = nullptr;
     c->ix.swmap = nullptr;
     c->swin_bytes = 0;
+}
+
+// frees the suffix-ordered window array (and does not build it again): called when something else needs the HBM
+void bk::release_swin(bk_ctx *c)
+{
+    if (!c || !c->d_swin) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    (void)hipDeviceSynchronize();
+    drop_swin(c);
     c->swin_denied = true;
     fprintf(stderr, "biokanga_amd: window array released to make room\n");
 }
@@ -854,8 +860,7 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
         if (full == (c->d_swmap == nullptr) && (full ? c->ix.sw_words == words : (c->swin_w == w_key || (c->swin_rebuilt && c->ix.sw_words == words)))) return BK_OK;
         c->swin_rebuilt = true;
         HIP_TRY(hipStreamSynchronize(s));
-        free_dev(c->d_swin); free_dev(c->d_swmap);
-        c->d_swin = nullptr; c->d_swmap = nullptr; c->ix.swin = nullptr; c->ix.swmap = nullptr; c->swin_bytes = 0;
+        drop_swin(c);
     }
     // (it serves the register-window kernel families of reads of up to 128 and up to 256 bases: every core of reads of up to 100 / 160
     // bases, the middle cores of longer ones; 2: made whatever the batch)
@@ -1148,18 +1153,13 @@ void bk_ctx_destroy(bk_ctx *c)
     grow_drop(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_dev(c->d_tgt4); free_dev(c->d_sa_lo); free_dev(c->d_sa_hi);
-    free_dev(c->d_snp_planes); free_dev(c->d_snp_tot); free_dev(c->d_snp_sites); free_dev(c->d_ent_start); free_dev(c->d_ent_end); free_dev(c->d_ent_id); free_dev(c->d_id2idx); free_dev(c->d_ktab); free_dev(c->d_ktab_hi); free_dev(c->d_k2); free_dev(c->d_kx[0]); free_dev(c->d_kx[1]); free_dev(c->d_slist); free_dev(c->d_slist_stage); free_dev(c->d_sort[0]); free_dev(c->d_sort[1]); free_dev(c->d_sort[2]); free_dev(c->d_sort_tmp); free_dev(c->d_tgt2); free_dev(c->d_tgt2s); free_dev(c->d_nflag); free_dev(c->d_rd2); free_dev(c->d_rmeta);
-    free_dev(c->d_rd4); free_dev(c->d_iv_first); free_dev(c->d_iv_n); free_dev(c->d_iv2);
-    free_dev(c->d_act[0]); free_dev(c->d_act[1]); free_dev(c->d_heavy); free_dev(c->d_wave); free_dev(c->d_iv32); free_dev(c->d_wave_work); free_dev(c->d_small);
-    for (int i = 0; i < 3; i++) free_dev(c->d_stage[i]);
-    free_dev(c->d_stripe_cnt);
-    free_dev(c->d_isa); free_dev(c->d_swin); free_dev(c->d_swmap); free_dev(c->d_seg2); free_dev(c->d_seq_global);
-    free_dev(c->d_seq_counts); free_dev(c->d_ctr); free_dev(c->hs.htab); free_dev(c->hs.slot_epoch);
-    free_dev(c->d_in_bases); free_dev(c->d_in_offs); free_dev(c->d_in_lens); free_dev(c->d_in_out);
-    free_dev(c->d_in_words); free_dev(c->d_in_lens16); free_dev(c->d_in_exc); free_dev(c->d_scan_tmp); free_dev(c->d_ctr_aux);
+    free_dev(c->d_snp_planes); free_dev(c->d_snp_tot); free_dev(c->d_ent_start); free_dev(c->d_ent_end); free_dev(c->d_ent_id); free_dev(c->d_id2idx); free_dev(c->d_ktab); free_dev(c->d_ktab_hi); free_dev(c->d_k2); free_dev(c->d_kx[0]); free_dev(c->d_kx[1]); free_dev(c->d_tgt2); free_dev(c->d_tgt2s); free_dev(c->d_nflag);
+    c->release_batch_buffers();           // everything grown on demand (bk_ctx::buf), while the device is current and the stream still there
+    free_dev(c->d_small);
+    free_dev(c->d_isa); free_dev(c->d_swin); free_dev(c->d_swmap); free_dev(c->d_seq_global);
+    free_dev(c->d_seq_counts); free_dev(c->d_ctr); free_dev(c->d_ctr_aux);
     if (c->h_small) (void)hipHostFree(c->h_small);
     free_dev(c->d_ctl);
-    free_dev(c->d_chrom_accept);
     for (void *&t : c->sam_text) if (t) { (void)hipHostFree(t); t = nullptr; }
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);

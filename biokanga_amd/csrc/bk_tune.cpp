@@ -21,15 +21,8 @@ int bk_ctx_reserve(bk_ctx *c, uint32_t max_batch_reads, uint32_t max_read_len)
     if (c->ix.k2) {
         // pass B's work list: at most one item per (read, strand, core)
         const uint64_t lanes = (uint64_t)n * ivc * (c->cfg.align_strand == 0 ? 2u : 1u);
-        if (lanes > c->cap_slist) {
-            free_dev(c->d_slist);
-            free_dev(c->d_slist_stage);
-            c->d_slist = c->d_slist_stage = nullptr;
-            c->cap_slist = 0;
-            HIP_TRY(dev_malloc(&c->d_slist, lanes * 4));
-            HIP_TRY(dev_malloc(&c->d_slist_stage, (lanes + (kListStripes + 2) * 1024) * 4));
-            c->cap_slist = lanes;
-        }
+        rc = ensure_slist(c, lanes, c->stream);
+        if (rc) return rc;
     }
     if (c->sort_lists) { rc = ensure_sort_scratch(c, n, c->stream); if (rc) return rc; }      // (grown when a phase's list is longer)
     if (c->use_wave && c->ix.isa == nullptr) { rc = size_heavy_scratch(c); if (rc) return rc; }     // hash-set dedupe of the wave kernel
@@ -41,12 +34,11 @@ int bk_ctx_set_chrom_filter(bk_ctx *c, const uint8_t *accept, uint32_t n)
     if (!c || (n && !accept)) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_dev(c->d_chrom_accept);
-    c->d_chrom_accept = nullptr;
+    c->buf.chrom_accept.reset();
     c->n_chrom_accept = 0;
     if (!n) return BK_OK;
-    HIP_TRY(dev_malloc(&c->d_chrom_accept, n));
-    HIP_TRY(hipMemcpy(c->d_chrom_accept, accept, n, hipMemcpyHostToDevice));
+    HIP_TRY(c->buf.chrom_accept.ensure(n));
+    HIP_TRY(hipMemcpy(c->buf.chrom_accept.get(), accept, n, hipMemcpyHostToDevice));
     c->n_chrom_accept = n;
     return BK_OK;
 }
@@ -149,13 +141,7 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->swin_denied = false;
         if (c->d_swin && (!c->use_swin || (c->use_swin == 3) != (c->d_swmap == nullptr))) {
             if (c->stream) (void)hipStreamSynchronize(c->stream);
-            free_dev(c->d_swin);
-            free_dev(c->d_swmap);
-            c->d_swin = nullptr;
-            c->d_swmap = nullptr;
-            c->ix.swin = nullptr;
-            c->ix.swmap = nullptr;
-            c->swin_bytes = 0;
+            drop_swin(c);
         }
         return old;
     }
