@@ -1,5 +1,6 @@
 // bk_dev_trim.h - CSfxArrayV3::AdaptiveTrim on the device, shared by the chimeric form of k_heavy (bk_heavy.hip) and the paired-end
-// orphan recovery (bk_rescue.hip).
+// orphan recovery (bk_rescue.hip), and the orphan recovery's window check (pe_window_ok, pe_window_key) - here so that the test kernels of
+// tests/hip/devtest.hip can include them as they stand.
 #pragma once
 #include "bk_dev_util.h"
 
@@ -94,6 +95,62 @@ __device__ int adaptive_trim_dev(const uint64_t *__restrict__ rdw, const uint64_
     if (best_len < min_trim) return 0;
     trim_mm = best_mm; trim5 = best_start; trim3 = best_end;
     return best_len;
+}
+
+// AdaptiveTrim(full length) acceptance of the read (packed words rdw) against the target at t
+__device__ __forceinline__ bool pe_window_ok(const uint64_t *__restrict__ rdw, int len, const uint64_t *__restrict__ tgt, uint64_t t,
+                                             int max_mm, int &mm_out)
+{
+    int mm = 0, run = 0;
+    bool have8 = false, first3 = false;
+    for (int i = 0; i < len; i += 16) {
+        int nv = len - i < 16 ? len - i : 16;
+        uint64_t x = (nib16(rdw, i) ^ nib16(tgt, t + i)) & top_mask(nv);
+        uint64_t f = (x | (x >> 1) | (x >> 2) | (x >> 3)) & 0x1111111111111111ULL;
+        uint32_t bits = flags_to_bits16(f);                         // bit k = base i+k mismatches
+        uint32_t valid = nv >= 16 ? 0xFFFFu : ((1u << nv) - 1);
+        uint32_t g = ~bits & valid;                                 // bit k = base matches
+        mm += __popc(bits);
+        if (i == 0) first3 = (g & 7u) == 7u;
+        // runs of >= 8 matches: inside the word, or continuing the run carried from previous words
+        uint32_t y = g & (g >> 1);
+        y &= y >> 2;
+        y &= y >> 4;
+        int lead = __ffs((int)(~g & 0x1FFFFu)) - 1;                 // matches at the start of this word (0..16)
+        if (lead > nv) lead = nv;
+        if (y != 0 || run + lead >= 8) have8 = true;
+        if (g == valid) run += nv;
+        else run = nv - (32 - __clz((int)(~g & valid)));            // matches after the last mismatch of this word
+    }
+    mm_out = mm;
+    if (len < 25 || len > 2048 || max_mm > 15) return false;         // AdaptiveTrim parameter validation -> eBSFerrParams
+    if (!have8 || !first3 || run < 3) return false;
+    if (mm > 0 && max_mm == 0) return false;
+    if ((max_mm + 1.0) / 100.0 <= (double)mm / (double)len) return false;
+    return true;
+}
+
+// One candidate window of AlignPairedRead.  ATW == 0: the partner must fit whole (MinChimericLen == 0, MinPutLen = ReadLen); otherwise
+// AdaptiveTrim may cut its ends down to min_put bases (SfxArrayV2.cpp:8327-8330,8400-8470).  The reference raises MinPutLen to the length of
+// every placement it takes and hands that to the next AdaptiveTrim call; a call with the initial MinPutLen returns the same stretch whenever
+// that stretch is at least as long as the raised limit and nothing acceptable otherwise (the limit only removes shorter candidates from
+// AdaptiveTrim's scan), so the outcome of the scan is the first window with the longest stretch and, among those, the fewest mismatches.
+// key: smaller = better; ~0 = not a candidate.  Bits 52.. = 4095 - trimmed length, bits 40..51 = mismatches, low 40 bits = scan order.
+template <int ATW>
+__device__ __forceinline__ unsigned long long pe_window_key(const uint64_t *__restrict__ rdw, int len, const uint64_t *__restrict__ tgt, uint64_t t,
+                                                            int max_mm, int min_put, unsigned long long order, int &t5, int &t3)
+{
+    t5 = 0; t3 = 0;
+    if constexpr (ATW == 0) {
+        int mm;
+        if (!(pe_window_ok(rdw, len, tgt, t, max_mm, mm) && mm <= max_mm)) return ~0ULL;
+        return ((unsigned long long)(4095 - len) << 52) | ((unsigned long long)mm << 40) | order;
+    } else {
+        int mm;
+        const int r = adaptive_trim_dev<ATW>(rdw, tgt, t, len, min_put, max_mm, 3, mm, t5, t3);
+        if (r < min_put || r == 0 || (r == min_put && mm > max_mm)) return ~0ULL;
+        return ((unsigned long long)(4095 - r) << 52) | ((unsigned long long)mm << 40) | order;
+    }
 }
 
 }  // namespace bk

@@ -1533,6 +1533,12 @@ static int adaptive_trim_ex(uint32_t seq_len, const uint8_t *probe, const uint8_
     return 0;
 }
 
+int ora_adaptive_trim(uint32_t len, const uint8_t *probe, const uint8_t *targ, uint32_t min_trim, uint32_t max_mm, uint32_t min_flank,
+                      uint32_t *mm, uint32_t *trim5, uint32_t *trim3)
+{
+    return adaptive_trim_ex(len, probe, targ, min_trim, max_mm, min_flank, mm, trim5, trim3);
+}
+
 /* AlignPairedRead, SfxArrayV2.cpp:8247-8433 (MinChimericLen = 0) */
 static int align_paired_read(const ora_sfx *s, int b3prime, int antisense, uint32_t chrom_id, uint32_t start_loci, uint32_t end_loci,
                              int min_dist, int max_dist, int max_allowed_mm, int read_len, int min_chimeric_pct, int core_len, int core_delta,

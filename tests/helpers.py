@@ -116,6 +116,9 @@ def oracle_lib():
     lib.ora_locate_cores.restype = None
     lib.ora_sa_element.argtypes = [ctypes.c_void_p, ctypes.c_int64]
     lib.ora_sa_element.restype = ctypes.c_int64
+    lib.ora_adaptive_trim.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.ora_adaptive_trim.restype = ctypes.c_int
     _oracle = lib
     return lib
 
@@ -142,7 +145,9 @@ def devtest_lib():
                        ("bkdt_htab_rounds", [vp, u32, u32, vp, vp, vp, u32, vp]),
                        ("bkdt_same_key", [vp, vp, u32, vp]),
                        ("bkdt_window2i", [i32, i32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp]),
-                       ("bkdt_window_rare", [i32, vp, u32, i32, vp, vp, vp, u32, vp, vp, vp, vp])):
+                       ("bkdt_window_rare", [i32, vp, u32, i32, vp, vp, vp, u32, vp, vp, vp, vp]),
+                       ("bkdt_adaptive_trim", [i32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
+                       ("bkdt_pe_window", [i32, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int

@@ -1,10 +1,11 @@
-// devtest.hip - test-only kernels around the device helpers of biokanga_amd/csrc (bk_dev_sets.h, bk_dev_window.h), included as they
-// stand.  Built as biokanga_amd/lib/libbk_devtest.so (csrc/Makefile); tests/helpers.py devtest_lib() loads it.  Every launcher takes raw
+// devtest.hip - test-only kernels around the device helpers of biokanga_amd/csrc (bk_dev_sets.h, bk_dev_window.h, bk_dev_trim.h), included as
+// they stand.  Built as biokanga_amd/lib/libbk_devtest.so (csrc/Makefile); tests/helpers.py devtest_lib() loads it.  Every launcher takes raw
 // device pointers, launches on the null stream, synchronises and returns the hipError_t.  The helpers' probe loops end only at a free
 // slot: the caller keeps an LDS set within kLdsSetFill keys and an HBM table at most half full (tombstones counted), epochs in
 // [1, kTombBit).
 #include "../../biokanga_amd/csrc/bk_dev_sets.h"
 #include "../../biokanga_amd/csrc/bk_dev_window.h"
+#include "../../biokanga_amd/csrc/bk_dev_trim.h"
 
 using namespace bk;
 
@@ -111,6 +112,42 @@ __global__ void __launch_bounds__(64) k_window_rare(const uint64_t *__restrict__
     eos[i] = w4.eos ? 1 : 0;
 }
 
+// one candidate per lane, every lane with its own length and parameters (the run loops diverge inside a wave, as in k_heavy):
+// rows[n][row_words] 4 bit/base words
+template <int ATW>
+__global__ void __launch_bounds__(64) k_adaptive_trim(const uint64_t *__restrict__ rows, uint32_t row_words, const int *__restrict__ len,
+                                                      const uint64_t *__restrict__ t, const uint64_t *__restrict__ tgt4, const int *__restrict__ min_trim,
+                                                      const int *__restrict__ max_mm, const int *__restrict__ min_flank, uint32_t n, int *__restrict__ out_len,
+                                                      int *__restrict__ out_mm, int *__restrict__ out_t5, int *__restrict__ out_t3)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int mm, t5, t3;
+    out_len[i] = adaptive_trim_dev<ATW>(rows + (uint64_t)i * row_words, tgt4, t[i], len[i], min_trim[i], max_mm[i], min_flank[i], mm, t5, t3);
+    out_mm[i] = mm; out_t5[i] = t5; out_t3[i] = t3;
+}
+
+// pe_window_key<ATW> of one candidate window per lane; ATW == 0: pe_window_ok's own result and mismatch count as well
+template <int ATW>
+__global__ void __launch_bounds__(64) k_pe_window(const uint64_t *__restrict__ rows, uint32_t row_words, const int *__restrict__ len,
+                                                  const uint64_t *__restrict__ t, const uint64_t *__restrict__ tgt4, const int *__restrict__ max_mm,
+                                                  const int *__restrict__ min_put, const unsigned long long *__restrict__ order, uint32_t n,
+                                                  unsigned long long *__restrict__ key_out, int *__restrict__ out_t5, int *__restrict__ out_t3,
+                                                  uint8_t *__restrict__ ok_out, int *__restrict__ mm_out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t *rdw = rows + (uint64_t)i * row_words;
+    int t5, t3;
+    key_out[i] = pe_window_key<ATW>(rdw, len[i], tgt4, t[i], max_mm[i], min_put[i], order[i], t5, t3);
+    out_t5[i] = t5; out_t3[i] = t3;
+    if constexpr (ATW == 0) {
+        int mm;
+        ok_out[i] = pe_window_ok(rdw, len[i], tgt4, t[i], max_mm[i], mm) ? 1 : 0;
+        mm_out[i] = mm;
+    }
+}
+
 int finish()
 {
     hipError_t e = hipGetLastError();
@@ -179,6 +216,34 @@ int bkdt_window_rare(int nw, const uint64_t *rows, uint32_t row_words, int four,
     if (nw == 8) hipLaunchKernelGGL((k_window_rare<8>), grid, block, 0, 0, rows, row_words, four, len, t, tgt4, n, bm, im, mm, eos);
     else if (nw == 16) hipLaunchKernelGGL((k_window_rare<16>), grid, block, 0, 0, rows, row_words, four, len, t, tgt4, n, bm, im, mm, eos);
     else return (int)hipErrorInvalidValue;
+    return finish();
+}
+
+// rows: n rows of row_words 4 bit/base words, row_words >= 4 atw + 1 (a read of 64 atw bases and the word nib16 loads behind it); tgt4 is
+// followed by a word of padding as well.  atw = 8 or 32 (the instantiations of k_heavy)
+int bkdt_adaptive_trim(int atw, const uint64_t *rows, uint32_t row_words, const int *len, const uint64_t *t, const uint64_t *tgt4, const int *min_trim,
+                       const int *max_mm, const int *min_flank, uint32_t n, int *out_len, int *out_mm, int *out_t5, int *out_t3)
+{
+    if ((atw != 8 && atw != 32) || row_words < 4u * (uint32_t)atw + 1) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    if (atw == 8) hipLaunchKernelGGL((k_adaptive_trim<8>), grid, block, 0, 0, rows, row_words, len, t, tgt4, min_trim, max_mm, min_flank, n, out_len, out_mm, out_t5, out_t3);
+    else hipLaunchKernelGGL((k_adaptive_trim<32>), grid, block, 0, 0, rows, row_words, len, t, tgt4, min_trim, max_mm, min_flank, n, out_len, out_mm, out_t5, out_t3);
+    return finish();
+}
+
+// the inputs of bkdt_adaptive_trim that pe_window_key takes (its flanks are 3, min_put is its min_trim) and the window's scan order.
+// atw = 0 (the read whole: pe_window_ok, whose result and mismatch count go to ok_out / mm_out - left alone otherwise), 8 or 32.
+// pe_window_ok reads the whole row before it looks at the length: with atw = 0 every len must be at most 16 (row_words - 1)
+int bkdt_pe_window(int atw, const uint64_t *rows, uint32_t row_words, const int *len, const uint64_t *t, const uint64_t *tgt4, const int *max_mm, uint32_t n,
+                   const int *min_put, const unsigned long long *order, unsigned long long *key_out, int *t5, int *t3, uint8_t *ok_out, int *mm_out)
+{
+    if ((atw != 0 && atw != 8 && atw != 32) || row_words < 4u * (uint32_t)atw + 1 || row_words < 2) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    if (atw == 0) hipLaunchKernelGGL((k_pe_window<0>), grid, block, 0, 0, rows, row_words, len, t, tgt4, max_mm, min_put, order, n, key_out, t5, t3, ok_out, mm_out);
+    else if (atw == 8) hipLaunchKernelGGL((k_pe_window<8>), grid, block, 0, 0, rows, row_words, len, t, tgt4, max_mm, min_put, order, n, key_out, t5, t3, ok_out, mm_out);
+    else hipLaunchKernelGGL((k_pe_window<32>), grid, block, 0, 0, rows, row_words, len, t, tgt4, max_mm, min_put, order, n, key_out, t5, t3, ok_out, mm_out);
     return finish();
 }
 
