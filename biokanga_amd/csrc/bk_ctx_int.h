@@ -1,9 +1,10 @@
 // bk_ctx_int.h - internal: the context behind the C ABI (include/biokanga_amd.h), shared by bk_engine.cpp (batch driver)
 // and bk_stream.cpp (overlapped host <-> device pipeline).  Not part of the boundary.
-// Who owns what: the index image (d_tgt4 .. d_swmap, the grow_* set) and the small fixed buffers (d_small, d_ctl, the counters, the SNP
-// planes) are raw pointers of bk_ctx, allocated by bk_image.cpp and freed by name in bk_ctx_destroy.  Everything the batch driver and the
-// entry points grow on demand is a bk::DevBuf in bk_ctx::buf (BatchBufs): its capacity is the buffer's own, and bk_ctx_destroy releases
-// the lot with release_batch_buffers().  POD structs that travel to kernels (HeavyScratch, DevBatch) carry raw pointers into them.
+// Who owns what: every device allocation of a context is a bk::DevBuf, whose capacity is the buffer's own size.  The index image and the
+// grow worker's tables are bk_ctx::image (ImageBufs, filled by bk_image.cpp), the small fixed buffers (counters, phase control, the SNP
+// planes) bk_ctx::fixed (FixedBufs), and everything the batch driver and the entry points grow on demand bk_ctx::buf (BatchBufs).
+// bk_ctx_destroy frees nothing by name: release_image_buffers() and release_batch_buffers() give the lot back.  POD structs that travel to
+// kernels (DevIndex - set from the image by publish_index alone - HeavyScratch, DevBatch) carry raw pointers into them.
 #pragma once
 #include <atomic>
 #include <thread>
@@ -51,6 +52,29 @@ struct BatchBufs {
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
 };
+// the index image in HBM, one owner per allocation; bk::publish_index (bk_image.cpp) sets the pointers of DevIndex from them
+struct ImageBufs {
+    DevBuf<uint64_t> tgt4, tgt2, tgt2s;   // packed target, 4 bit/base; its 2 bit/base copy, the same stored 32 bytes later (DevIndex::tgt2, tgt2s)
+    DevBuf<uint32_t> sa_lo, isa;          // suffix array (low 32 bits of every element), inverse suffix array
+    DevBuf<uint8_t> sa_hi, nflag;         // fifth byte of an index's 5-byte elements (empty otherwise); N/EOS block bitmap beside tgt2
+    DevBuf<uint64_t> ent_start, ent_end;  // entry table
+    DevBuf<uint32_t> ent_id, id2idx;
+    DevBuf<uint8_t> ktab;                 // k-mer table, in bytes: it has four views (DevIndex::ktab32 / ktab64 / ktab_hi + ktab32 / ktab2)
+    DevBuf<uint64_t> ktab_hi;             // .. a 64-bit start per 2^16 codes where the table is 32-bit offsets from those ("ktab_wide" 1; every group spans < 2^32 suffixes)
+    DevBuf<uint32_t> k2, kx[kMoreKeys];   // second-level search keys; third-, fourth-level (DevIndex::k2, kx)
+    DevBuf<uint8_t> swin;                 // suffix-ordered window array (DevIndex::swin), built when the first batch it serves arrives
+    DevBuf<uint32_t> swmap;               // .. and which blocks of the suffix array it holds (DevIndex::swmap; empty: all of them)
+    DevBuf<uint32_t> grow_kx[kMoreKeys];  // BK_CTX_GROW_IMAGE: what the worker has made - its thread's alone until the batches' thread has
+    DevBuf<uint8_t> grow_ktab2;           // .. joined it or acquire-loaded grow_state - and the batches' thread has not yet taken in
+};
+// the context's small device buffers of fixed size
+struct FixedBufs {
+    DevBuf<uint32_t> small;               // [0] act_cnt [1] next_cnt [2] heavy_cnt [3] cmax [4] cursor [5] maxlen [6] wave_cnt [7] wave cursor
+    DevBuf<PhaseCtl> ctl;                 // kMaxPhases + 2 lines: the counts of a chunk's phases (bk_device.h)
+    DevBuf<unsigned long long> seq_counts, ctr, ctr_aux, snp_tot;
+    DevBuf<unsigned long long> seq_global;        // bk_seq_counts_allreduce: the counts summed over every context of the run
+    DevBuf<uint32_t> snp_planes;          // SNP pile-up: 6 count planes over the concatenated target
+};
 }  // namespace bk
 
 struct bk_ctx {
@@ -59,22 +83,12 @@ struct bk_ctx {
     bk_align_params params{};
     bk::DevAlignCfg cfg{};
     bk::DevIndex ix{};
-    // owned device allocations of the index image
-    uint64_t *d_tgt4 = nullptr;
-    uint32_t *d_sa_lo = nullptr;
-    uint8_t *d_sa_hi = nullptr;
-    uint64_t *d_ent_start = nullptr, *d_ent_end = nullptr;
-    uint32_t *d_ent_id = nullptr, *d_id2idx = nullptr;
-    void *d_ktab = nullptr;
-    size_t ktab_bytes = 0, nflag_bytes = 0;
-    uint64_t *d_tgt2 = nullptr;           // 2 bit/base target copy (DevIndex::tgt2)
-    uint64_t *d_tgt2s = nullptr;          // the same, stored 32 bytes later (DevIndex::tgt2s)
-    uint8_t *d_nflag = nullptr;
+    bk::ImageBufs image;                  // owned device allocations of the index image
+    bk::FixedBufs fixed;                  // .. and the small fixed buffers
+    void release_image_buffers() { image = bk::ImageBufs{}; fixed = bk::FixedBufs{}; }
     uint64_t n_tgt4_words = 0;
     uint32_t cap_rd2w = 0;
     int use_tgt2 = 2;        // 0: 4-bit windows only, 1: 2-bit copy, 2: 2-bit copy stored twice (32 bytes apart)
-    uint32_t *d_k2 = nullptr;             // second-level search keys (DevIndex::k2)
-    uint32_t *d_kx[bk::kMoreKeys] = {nullptr, nullptr};   // third-, fourth-level search keys (DevIndex::kx)
     int sort_lists = 7;      // bit 0: search work list grouped by index position; bit 1: wave list sorted, by index position or (bit 2) longest read first
     bool sort_lists_set = false;   // .. as the caller's knob left it; else bit 0 follows the index: off where it has third-level keys (tables_end)
     int sort_shift = 0;      // keys = suffix array index >> sort_shift (fits 32 bits)
@@ -86,8 +100,6 @@ struct bk_ctx {
     uint64_t grow_after = 5 * BK_POLICY_MIN_READS, grow_seen = 0;      // (a context that was started lean for a short job and turned out to run a long one)
     std::atomic<int> grow_state{0};          // 0 not started, 1 being made, 2 made, 3 nothing made (no room / not in order), 4 taken in
     std::thread grow_thread;
-    uint32_t *grow_kx[bk::kMoreKeys] = {nullptr, nullptr};
-    void *grow_ktab2 = nullptr;
     bk::DevIndex grow_ix{};                  // the index as it was when the worker started (its own copy: the batches' thread goes on changing ix - the window array)
     bool grow_want_ktab2 = false;
     bool grow_elem = false, grow_want_elem = false;        // the worker's k-mer table of pairs carries suffix array elements for buckets of one suffix ("use_ktab2" 2)
@@ -96,9 +108,6 @@ struct bk_ctx {
     int use_iv32 = 1;        // phase 0 leaves the interval of a read's first k + 16 bases for the offset-0 cores of the later phases
     uint32_t wave_waves = 256u * 8u * 4u;   // resident waves the wave kernel is launched with
     int use_isa = 1;         // 0: no inverse suffix array - the wave kernel dedupes with its hash set (as it does for 5-byte indexes)
-    uint32_t *d_isa = nullptr;
-    void *d_swin = nullptr;               // suffix-ordered window array (DevIndex::swin), built when the first batch it serves arrives
-    uint32_t *d_swmap = nullptr;          // .. and which blocks of the suffix array it holds (DevIndex::swmap; null: all of them)
     int use_swin = 1;         // 0: none; 1: the part of the suffix array the wave kernel's long walks visit; 2: the same, whatever the batch's read lengths; 3: every suffix
     uint64_t swin_budget = 0; // most bytes the partial array may take (0: by the free memory)
     int swin_skip_short = 0;  // the coverage rule leaves out this many of the reads' shortest core lengths
@@ -113,26 +122,21 @@ struct bk_ctx {
     int lazy_search = 1;     // 1: small k-mer buckets are handed to the extend kernels unverified
     bool ktab64 = false;
     int ktab_wide = 0;                    // "ktab_wide": 0 bucket starts of 64 bits only where the index needs them; 1 always, packed as ktab_hi + offsets; 2 always, unpacked (tests)
-    uint64_t *d_ktab_hi = nullptr;        // .. stored as 32-bit offsets from a 64-bit start per 2^16 codes (DevIndex::ktab_hi) when every such group spans less than 2^32 suffixes
     int k_req = -1;          // requested k (-1 auto)
     int use_ktab = 1;
     uint32_t el_size = 4;
     uint64_t tot_seq_len = 0;
     std::string dataset;
     std::vector<bk_entry_info> entries;
-    // SNP pile-up: 6 count planes over the concatenated target, site list of the last bk_snp_sites call (device side: buf.snp_sites)
-    uint32_t *d_snp_planes = nullptr;
-    unsigned long long *d_snp_tot = nullptr;
+    // SNP pile-up (count planes: fixed.snp_planes): site list of the last bk_snp_sites call (device side: buf.snp_sites)
     std::vector<bk_snp_site> snp_sites;
 
     bk::BatchBufs buf;                    // every device buffer that is grown on demand
     void release_batch_buffers() { buf = bk::BatchBufs{}; }
     // what the batch scratch was sized for (scratch_bytes_per_read, maybe_build_swin)
     uint32_t cap_reads = 0, cap_wpr = 0, cap_iv_cores = 0;
-    uint32_t *d_small = nullptr;          // [0] act_cnt [1] next_cnt [2] heavy_cnt [3] cmax [4] cursor [5] maxlen [6] wave_cnt [7] wave cursor
-    uint32_t *h_small = nullptr;          // pinned mirror (two PhaseCtl lines when the phase loop reads its counts back)
-    bk::PhaseCtl *d_ctl = nullptr;        // kMaxPhases + 2 lines: the counts of a chunk's phases (bk_device.h)
-    bk::PhaseCtl *h_ctl = nullptr;        // pinned: the last chunk's counts, copied behind its kernels
+    uint32_t *h_small = nullptr;          // pinned mirror of fixed.small (two PhaseCtl lines when the phase loop reads its counts back)
+    bk::PhaseCtl *h_ctl = nullptr;        // pinned: the last chunk's counts (fixed.ctl), copied behind its kernels
     hipEvent_t ev_ctl = nullptr;
     bool ctl_pending = false, hist_valid = false;
     uint32_t ctl_pending_reads = 0, ctl_pending_maxlen = 0;
@@ -140,9 +144,7 @@ struct bk_ctx {
     double hist_slist[bk::kMaxPhases] = {0}, hist_wave[bk::kMaxPhases] = {0};      // per phase: pass B items / wave-kernel reads per read of the chunk
     int async_error = 0;     // what take_phase_history found wrong with a batch of bk_align_batch_device_async (reported by the next call)
     int async_phases = 1;    // 1: the main path's phase loop launches without reading counts back (see align_chunk)
-    unsigned long long *d_seq_counts = nullptr, *d_ctr = nullptr, *d_ctr_aux = nullptr;
-    unsigned long long *d_seq_global = nullptr;   // bk_seq_counts_allreduce: the counts summed over every context of the run
-    bool force_rccl = false;                      // .. through RCCL even on one device ("force_rccl")
+    bool force_rccl = false;                      // bk_seq_counts_allreduce goes through RCCL even on one device ("force_rccl")
     uint64_t rccl_allreduces = 0;                 // .. how many of this context's reductions went through RCCL, the ranks of the last one's communicator
     int rccl_ranks = 0;
     // heavy path scratch (owned by buf.htab, buf.slot_epoch)
@@ -159,6 +161,7 @@ struct bk_ctx {
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)
     bool tables_built = false;            // k-mer table, second-level keys, inverse suffix array exist (made behind the suffix array's upload)
+    bool tables_under_way = false;        // .. are being made (tables_begin .. tables_end): publish_index leaves their pointers null
     void *sam_text[2] = {nullptr, nullptr};   // bk_sam_format's page-locked text buffers, kept for the next call (giving page-locked memory back costs 0.1 s per GB)
     uint64_t sam_text_cap = 0;
     uint32_t n_chrom_accept = 0;          // entries of buf.chrom_accept (bk_ctx_set_chrom_filter)

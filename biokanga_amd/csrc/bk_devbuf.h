@@ -1,7 +1,9 @@
-// bk_devbuf.h - bk::DevBuf<T>: the owner of one device buffer that is grown on demand (the context's batch-side buffers in bk_ctx_int.h,
-// the temporaries of the entry points).  A pointer and a capacity in elements; frees in its destructor.  Growing frees first and then
-// allocates exactly what was asked for - no copy, no growth factor: free-before-allocate is what keeps the peak inside the HBM budget of
-// DESIGN.md section 3.  All memory goes through bk::dev_malloc_bytes / bk::free_dev (bk_image.cpp: BK_POISON, BK_TIMING).
+// bk_devbuf.h - bk::DevBuf<T>: the owner of one device buffer (bk_ctx_int.h: the index image, the small fixed buffers and the batch-side
+// buffers of a context; the temporaries of bk_image.cpp and of the entry points).  A pointer and a capacity in elements - the capacity IS
+// the buffer's size: an image table is made by ensure() on an empty buffer, cloned by its cap(), handed on by move.  Frees in its
+// destructor; a move-assignment frees what the target held on the spot.  Growing frees first and then allocates exactly what was asked
+// for - no copy, no growth factor: free-before-allocate is what keeps the peak inside the HBM budget of DESIGN.md section 3.  All memory
+// goes through bk::dev_malloc_bytes / bk::free_dev (bk_image.cpp: BK_POISON, BK_TIMING).
 #pragma once
 #include <cstddef>
 #include <utility>

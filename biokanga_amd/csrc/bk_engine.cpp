@@ -48,7 +48,7 @@ int ensure_batch_scratch(bk_ctx *c, uint32_t n_reads, uint32_t wpr, uint32_t rd2
     HIP_TRY(m.rd4.ensure(nr * 2 * w));
     if (w2) HIP_TRY(m.rd2.ensure(nr * 2 * w2 + 8));        // (+ the words a 32-base fetch at a row's end runs into)
     HIP_TRY(m.rmeta.ensure((nr + 2) / 2 * 2));
-    if (c->d_sa_hi == nullptr && c->ix.n < (1ULL << 32))
+    if (c->image.sa_hi.get() == nullptr && c->ix.n < (1ULL << 32))
         HIP_TRY(m.iv2.ensure(nr * 2 * ivc));
     else {
         HIP_TRY(m.iv_first.ensure(nr * 2 * ivc));
@@ -142,7 +142,7 @@ static DevBatch make_batch(bk_ctx *c, const DevReads &in, uint32_t first, uint32
     b.pk_words = in.words; b.pk_exc = in.exc; b.pk_nexc = in.words ? in.n_exc : 0; b.pk_read0 = first;
     b.rd4 = m.rd4.get(); b.iv_first = m.iv_first.get(); b.iv_n = m.iv_n.get(); b.iv2 = m.iv2.get();
     b.rmeta = m.rmeta.get();
-    b.out = d_out; b.seq_counts = c->d_seq_counts; b.ctr = c->d_ctr;
+    b.out = d_out; b.seq_counts = c->fixed.seq_counts.get(); b.ctr = c->fixed.ctr.get();
     b.wpr = wpr; b.n_reads = n; b.iv_cores = iv_cores;
     return b;
 }
@@ -276,7 +276,7 @@ int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipS
     if (rc) return rc;
     uint32_t n_multi = 0;
     if (lc.total) {
-        uint32_t *sm = c->d_small;
+        uint32_t *sm = c->fixed.small.get();
         if (d_seg2) {
             HIP_TRY(lc.trims.ensure((size_t)lc.total));
             HIP_TRY(clear_dev(lc.trims.get(), (size_t)lc.total * sizeof(bk_loci_trims), s));
@@ -317,7 +317,7 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
     HIP_TRY(dense.ensure((size_t)n * width));
     rc = size_heavy_scratch(c);
     if (rc) return rc;
-    uint32_t *sm = c->d_small;
+    uint32_t *sm = c->fixed.small.get();
     HIP_TRY(hipMemsetAsync(sm + 4, 0, 4, s));
     launch_best(c->ix, c->cfg, b, c->hs, d_list, n_list, sm + 4, lc.cnt.get(), dense.get(), s);
     HIP_TRY(hipGetLastError());
@@ -332,7 +332,7 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
 
 int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
 {
-    uint32_t *sm = c->d_small, *hm = c->h_small;
+    uint32_t *sm = c->fixed.small.get(), *hm = c->h_small;
     HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
     const uint32_t wpr = words_per_read(maxlen);
     // register-resident window kernels handle reads of <= 128 / <= 256 / <= 16 * kNwLong / <= 16 * kNwLongest bases
@@ -341,7 +341,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     const bool two_bit = reg_path && c->ix.tgt2 != nullptr;
     const uint32_t ivc = iv_cores_for(c, maxlen);
     int rc = ensure_batch_scratch(c, n, wpr, two_bit ? (uint32_t)(nw16 / 2) : 0u, ivc);
-    if (rc && c->d_swin) {                        // the window array is a luxury: it goes before a batch is refused for want of memory
+    if (rc && c->image.swin.get()) {                        // the window array is a luxury: it goes before a batch is refused for want of memory
         (void)hipGetLastError();
         bk::release_swin(c);
         rc = ensure_batch_scratch(c, n, wpr, two_bit ? (uint32_t)(nw16 / 2) : 0u, ivc);
@@ -367,7 +367,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     // are sized from what the previous chunk needed (items beyond that run unsorted: order never changes a result).  The other
     // configurations (general kernel family, lane-per-read kernels, no key array, -N, BK_DEBUG) keep reading the counts back, which
     // sizes their launches exactly.
-    PhaseCtl *ctl = c->d_ctl;
+    PhaseCtl *ctl = c->fixed.ctl.get();
     HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PhaseCtl) * (kMaxPhases + 2), s));
     auto P = [&](int ph) { return reinterpret_cast<uint32_t *>(ctl + ph); };      // words of ctl[ph]: [0] n_act [1] cmax [2] n_slist [3] n_wave [4] n_heavy [5] wave cursor [6] heavy cursor
     // bounds of a read of up to maxlen bases: phases, cores per strand in each
@@ -597,7 +597,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         tm.end(Span::Heavy, ei, s);
     }
     hipEvent_t e4 = tm.begin(s);
-    launch_count_seqs(d_out, n, c->d_id2idx, c->ix.n_ent, c->d_seq_counts, s);
+    launch_count_seqs(d_out, n, c->image.id2idx.get(), c->ix.n_ent, c->fixed.seq_counts.get(), s);
     HIP_TRY(hipGetLastError());
     tm.end(Span::Other, e4, s);
     if (c->cfg.max_hits > 1 && !c->params.best_matches) {
@@ -663,9 +663,9 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     // longest read of the call -> row width of the packed reads and the kernel family used (the pipeline knows it already)
     uint32_t maxlen = maxlen_known;
     if (!maxlen) {
-        HIP_TRY(hipMemsetAsync(c->d_small, 0, 16 * 4, s));
-        launch_max_len(d_lens, nreads, c->d_small + 5, s);
-        HIP_TRY(hipMemcpyAsync(c->h_small, c->d_small, 16 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
+        launch_max_len(d_lens, nreads, c->fixed.small.get() + 5, s);
+        HIP_TRY(hipMemcpyAsync(c->h_small, c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         maxlen = c->h_small[5];
     }
@@ -756,12 +756,12 @@ int bk::engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nrea
     size_t tb = c->buf.scan_tmp.cap();
     HIP_TRY(bk::prim::exclusive_sum(c->buf.scan_tmp.get(), tb, (unsigned long long *)d_offs, (unsigned long long *)d_offs, (size_t)nreads, s));
     // [0] max over reads of (first word + words) = the batch's word count, [1] longest read; exceptions in range and ascending
-    HIP_TRY(hipMemsetAsync(c->d_ctr_aux, 0, 32, s));
-    launch_packed_extent(d_offs, d_lens32, nreads, c->d_ctr_aux, s);
-    launch_check_exc(d_exc, n_exc, d_lens32, nreads, reinterpret_cast<uint32_t *>(c->d_ctr_aux + 2), s);
+    HIP_TRY(hipMemsetAsync(c->fixed.ctr_aux.get(), 0, 32, s));
+    launch_packed_extent(d_offs, d_lens32, nreads, c->fixed.ctr_aux.get(), s);
+    launch_check_exc(d_exc, n_exc, d_lens32, nreads, reinterpret_cast<uint32_t *>(c->fixed.ctr_aux.get() + 2), s);
     HIP_TRY(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, c->d_ctr_aux, 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h, c->fixed.ctr_aux.get(), 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (h[0] != n_words || h[1] > (unsigned long long)kMaxReadLenAbs || (uint32_t)h[2] != 0) return BK_ERR_PARAMS;
     *maxlen = (uint32_t)h[1];
@@ -780,7 +780,7 @@ int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_h
     // (launch_pe never touches the interval records: the slots keep whatever core count the SE pass sized them for)
     const uint32_t ivc = c->cap_iv_cores ? c->cap_iv_cores : iv_cores_for(c, maxlen);
     int rc = ensure_batch_scratch(c, nreads, wpr, 0, ivc);
-    if (rc && c->d_swin) {                        // the window array goes before a batch is refused for want of memory (as in align_chunk)
+    if (rc && c->image.swin.get()) {                        // the window array goes before a batch is refused for want of memory (as in align_chunk)
         (void)hipGetLastError();
         bk::release_swin(c);
         rc = ensure_batch_scratch(c, nreads, wpr, 0, ivc);
@@ -795,9 +795,9 @@ int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_h
         d_seg2 = c->buf.seg2.get();
         HIP_TRY(hipMemcpyAsync(d_seg2, seg2_host, (size_t)nreads * sizeof(bk_seg2), hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipMemsetAsync(c->d_small, 0, 16 * 4, s));
+    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
     launch_pe(c->ix, c->cfg, b, pe->pe_mode, pe->pair_min_len, pe->pair_max_len, pe->pair_strand ? 1 : 0, d_hits, n_pairs,
-              c->buf.heavy.get(), c->d_small, c->h_small, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
+              c->buf.heavy.get(), c->fixed.small.get(), c->h_small, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
     HIP_TRY(hipGetLastError());
     if (seg2_host && !seg2_dev) HIP_TRY(hipMemcpyAsync(seg2_host, d_seg2, (size_t)nreads * sizeof(bk_seg2), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1086,9 +1086,9 @@ int bk_pair_batch_seg2_device(bk_ctx *c, const void *d_bases, const void *d_offs
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t nreads = 2 * n_pairs;
     hipStream_t s = c->stream;
-    HIP_TRY(hipMemsetAsync(c->d_small, 0, 16 * 4, s));
-    launch_max_len((const uint32_t *)d_lens, nreads, c->d_small + 5, s);
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->d_small, 16 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
+    launch_max_len((const uint32_t *)d_lens, nreads, c->fixed.small.get() + 5, s);
+    HIP_TRY(hipMemcpyAsync(c->h_small, c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint32_t maxlen = c->h_small[5];
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
@@ -1107,7 +1107,7 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
     PhaseCtl ctl{};
-    HIP_TRY(hipMemcpy(&ctl, c->d_ctl + c->dbg_phase, sizeof(PhaseCtl), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&ctl, c->fixed.ctl.get() + c->dbg_phase, sizeof(PhaseCtl), hipMemcpyDeviceToHost));
     *n_act = ctl.n_act;
     *iv_cores = c->dbg_ivc;
     if (!act && !first && !count) return BK_OK;
@@ -1150,11 +1150,11 @@ int bk_get_counters(bk_ctx *c, bk_counters *out, int reset)
     if (!c || !out) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long hs[kCtrStripes * 8], h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(hs, c->d_ctr, sizeof(hs), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs, c->fixed.ctr.get(), sizeof(hs), hipMemcpyDeviceToHost));
     for (int i = 0; i < kCtrStripes * 8; i++) h[i & 7] += hs[i];
     memset(out, 0, sizeof(*out));
     out->n_search = h[0]; out->n_cand = h[1]; out->n_lcm_calls = h[2]; out->n_heavy = h[3]; out->n_cand_heavy = h[4]; out->reserved[0] = h[5]; out->reserved[1] = h[6];
-    if (reset) HIP_TRY(dev_zero_now(c->d_ctr, sizeof(hs)));
+    if (reset) HIP_TRY(dev_zero_now(c->fixed.ctr.get(), sizeof(hs)));
     return BK_OK;
 }
 

@@ -149,15 +149,13 @@ inline uint64_t scratch_bytes_per_read(uint32_t wpr, uint32_t rd2w = 8, uint32_t
 
 // ---- bk_image.cpp: parameters -> DevAlignCfg, the tables of the index image, the window array, contexts
 int derive_cfg(bk_ctx *c);
-void free_dev(void *p);
 hipError_t clear_dev(void *p, size_t bytes, hipStream_t s);
 struct TablePlan {
     bool ktab = false, k2 = false, isa = false;
     bool ktab2 = false;                            // the k-mer table's entries are pairs {bucket start, y} from the start (DevIndex::ktab2): starts written in place, y filled in tables_end
     int kx = 0;                                    // key arrays behind the second-level keys (DevIndex::kx)
     int k = 0;
-    unsigned long long *d_bad = nullptr;           // places where the second-level keys are not in order inside a bucket; the third-level keys inside a run of equal second-level keys
-    ~TablePlan() { free_dev(d_bad); }
+    DevBuf<unsigned long long> d_bad;              // places where the second-level keys are not in order inside a bucket; the third-level keys inside a run of equal second-level keys
 };
 
 int tables_begin(bk_ctx *c, TablePlan &tp);
@@ -165,6 +163,7 @@ int tables_range(bk_ctx *c, const TablePlan &tp, uint64_t i0, uint64_t i1, unsig
 int tables_end(bk_ctx *c, TablePlan &tp);
 int build_tables(bk_ctx *c);
 int build_tgt2(bk_ctx *c);
+void publish_index(bk_ctx *c);      // every pointer of c->ix from the owners in c->image
 void grow_take_in(bk_ctx *c);
 void grow_drop(bk_ctx *c);
 void grow_tick(bk_ctx *c, uint64_t nreads, bool now = false);

@@ -11,8 +11,8 @@ int bk_seq_counts(bk_ctx *c, uint64_t *per_entry_hits, uint32_t n, int reset)
 {
     if (!c || !per_entry_hits || n != c->entries.size()) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy(per_entry_hits, c->d_seq_counts, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(dev_zero_now(c->d_seq_counts, (size_t)n * 8));
+    HIP_TRY(hipMemcpy(per_entry_hits, c->fixed.seq_counts.get(), (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(dev_zero_now(c->fixed.seq_counts.get(), (size_t)n * 8));
     return BK_OK;
 }
 
@@ -67,15 +67,15 @@ int bk_seq_counts_allreduce(bk_ctx *const *ctxs, int n, uint64_t *out, uint32_t 
     for (int i = 0; i < n; i++) {
         bk_ctx *c = ctxs[i];
         HIP_TRY(hipSetDevice(c->device));
-        if (!c->d_seq_global) HIP_TRY(dev_malloc(&c->d_seq_global, bytes ? bytes : 8));
+        if (!c->fixed.seq_global.get()) HIP_TRY(c->fixed.seq_global.ensure(n_entries ? n_entries : 1));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     for (int i = 0; i < n; i++) {
         bk_ctx *c = ctxs[i], *L = ctxs[leader_of[i]];
         HIP_TRY(hipSetDevice(c->device));
-        if (c == L) HIP_TRY(hipMemcpyAsync(L->d_seq_global, c->d_seq_counts, bytes, hipMemcpyDeviceToDevice, L->stream));
+        if (c == L) HIP_TRY(hipMemcpyAsync(L->fixed.seq_global.get(), c->fixed.seq_counts.get(), bytes, hipMemcpyDeviceToDevice, L->stream));
         else {
-            hipLaunchKernelGGL(k_add_u64, dim3((n_entries + 255) / 256), dim3(256), 0, L->stream, L->d_seq_global, c->d_seq_counts, n_entries);
+            hipLaunchKernelGGL(k_add_u64, dim3((n_entries + 255) / 256), dim3(256), 0, L->stream, L->fixed.seq_global.get(), c->fixed.seq_counts.get(), n_entries);
             HIP_TRY(hipGetLastError());
         }
     }
@@ -105,7 +105,7 @@ int bk_seq_counts_allreduce(bk_ctx *const *ctxs, int n, uint64_t *out, uint32_t 
         for (size_t k = 0; k < leaders.size() && r == ncclSuccess; k++) {
             bk_ctx *L = ctxs[leaders[k]];
             (void)hipSetDevice(L->device);
-            r = rccl.AllReduce(L->d_seq_global, L->d_seq_global, n_entries, ncclUint64, ncclSum, comms[k], L->stream);
+            r = rccl.AllReduce(L->fixed.seq_global.get(), L->fixed.seq_global.get(), n_entries, ncclUint64, ncclSum, comms[k], L->stream);
         }
         ncclResult_t r2 = rccl.GroupEnd();
         for (int j : leaders) { (void)hipSetDevice(ctxs[j]->device); (void)hipStreamSynchronize(ctxs[j]->stream); }
@@ -116,12 +116,12 @@ int bk_seq_counts_allreduce(bk_ctx *const *ctxs, int n, uint64_t *out, uint32_t 
         bk_ctx *c = ctxs[i], *L = ctxs[leader_of[i]];
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(L->stream));
-        if (c != L) HIP_TRY(hipMemcpy(c->d_seq_global, L->d_seq_global, bytes, hipMemcpyDeviceToDevice));
-        if (reset) HIP_TRY(dev_zero_now(c->d_seq_counts, bytes));
+        if (c != L) HIP_TRY(hipMemcpy(c->fixed.seq_global.get(), L->fixed.seq_global.get(), bytes, hipMemcpyDeviceToDevice));
+        if (reset) HIP_TRY(dev_zero_now(c->fixed.seq_counts.get(), bytes));
     }
     if (out) {
         HIP_TRY(hipSetDevice(ctxs[0]->device));
-        HIP_TRY(hipMemcpy(out, ctxs[0]->d_seq_global, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, ctxs[0]->fixed.seq_global.get(), bytes, hipMemcpyDeviceToHost));
     }
     return BK_OK;
 }

@@ -5,6 +5,9 @@
 // (Aligner.cpp:341-356,8725-8761).  Compiled with hipcc; the kernels are in bk_index.hip.
 #include "bk_engine_int.h"
 
+// HIP_TRY's quiet sibling for the window array's builders (their callers take a failure for "no array"): prints nothing, clears the sticky error
+#define SW_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (void)hipGetLastError(); return e_ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL; } } while (0)
+
 namespace bk {
 // hipMemset that has happened when it returns: a memset only joins the null stream's queue, and the pipelines' streams (non-blocking) do
 // not wait for that queue - a kernel launched on one of them right after could meet the old bytes, or have its own writes zeroed later
@@ -128,6 +131,29 @@ int pick_k(uint64_t n)
 // made range by range: behind the suffix array's upload (bk_ctx_create_ex sends it in slices and these kernels work on a slice while the
 // next crosses PCIe), or in one go.  tables_begin decides and allocates, tables_range enqueues, tables_end checks and publishes.
 
+// Every pointer of the DevIndex the kernels see, from the owners in bk_ctx::image - the one place that knows which view of the k-mer table is
+// live.  Called wherever an owner has been filled, replaced or emptied (the scalars of DevIndex are set where they are computed).
+void publish_index(bk_ctx *c)
+{
+    const ImageBufs &im = c->image;
+    DevIndex &ix = c->ix;
+    ix.tgt4 = im.tgt4.get(); ix.sa_lo = im.sa_lo.get(); ix.sa_hi = im.sa_hi.get();
+    ix.ent_start = im.ent_start.get(); ix.ent_end = im.ent_end.get(); ix.ent_id = im.ent_id.get(); ix.id2idx = im.id2idx.get();
+    const bool tabs = !c->tables_under_way;          // (between tables_begin and tables_end the tables read as absent)
+    const void *kt = tabs ? im.ktab.get() : nullptr;
+    const bool packed = c->ktab64 && im.ktab_hi.get() != nullptr, pairs = !c->ktab64 && c->ktab_is2;
+    ix.ktab64 = c->ktab64 && !packed ? static_cast<const uint64_t *>(kt) : nullptr;
+    ix.ktab_hi = packed ? im.ktab_hi.get() : nullptr;
+    ix.ktab2 = pairs ? static_cast<const uint2 *>(kt) : nullptr;
+    ix.ktab32 = packed || (!c->ktab64 && !pairs) ? static_cast<const uint32_t *>(kt) : nullptr;
+    ix.k2 = tabs ? im.k2.get() : nullptr;
+    for (int i = 0; i < kMoreKeys; i++) ix.kx[i] = tabs ? im.kx[i].get() : nullptr;
+    // a bucket of one suffix carries its suffix array element: asked for, 4-byte elements, and keys (no keys, no two-pass search: nothing hands elements on)
+    ix.ktab2_elem = (ix.ktab2 != nullptr && c->use_ktab2 >= 2 && im.sa_hi.get() == nullptr && ix.k2 != nullptr) ? 1 : 0;
+    ix.isa = tabs ? im.isa.get() : nullptr; ix.tgt2 = im.tgt2.get(); ix.tgt2s = im.tgt2s.get(); ix.nflag = im.nflag.get();
+    ix.swin = reinterpret_cast<const uint4 *>(im.swin.get()); ix.swmap = im.swmap.get();
+}
+
 // ------------------------------------------------------------------------------------------------
 // BK_CTX_GROW_IMAGE: a context starts with the image a short job wants and grows the tables that pay over thousands of millions of reads
 // - the key arrays behind the second-level keys, the k-mer table entries that carry their bucket's first key - while it works: a thread
@@ -138,50 +164,50 @@ void grow_worker(bk_ctx *c)
 {
     int st = 3;
     hipStream_t s = nullptr;
-    unsigned long long *d_bad = nullptr;
+    DevBuf<unsigned long long> d_bad;
+    ImageBufs &im = c->image;                        // (grow_kx, grow_ktab2: this thread's until grow_state says otherwise)
     do {
         if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
         const DevIndex &ix = c->grow_ix;             // (set by the thread that started this one, before it did)
         const uint64_t n = ix.n;
-        const uint64_t need = k2s_start(n, kK2Levels + 1) * 4;
+        const uint64_t n_keys = k2s_start(n, kK2Levels + 1), need = n_keys * 4;
         int nk = 0;
         if (ix.k2 != nullptr && ix.kx[0] == nullptr) {
             for (int i = 0; i < kMoreKeys; i++) {
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b || free_b - need < total_b / 5) break;
-                if (dev_malloc(&c->grow_kx[i], need) != hipSuccess) { (void)hipGetLastError(); c->grow_kx[i] = nullptr; break; }
+                if (im.grow_kx[i].ensure(n_keys) != hipSuccess) { (void)hipGetLastError(); break; }
                 nk = i + 1;
             }
         }
         if (nk) {
             unsigned long long bad2[2] = {0, 0};
-            bool ok = dev_malloc(&d_bad, 16) == hipSuccess && hipMemsetAsync(d_bad, 0, 16, s) == hipSuccess;
+            bool ok = d_bad.ensure(2) == hipSuccess && hipMemsetAsync(d_bad.get(), 0, 16, s) == hipSuccess;
             if (ok) {
-                launch_build_k2(ix, const_cast<uint32_t *>(ix.k2), c->grow_kx[0], nk > 1 ? c->grow_kx[1] : nullptr, d_bad, s, 0, n, false);
-                ok = hipMemcpyAsync(bad2, d_bad, 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && !bad2[0] && !bad2[1];
+                launch_build_k2(ix, const_cast<uint32_t *>(ix.k2), im.grow_kx[0].get(), nk > 1 ? im.grow_kx[1].get() : nullptr, d_bad.get(), s, 0, n, false);
+                ok = hipMemcpyAsync(bad2, d_bad.get(), 16, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess && !bad2[0] && !bad2[1];
             }
             if (ok) {
-                for (int i = 0; i < nk; i++) launch_build_k2_levels(c->grow_kx[i], n, s);
+                for (int i = 0; i < nk; i++) launch_build_k2_levels(im.grow_kx[i].get(), n, s);
                 ok = hipStreamSynchronize(s) == hipSuccess;
             }
             if (!ok) {
                 (void)hipGetLastError();
-                for (int i = 0; i < kMoreKeys; i++) { free_dev(c->grow_kx[i]); c->grow_kx[i] = nullptr; }
+                for (auto &b : im.grow_kx) b.reset();
                 nk = 0;
             }
         }
         if (c->grow_want_ktab2 && ix.k2 != nullptr && ix.ktab32 != nullptr) {
             const uint64_t n_entries = (1ULL << (2 * ix.k)) + 1;
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && n_entries * 8 + (total_b / 5) < free_b && dev_malloc(&c->grow_ktab2, n_entries * 8) == hipSuccess) {
-                launch_make_ktab2(ix.ktab32, ix.k2, n_entries, n, c->grow_ktab2, s, c->grow_want_elem ? ix.sa_lo : nullptr);
-                if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); free_dev(c->grow_ktab2); c->grow_ktab2 = nullptr; }
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && n_entries * 8 + (total_b / 5) < free_b && im.grow_ktab2.ensure(n_entries * 8) == hipSuccess) {
+                launch_make_ktab2(ix.ktab32, ix.k2, n_entries, n, im.grow_ktab2.get(), s, c->grow_want_elem ? ix.sa_lo : nullptr);
+                if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); im.grow_ktab2.reset(); }
             } else
                 (void)hipGetLastError();
         }
-        st = (nk || c->grow_ktab2) ? 2 : 3;
+        st = (nk || im.grow_ktab2.get()) ? 2 : 3;
     } while (false);
-    free_dev(d_bad);
     if (s) (void)hipStreamDestroy(s);
     c->grow_state.store(st, std::memory_order_release);
 }
@@ -189,25 +215,21 @@ void grow_worker(bk_ctx *c)
 // the worker's tables become the context's (between two batches; the device is made idle before the k-mer table it replaces is given back)
 void grow_take_in(bk_ctx *c)
 {
-    if (c->grow_thread.joinable()) c->grow_thread.join();
+    if (c->grow_thread.joinable()) c->grow_thread.join();          // (the worker's buffers are read only behind this join)
     if (c->grow_state.load(std::memory_order_acquire) == 2) {
+        ImageBufs &im = c->image;
         for (int i = 0; i < kMoreKeys; i++)
-            if (c->grow_kx[i]) { c->d_kx[i] = c->grow_kx[i]; c->ix.kx[i] = c->grow_kx[i]; c->grow_kx[i] = nullptr; }
-        if (c->ix.kx[0]) c->use_k3 = kMoreKeys;
-        if (c->grow_ktab2) {
+            if (im.grow_kx[i].get()) im.kx[i] = std::move(im.grow_kx[i]);
+        if (im.kx[0].get()) c->use_k3 = kMoreKeys;
+        if (im.grow_ktab2.get()) {
             // (earlier batches may still run on a caller's stream - bk_stream's, bk_align_batch_device_async's - with the old table's
-            // address in their kernel arguments: the whole device is waited for, not the context's own stream)
+            // address in their kernel arguments: the whole device is waited for, not the context's own stream - BEFORE the move frees that table)
             (void)hipDeviceSynchronize();
-            free_dev(c->d_ktab);
-            c->d_ktab = c->grow_ktab2;
-            c->grow_ktab2 = nullptr;
-            c->ktab_bytes = (size_t)((1ULL << (2 * c->ix.k)) + 1) * 8;
+            im.ktab = std::move(im.grow_ktab2);
             c->ktab_is2 = true;
             c->use_ktab2 = c->grow_want_elem ? 2 : 1;
-            c->ix.ktab2_elem = c->grow_want_elem ? 1 : 0;
-            c->ix.ktab32 = nullptr;
-            c->ix.ktab2 = reinterpret_cast<const uint2 *>(c->d_ktab);
         }
+        publish_index(c);
         if (!c->sort_lists_set) c->sort_lists = (c->sort_lists & ~1) | (c->ix.kx[0] == nullptr ? 1 : 0);
         if (env::timing())
             fprintf(stderr, "biokanga_amd: long-run tables taken in after %llu reads: %d key array(s) behind the second-level keys%s\n",
@@ -220,9 +242,8 @@ void grow_take_in(bk_ctx *c)
 void grow_drop(bk_ctx *c)
 {
     if (c->grow_thread.joinable()) c->grow_thread.join();
-    for (int i = 0; i < kMoreKeys; i++) { free_dev(c->grow_kx[i]); c->grow_kx[i] = nullptr; }
-    free_dev(c->grow_ktab2);
-    c->grow_ktab2 = nullptr;
+    for (auto &b : c->image.grow_kx) b.reset();
+    c->image.grow_ktab2.reset();
     if (c->grow_state.load() != 0) c->grow_state.store(4);
 }
 
@@ -237,7 +258,7 @@ void grow_tick(bk_ctx *c, uint64_t nreads, bool now)
         if ((now || c->grow_seen >= c->grow_after) && c->tables_built && c->ix.k2 != nullptr) {
             c->grow_ix = c->ix;
             c->grow_want_ktab2 = !c->ktab64 && !c->ktab_is2;
-            c->grow_want_elem = c->grow_elem && c->d_sa_hi == nullptr;
+            c->grow_want_elem = c->grow_elem && c->image.sa_hi.get() == nullptr;
             c->grow_state.store(1);
             c->grow_thread = std::thread(grow_worker, c);
         }
@@ -247,14 +268,15 @@ void grow_tick(bk_ctx *c, uint64_t nreads, bool now)
 
 int tables_begin(bk_ctx *c, TablePlan &tp)
 {
+    // Order: the worker's tables and every old table go before the first new allocation below; the table pointers read null while the build is under way
+    ImageBufs &im = c->image;
     grow_drop(c);
-    free_dev(c->d_ktab); free_dev(c->d_ktab_hi); free_dev(c->d_k2); free_dev(c->d_isa);
-    c->d_ktab = nullptr; c->d_ktab_hi = nullptr; c->d_k2 = nullptr; c->d_isa = nullptr;
-    for (int i = 0; i < kMoreKeys; i++) { free_dev(c->d_kx[i]); c->d_kx[i] = nullptr; c->ix.kx[i] = nullptr; }
-    c->ix.ktab32 = nullptr; c->ix.ktab64 = nullptr; c->ix.ktab_hi = nullptr; c->ix.ktab2 = nullptr; c->ix.k2 = nullptr; c->ix.isa = nullptr;
+    im.ktab.reset(); im.ktab_hi.reset(); im.k2.reset(); im.isa.reset();
+    for (auto &b : im.kx) b.reset();
     c->ktab_is2 = false;
-    c->ix.ktab2_elem = 0;
     c->ix.k = 0;
+    c->tables_under_way = true;
+    publish_index(c);
     // What the HBM has room for is decided before anything is allocated, in the order of what a byte buys: k-mer table, second-level
     // keys, inverse suffix array, the key arrays behind the second-level keys, then the k-mer table's second words - each only where a
     // fifth of the HBM stays free behind it (batch scratch, window array).  Nothing is given back or allocated again afterwards: an
@@ -267,7 +289,7 @@ int tables_begin(bk_ctx *c, TablePlan &tp)
         c->ktab64 = c->ix.n >= (1ULL << 32) || c->ktab_wide != 0;
         const uint64_t ktab_bytes = (ncodes + 1) * (c->ktab64 ? 8 : 4);
         const uint64_t need = k2s_start(c->ix.n, kK2Levels + 1) * 4;          // (the keys and their sampled levels, bk_dev_k2.h)
-        const bool want_isa = c->use_wave && c->use_isa && c->d_sa_hi == nullptr && c->ix.n < (1ULL << 32);
+        const bool want_isa = c->use_wave && c->use_isa && im.sa_hi.get() == nullptr && c->ix.n < (1ULL << 32);
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         uint64_t planned = ktab_bytes;
@@ -286,20 +308,19 @@ int tables_begin(bk_ctx *c, TablePlan &tp)
         }
         // the k-mer table's entries as pairs (4-byte indexes; 17 GB more at k = 16): see DevIndex::ktab2
         if (tp.k2 && c->use_ktab2 && !c->ktab64 && fits(ktab_bytes)) tp.ktab2 = true;
-        const size_t bytes = (size_t)ktab_bytes * (tp.ktab2 ? 2 : 1);
-        HIP_TRY(dev_malloc(&c->d_ktab, bytes));
-        c->ktab_bytes = bytes;
+        // (the allocations keep this order: k-mer table, second-level keys, d_bad, the key arrays behind them, inverse suffix array)
+        HIP_TRY(im.ktab.ensure((size_t)ktab_bytes * (tp.ktab2 ? 2 : 1)));
         tp.ktab = true;
         tp.k = k;
         if (tp.k2) {
-            HIP_TRY(dev_malloc(&c->d_k2, need));
-            HIP_TRY(dev_malloc(&tp.d_bad, 16));
-            HIP_TRY(hipMemsetAsync(tp.d_bad, 0, 16, c->stream));
-            for (int i = 0; i < tp.kx; i++) HIP_TRY(dev_malloc(&c->d_kx[i], need));
+            HIP_TRY(im.k2.ensure(need / 4));
+            HIP_TRY(tp.d_bad.ensure(2));
+            HIP_TRY(hipMemsetAsync(tp.d_bad.get(), 0, 16, c->stream));
+            for (int i = 0; i < tp.kx; i++) HIP_TRY(im.kx[i].ensure(need / 4));
         }
     }
-    if (c->use_wave && c->use_isa && c->d_sa_hi == nullptr && c->ix.n < (1ULL << 32)) {
-        HIP_TRY(dev_malloc(&c->d_isa, c->ix.n * 4));
+    if (c->use_wave && c->use_isa && im.sa_hi.get() == nullptr && c->ix.n < (1ULL << 32)) {
+        HIP_TRY(im.isa.ensure(c->ix.n));
         tp.isa = true;
     }
     return BK_OK;
@@ -311,70 +332,68 @@ int tables_range(bk_ctx *c, const TablePlan &tp, uint64_t i0, uint64_t i1, unsig
     DevIndex ix = c->ix;
     ix.k = tp.k;
     const bool last = i1 >= c->ix.n;
-    if (tp.ktab) launch_build_ktab(ix, c->d_ktab, tp.k, c->ktab64, c->stream, i0, last ? c->ix.n + 1 : i1, bucket_starts, tp.ktab2);
-    if (tp.k2) launch_build_k2(ix, c->d_k2, tp.kx > 0 ? c->d_kx[0] : nullptr, tp.kx > 1 ? c->d_kx[1] : nullptr, tp.d_bad, c->stream, i0, i1);
-    if (tp.isa) launch_build_isa(c->d_sa_lo, c->ix.n, c->d_isa, c->stream, i0, i1);
+    const ImageBufs &im = c->image;
+    if (tp.ktab) launch_build_ktab(ix, im.ktab.get(), tp.k, c->ktab64, c->stream, i0, last ? c->ix.n + 1 : i1, bucket_starts, tp.ktab2);
+    if (tp.k2) launch_build_k2(ix, im.k2.get(), tp.kx > 0 ? im.kx[0].get() : nullptr, tp.kx > 1 ? im.kx[1].get() : nullptr, tp.d_bad.get(), c->stream, i0, i1);
+    if (tp.isa) launch_build_isa(im.sa_lo.get(), c->ix.n, im.isa.get(), c->stream, i0, i1);
     HIP_TRY(hipGetLastError());
     return BK_OK;
 }
 
 int tables_end(bk_ctx *c, TablePlan &tp)
 {
+    ImageBufs &im = c->image;
     unsigned long long bad2[2] = {0, 0};
-    if (tp.k2) HIP_TRY(hipMemcpyAsync(bad2, tp.d_bad, 16, hipMemcpyDeviceToHost, c->stream));
+    if (tp.k2) HIP_TRY(hipMemcpyAsync(bad2, tp.d_bad.get(), 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (tp.ktab && c->ktab64 && c->ktab_wide != 2) {
         // the table of an index beyond 2^32 suffixes at half its size (17 of 34 GB at k = 16: room for the window array such an index may
         // ask for): 32-bit offsets from a 64-bit start per 2^16 codes - unless a group of codes spans 2^32 suffixes
         const uint64_t n_entries = (1ULL << (2 * tp.k)) + 1, n_hi = (n_entries >> 16) + 2;
-        uint32_t *d_off = nullptr, *d_flag = nullptr, flag = 1;
-        uint64_t *d_hi = nullptr;
-        if (dev_malloc(&d_off, n_entries * 4) == hipSuccess && dev_malloc(&d_hi, n_hi * 8) == hipSuccess && dev_malloc(&d_flag, 4) == hipSuccess &&
-            hipMemsetAsync(d_flag, 0, 4, c->stream) == hipSuccess) {
-            launch_pack_ktab64((const uint64_t *)c->d_ktab, n_entries, d_off, d_hi, d_flag, c->stream);
-            if (hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) flag = 1;
+        // Order: offsets and ktab_hi are allocated while the 64-bit table lives, which goes (the move frees it) only when nothing overflowed - else the two go, leaving scope, and it is kept
+        DevBuf<uint8_t> d_off;
+        DevBuf<uint64_t> d_hi;
+        DevBuf<uint32_t> d_flag;
+        uint32_t flag = 1;
+        if (d_off.ensure(n_entries * 4) == hipSuccess && d_hi.ensure(n_hi) == hipSuccess && d_flag.ensure(1) == hipSuccess &&
+            hipMemsetAsync(d_flag.get(), 0, 4, c->stream) == hipSuccess) {
+            launch_pack_ktab64((const uint64_t *)im.ktab.get(), n_entries, (uint32_t *)d_off.get(), d_hi.get(), d_flag.get(), c->stream);
+            if (hipMemcpyAsync(&flag, d_flag.get(), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) flag = 1;
         }
         (void)hipGetLastError();
-        free_dev(d_flag);
+        d_flag.reset();
         if (flag == 0) {
-            free_dev(c->d_ktab);
-            c->d_ktab = d_off;
-            c->ktab_bytes = (size_t)n_entries * 4;
-            c->d_ktab_hi = d_hi;
-        } else { free_dev(d_off); free_dev(d_hi); }
+            im.ktab = std::move(d_off);
+            im.ktab_hi = std::move(d_hi);
+        }
     }
     if (tp.ktab) {
-        if (c->ktab64 && c->d_ktab_hi) { c->ix.ktab32 = (const uint32_t *)c->d_ktab; c->ix.ktab_hi = c->d_ktab_hi; }
-        else if (c->ktab64) c->ix.ktab64 = (const uint64_t *)c->d_ktab;
-        else if (tp.ktab2) { c->ix.ktab2 = reinterpret_cast<const uint2 *>(c->d_ktab); c->ktab_is2 = true; c->ix.ktab2_elem = (c->use_ktab2 >= 2 && c->d_sa_hi == nullptr) ? 1 : 0; }
-        else c->ix.ktab32 = (const uint32_t *)c->d_ktab;
+        c->ktab_is2 = tp.ktab2;
         c->ix.k = tp.k;
     }
     const unsigned long long bad = bad2[0];
     if (tp.kx && (bad || bad2[1])) {
         if (!bad) fprintf(stderr, "biokanga_amd: suffix array not in nibble order at %llu place(s) beyond the second-level keys; third-level keys disabled\n", bad2[1]);
-        for (int i = 0; i < kMoreKeys; i++) { free_dev(c->d_kx[i]); c->d_kx[i] = nullptr; }
+        for (auto &b : im.kx) b.reset();
         tp.kx = 0;
     }
     if (tp.k2 && bad) {
         fprintf(stderr, "biokanga_amd: suffix array not in nibble order inside %llu k-mer bucket(s); second-level keys disabled\n", bad);
-        free_dev(c->d_k2);
-        c->d_k2 = nullptr;
+        im.k2.reset();
     } else if (tp.k2) {
-        launch_build_k2_levels(c->d_k2, c->ix.n, c->stream);
-        for (int i = 0; i < tp.kx; i++) launch_build_k2_levels(c->d_kx[i], c->ix.n, c->stream);
+        launch_build_k2_levels(im.k2.get(), c->ix.n, c->stream);
+        for (int i = 0; i < tp.kx; i++) launch_build_k2_levels(im.kx[i].get(), c->ix.n, c->stream);
         HIP_TRY(hipGetLastError());
-        c->ix.k2 = c->d_k2;
-        for (int i = 0; i < kMoreKeys; i++) c->ix.kx[i] = i < tp.kx ? c->d_kx[i] : nullptr;
     }
+    // (every owner is final: published here, in front of the one launch below that reads what was published - ix.ktab2_elem)
+    c->tables_under_way = false;
+    publish_index(c);
     // the second words of a k-mer table of pairs (its first words, the bucket starts, are in place): a bucket's only key or the map of
     // its keys' first five bits - or maps that hide nothing where the keys turned out unusable
     if (tp.ktab2) {
-        if (c->d_k2 == nullptr) c->ix.ktab2_elem = 0;       // (no keys, no two-pass search: nothing hands elements on)
-        launch_fill_ktab2_y(c->d_ktab, c->d_k2, (1ULL << (2 * tp.k)) + 1, c->stream, c->ix.ktab2_elem ? c->d_sa_lo : nullptr);
+        launch_fill_ktab2_y(im.ktab.get(), im.k2.get(), (1ULL << (2 * tp.k)) + 1, c->stream, c->ix.ktab2_elem ? im.sa_lo.get() : nullptr);
         HIP_TRY(hipGetLastError());
     }
-    if (tp.isa) c->ix.isa = c->d_isa;
     HIP_TRY(hipStreamSynchronize(c->stream));       // (batches run on their callers' streams, which do not wait for this one)
     // pass B's items grouped by bucket: 1.6 ms of a C2 step's pass B for 2.2 ms of sorting once the deep bisections run over key arrays
     // (profiles/NOTES.md, round 5) - grouped only where they still run over suffix array + target
@@ -396,9 +415,9 @@ int build_tables(bk_ctx *c)
 // 2 bit/base target copy + N/EOS block bitmap for the window compare of the extend kernels
 int build_tgt2(bk_ctx *c)
 {
-    free_dev(c->d_tgt2); free_dev(c->d_nflag); free_dev(c->d_tgt2s); c->d_tgt2s = nullptr; c->ix.tgt2s = nullptr;
-    c->d_tgt2 = nullptr; c->d_nflag = nullptr;
-    c->ix.tgt2 = nullptr; c->ix.nflag = nullptr;
+    ImageBufs &im = c->image;
+    im.tgt2.reset(); im.nflag.reset(); im.tgt2s.reset();
+    publish_index(c);
     if (!c->use_tgt2) return BK_OK;
     const uint64_t nblocks = c->n_tgt4_words / 4;
     // flag granule: the smallest power of two that keeps the bitmap within 16 KB; at least 512 bases so that a
@@ -407,29 +426,23 @@ int build_tgt2(bk_ctx *c)
     int shift = 9;
     while ((((nblocks * 64) >> shift) + 7) / 8 > 16384) shift++;
     const uint64_t flag_bytes = (((((nblocks * 64) >> shift) + 1) + 31) / 32) * 4 + 16;
-    HIP_TRY(dev_malloc(&c->d_tgt2, nblocks * 16 + 64));
-    HIP_TRY(dev_malloc(&c->d_nflag, flag_bytes));
-    c->nflag_bytes = flag_bytes;
-    HIP_TRY(hipMemsetAsync(c->d_nflag, 0, flag_bytes, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_tgt2 + nblocks * 2, 0, 64, c->stream));
-    launch_pack_target2(c->d_tgt4, c->n_tgt4_words, c->d_tgt2, (unsigned int *)c->d_nflag, shift, c->stream);
+    HIP_TRY(im.tgt2.ensure(nblocks * 2 + 8));
+    HIP_TRY(im.nflag.ensure(flag_bytes));
+    HIP_TRY(hipMemsetAsync(im.nflag.get(), 0, flag_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(im.tgt2.get() + nblocks * 2, 0, 64, c->stream));
+    launch_pack_target2(im.tgt4.get(), c->n_tgt4_words, im.tgt2.get(), (unsigned int *)im.nflag.get(), shift, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->ix.tgt2 = c->d_tgt2;
-    c->ix.nflag = c->d_nflag;
     c->ix.nflag_bytes = (uint32_t)flag_bytes;
-    free_dev(c->d_tgt2s);
-    c->d_tgt2s = nullptr;
-    c->ix.tgt2s = nullptr;
     if (c->use_tgt2 >= 2) {
         // second copy: element j holds tgt2[j + 4], i.e. logical byte p sits at physical byte p - 32
-        HIP_TRY(dev_malloc(&c->d_tgt2s, nblocks * 16 + 64));
-        HIP_TRY(clear_dev(c->d_tgt2s, nblocks * 16 + 64, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_tgt2s, c->d_tgt2 + 4, (nblocks * 2 - 4) * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(im.tgt2s.ensure(nblocks * 2 + 8));
+        HIP_TRY(clear_dev(im.tgt2s.get(), nblocks * 16 + 64, c->stream));
+        HIP_TRY(hipMemcpyAsync(im.tgt2s.get(), im.tgt2.get() + 4, (nblocks * 2 - 4) * 8, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->ix.tgt2s = c->d_tgt2s;
     }
     c->ix.flag_shift = shift;
+    publish_index(c);
     return BK_OK;
 }
 
@@ -450,37 +463,35 @@ int setup_entries(bk_ctx *c, const bk_entry_info *entries, uint32_t n_entries)
         c->tot_seq_len += entries[i].seq_len;
         if (i && es[i] <= ee[i - 1]) return BK_ERR_PARAMS;
     }
-    HIP_TRY(dev_malloc(&c->d_ent_start, n_entries * 8));
-    HIP_TRY(dev_malloc(&c->d_ent_end, n_entries * 8));
-    HIP_TRY(dev_malloc(&c->d_ent_id, n_entries * 4));
-    HIP_TRY(hipMemcpy(c->d_ent_start, es.data(), n_entries * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_ent_end, ee.data(), n_entries * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_ent_id, ei.data(), n_entries * 4, hipMemcpyHostToDevice));
-    c->ix.ent_start = c->d_ent_start;
-    c->ix.ent_end = c->d_ent_end;
-    c->ix.ent_id = c->d_ent_id;
+    ImageBufs &im = c->image; FixedBufs &fx = c->fixed;
+    HIP_TRY(im.ent_start.ensure(n_entries));
+    HIP_TRY(im.ent_end.ensure(n_entries));
+    HIP_TRY(im.ent_id.ensure(n_entries));
+    HIP_TRY(hipMemcpy(im.ent_start.get(), es.data(), n_entries * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(im.ent_end.get(), ee.data(), n_entries * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(im.ent_id.get(), ei.data(), n_entries * 4, hipMemcpyHostToDevice));
     {   // EntryID -> entry index, for the per-sequence hit counts
         uint32_t max_id = 0;
         for (uint32_t i = 0; i < n_entries; i++) max_id = std::max(max_id, ei[i]);
         if ((uint64_t)max_id > 16ULL * n_entries + (1u << 20)) return BK_ERR_PARAMS;
         std::vector<uint32_t> map((size_t)max_id + 1, 0xFFFFFFFFu);
         for (uint32_t i = 0; i < n_entries; i++) map[ei[i]] = i;
-        HIP_TRY(dev_malloc(&c->d_id2idx, map.size() * 4));
-        HIP_TRY(hipMemcpy(c->d_id2idx, map.data(), map.size() * 4, hipMemcpyHostToDevice));
-        c->ix.id2idx = c->d_id2idx;
+        HIP_TRY(im.id2idx.ensure(map.size()));
+        HIP_TRY(hipMemcpy(im.id2idx.get(), map.data(), map.size() * 4, hipMemcpyHostToDevice));
         c->ix.max_id = max_id;
     }
     c->ix.n_ent = n_entries;
-    HIP_TRY(dev_malloc(&c->d_seq_counts, n_entries * 8));
-    HIP_TRY(dev_zero_now(c->d_seq_counts, n_entries * 8));
-    HIP_TRY(dev_malloc(&c->d_ctr, (size_t)kCtrStripes * 8 * 8));
-    HIP_TRY(dev_zero_now(c->d_ctr, (size_t)kCtrStripes * 8 * 8));
-    HIP_TRY(dev_malloc(&c->d_small, 16 * 4));
-    HIP_TRY(dev_malloc(&c->d_ctl, sizeof(PhaseCtl) * (kMaxPhases + 2)));
+    publish_index(c);
+    HIP_TRY(fx.seq_counts.ensure(n_entries));
+    HIP_TRY(dev_zero_now(fx.seq_counts.get(), n_entries * 8));
+    HIP_TRY(fx.ctr.ensure((size_t)kCtrStripes * 8));
+    HIP_TRY(dev_zero_now(fx.ctr.get(), (size_t)kCtrStripes * 8 * 8));
+    HIP_TRY(fx.small.ensure(16));
+    HIP_TRY(fx.ctl.ensure(kMaxPhases + 2));
     HIP_TRY(hipHostMalloc(&c->h_ctl, sizeof(PhaseCtl) * (kMaxPhases + 2)));
     HIP_TRY(bk::make_wait_event(&c->ev_ctl));
     HIP_TRY(bk::make_wait_event(&c->ev_wait));
-    HIP_TRY(dev_malloc(&c->d_ctr_aux, 32));
+    HIP_TRY(fx.ctr_aux.ensure(4));
     HIP_TRY(hipHostMalloc(&c->h_small, 2 * sizeof(PhaseCtl)));
     int rc = derive_cfg(c);
     clk0.lap("entry table, small buffers");
@@ -531,28 +542,27 @@ int adopt_device_image(bk_ctx *c, const uint8_t *d_seq, uint64_t n, const uint8_
     c->el_size = (uint32_t)el;
     c->ix.n = n;
     uint64_t nwords = ((n + 15) / 16 + (kMaxReadLenAbs / 16) + 4 + 3) & ~3ULL;      // whole 64-base blocks
-    HIP_TRY(dev_malloc(&c->d_tgt4, nwords * 8));
-    launch_pack_target(d_seq, n, c->d_tgt4, nwords, c->stream);
+    ImageBufs &im = c->image;
+    HIP_TRY(im.tgt4.ensure(nwords));
+    launch_pack_target(d_seq, n, im.tgt4.get(), nwords, c->stream);
     HIP_TRY(hipGetLastError());
     c->n_tgt4_words = nwords;
     c->sort_shift = 0;
     while ((n >> c->sort_shift) >= (1ULL << 32)) c->sort_shift++;
     if (d_sa == nullptr) {
-        // (4-byte elements that the caller has put where they stay: c->d_sa_lo is allocated and filled)
-        if (el != 4 || !c->d_sa_lo) return BK_ERR_INTERNAL;
+        // (4-byte elements that the caller has put where they stay: image.sa_lo is allocated and filled)
+        if (el != 4 || !im.sa_lo.get()) return BK_ERR_INTERNAL;
     } else {
-        HIP_TRY(dev_malloc(&c->d_sa_lo, n * 4));
+        HIP_TRY(im.sa_lo.ensure(n));
         if (el == 5) {
-            HIP_TRY(dev_malloc(&c->d_sa_hi, n));
-            launch_split_sa5(d_sa, n, c->d_sa_lo, c->d_sa_hi, c->stream);
+            HIP_TRY(im.sa_hi.ensure(n));
+            launch_split_sa5(d_sa, n, im.sa_lo.get(), im.sa_hi.get(), c->stream);
             HIP_TRY(hipGetLastError());
         } else
-            HIP_TRY(hipMemcpyAsync(c->d_sa_lo, d_sa, n * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(im.sa_lo.get(), d_sa, n * 4, hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->ix.tgt4 = c->d_tgt4;
-    c->ix.sa_lo = c->d_sa_lo;
-    c->ix.sa_hi = c->d_sa_hi;
+    publish_index(c);
     return BK_OK;
 }
 
@@ -565,20 +575,18 @@ int adopt_device_image(bk_ctx *c, const uint8_t *d_seq, uint64_t n, const uint8_
 // the window array and its map given back (the caller has waited for whatever reads them)
 void bk::drop_swin(bk_ctx *c)
 {
-    free_dev(c->d_swin);
-    free_dev(c->d_swmap);
-    c->d_swin = nullptr;
-    c->d_swmap = nullptr;
-    c->ix.swin = nullptr;
-    c->ix.swmap = nullptr;
+    c->image.swin.reset();
+    c->image.swmap.reset();
+    publish_index(c);
     c->swin_bytes = 0;
 }
 
 // frees the suffix-ordered window array (and does not build it again): called when something else needs the HBM
 void bk::release_swin(bk_ctx *c)
 {
-    if (!c || !c->d_swin) return;
+    if (!c || !c->image.swin.get()) return;
     (void)hipSetDevice(c->device);
+    // (order: whatever reads the array has ended before it is given back)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipDeviceSynchronize();
     drop_swin(c);
@@ -601,29 +609,31 @@ struct SwinBuild {
     int mode = 0;                             // 0: one range, entries sized by its coverage; 1: ranges behind the upload's slices; 2: ranges of an index in place
     uint64_t done = 0;                        // suffix array indexes below this are dealt with (a multiple of 64, or n)
     uint64_t range_cap = 0;                   // most indexes one range may hold (what the scratch is sized for)
-    unsigned long long *d_brk[kSwLevels] = {};
-    uint32_t *d_flags = nullptr, *d_incl = nullptr, *d_map = nullptr, *d_used = nullptr;
-    void *d_tmp = nullptr, *d_ent = nullptr;
+    DevBuf<unsigned long long> d_brk[kSwLevels];
+    DevBuf<uint32_t> d_flags, d_incl, d_map, d_used;
+    DevBuf<uint8_t> d_tmp, d_ent;             // the scan's temporary; the entries (the context's window array once swin_end hands them over)
     size_t tmp_bytes = 0;
-    unsigned long long *d_starts = nullptr;   // bucket-start bitmap from k_build_ktab (null: read off the finished k-mer table)
+    DevBuf<unsigned long long> d_starts;      // bucket-start bitmap from k_build_ktab (empty: read off the finished k-mer table)
     // sliced builds: the entries' memory is allocated by a thread of its own from the moment the index's size is known (a large
     // allocation takes the driver 16 ms per GB and more when another process has just given memory back): ranges whose turn comes
     // before it is there have their entries made later
     std::thread ent_alloc;
     std::atomic<int> ent_state{0};            // 0 not asked for, 1 being allocated, 2 there, 3 failed
-    void *ent_mem = nullptr;
+    DevBuf<uint8_t> ent_mem;                  // (the thread's until ent_state leaves 1)
     uint64_t filled = 0;                      // entries of the suffix array indexes below this are made
     double t0 = 0;
-    void drop_scratch() { for (auto &q : d_brk) { free_dev(q); q = nullptr; } free_dev(d_flags); free_dev(d_incl); free_dev(d_tmp); free_dev(d_starts); d_flags = d_incl = nullptr; d_tmp = nullptr; d_starts = nullptr; }
-    ~SwinBuild() { if (ent_alloc.joinable()) ent_alloc.join(); if (ent_mem && ent_mem != d_ent) free_dev(ent_mem); drop_scratch(); free_dev(d_map); free_dev(d_ent); free_dev(d_used); }
+    void drop_scratch() { for (auto &q : d_brk) q.reset(); d_flags.reset(); d_incl.reset(); d_tmp.reset(); d_starts.reset(); }
+    // Order: the allocating thread is joined before its memory is touched or released (the members go after this body)
+    ~SwinBuild() { if (ent_alloc.joinable()) ent_alloc.join(); }
+    // the thread's memory becomes the entries' once it is there (not while it is still being allocated, or when that failed)
+    void take_ahead() { if (ent_state == 2) { if (ent_alloc.joinable()) ent_alloc.join(); if (ent_mem.get()) d_ent = std::move(ent_mem); } }
+    void brk_ptrs(unsigned long long **out) { for (int l = 0; l < kSwLevels; l++) out[l] = d_brk[l].get(); }
     // the entries' memory, asked for ahead of swin_begin: `bytes` on `device`
     void alloc_ahead(int device, uint64_t bytes)
     {
         ent_state = 1;
         ent_alloc = std::thread([this, device, bytes]() {
-            void *p = nullptr;
-            if (hipSetDevice(device) != hipSuccess || dev_malloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); ent_state = 3; return; }
-            ent_mem = p;
+            if (hipSetDevice(device) != hipSuccess || ent_mem.ensure(bytes) != hipSuccess) { (void)hipGetLastError(); ent_state = 3; return; }
             ent_state = 2;
         });
     }
@@ -687,20 +697,19 @@ int swin_begin(bk_ctx *c, SwinBuild &sb, const int *w, int n_levels, int words, 
     if (sb.cap_blocks == 0) return 1;
     sb.range_cap = std::min<uint64_t>(range_cap, n) + 64;
     const uint64_t brk_words = (sb.range_cap >> 6) + 4, blocks = (sb.range_cap >> kSwBlkShift) + 2;
-#define SW_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (void)hipGetLastError(); return e_ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL; } } while (0)
-    for (int l = 0; l < n_levels; l++) SW_TRY(dev_malloc(&sb.d_brk[l], brk_words * 8));
-    SW_TRY(dev_malloc(&sb.d_flags, blocks * 4));
-    SW_TRY(dev_malloc(&sb.d_incl, blocks * 4));
-    SW_TRY(dev_malloc(&sb.d_map, n_blocks * 4));
-    SW_TRY(dev_malloc(&sb.d_used, 4));
-    SW_TRY(hipMemsetAsync(sb.d_used, 0, 4, s));
-    SW_TRY(bk::prim::inclusive_sum(nullptr, sb.tmp_bytes, sb.d_flags, sb.d_incl, (size_t)blocks, s));
-    SW_TRY(dev_malloc(&sb.d_tmp, sb.tmp_bytes + 256));
+    for (int l = 0; l < n_levels; l++) SW_TRY(sb.d_brk[l].ensure(brk_words));
+    SW_TRY(sb.d_flags.ensure(blocks));
+    SW_TRY(sb.d_incl.ensure(blocks));
+    SW_TRY(sb.d_map.ensure(n_blocks));
+    SW_TRY(sb.d_used.ensure(1));
+    SW_TRY(hipMemsetAsync(sb.d_used.get(), 0, 4, s));
+    SW_TRY(bk::prim::inclusive_sum(nullptr, sb.tmp_bytes, sb.d_flags.get(), sb.d_incl.get(), (size_t)blocks, s));
+    SW_TRY(sb.d_tmp.ensure(sb.tmp_bytes + 256));
     sb.mode = mode;
     if (mode == 1) {
-        if (sb.ent_state == 0) SW_TRY(dev_malloc(&sb.d_ent, (uint64_t)sb.cap_blocks * block_bytes));      // (else: alloc_ahead's thread brings it)
-        SW_TRY(dev_malloc(&sb.d_starts, ((n >> 6) + 4) * 8));
-        SW_TRY(clear_dev(sb.d_starts, ((n >> 6) + 4) * 8, s));
+        if (sb.ent_state == 0) SW_TRY(sb.d_ent.ensure((uint64_t)sb.cap_blocks * block_bytes));      // (else: alloc_ahead's thread brings it)
+        SW_TRY(sb.d_starts.ensure((n >> 6) + 4));
+        SW_TRY(clear_dev(sb.d_starts.get(), ((n >> 6) + 4) * 8, s));
     }
     return BK_OK;
 }
@@ -709,32 +718,34 @@ int swin_begin(bk_ctx *c, SwinBuild &sb, const int *w, int n_levels, int words, 
 int swin_range(bk_ctx *c, SwinBuild &sb, const DevIndex &ix, uint64_t upto, hipStream_t s)
 {
     const uint64_t n = ix.n;
+    unsigned long long *brk[kSwLevels];
+    sb.brk_ptrs(brk);
     while (sb.done < n) {
         uint64_t e = upto >= n ? n : (upto & ~63ULL);
         if (e > sb.done && e - sb.done > sb.range_cap - 64) e = (sb.done + sb.range_cap - 64) & ~63ULL;      // (no more than the scratch holds at a time)
         if (e <= sb.done) break;
         const uint64_t a = sb.done, len = e - a;
         const uint64_t n_words = (len >> 6) + 2, n_blocks = (len + (1u << kSwBlkShift) - 1) >> kSwBlkShift;
-        launch_swin_breaks(ix, sb.w, sb.n_levels, sb.d_brk, a, e, n_words, sb.d_starts, s);
-        for (int l = 0; l < sb.n_levels; l++) launch_swin_cover(sb.d_brk[l], len, sb.max_run, sb.min_run, sb.d_flags, n_blocks, l == 0, s);
+        launch_swin_breaks(ix, sb.w, sb.n_levels, brk, a, e, n_words, sb.d_starts.get(), s);
+        for (int l = 0; l < sb.n_levels; l++) launch_swin_cover(brk[l], len, sb.max_run, sb.min_run, sb.d_flags.get(), n_blocks, l == 0, s);
         SW_TRY(hipGetLastError());
         size_t tb = sb.tmp_bytes;
-        SW_TRY(bk::prim::inclusive_sum(sb.d_tmp, tb, sb.d_flags, sb.d_incl, (size_t)n_blocks, s));
-        launch_swin_map(sb.d_flags, sb.d_incl, n_blocks, sb.cap_blocks, sb.d_used, sb.d_map + (a >> kSwBlkShift), s);
-        if (sb.d_ent == nullptr && sb.ent_state == 2) sb.d_ent = sb.ent_mem;
-        if (sb.d_ent == nullptr && sb.ent_state == 1) { sb.done = e; continue; }       // (its memory is not there yet: the entries follow)
-        if (sb.d_ent == nullptr && sb.ent_state == 3) return BK_ERR_MEM;
-        if (sb.d_ent == nullptr) {
+        SW_TRY(bk::prim::inclusive_sum(sb.d_tmp.get(), tb, sb.d_flags.get(), sb.d_incl.get(), (size_t)n_blocks, s));
+        launch_swin_map(sb.d_flags.get(), sb.d_incl.get(), n_blocks, sb.cap_blocks, sb.d_used.get(), sb.d_map.get() + (a >> kSwBlkShift), s);
+        if (sb.d_ent.get() == nullptr) sb.take_ahead();
+        if (sb.d_ent.get() == nullptr && sb.ent_state == 1) { sb.done = e; continue; }       // (its memory is not there yet: the entries follow)
+        if (sb.d_ent.get() == nullptr && sb.ent_state == 3) return BK_ERR_MEM;
+        if (sb.d_ent.get() == nullptr) {
             // (the whole array in one range: the entries take what the coverage needs, known now)
             if (a != 0 || e != n) return BK_ERR_INTERNAL;
             uint32_t used = 0;
-            SW_TRY(hipMemcpyAsync(&used, sb.d_used, 4, hipMemcpyDeviceToHost, s));
+            SW_TRY(hipMemcpyAsync(&used, sb.d_used.get(), 4, hipMemcpyDeviceToHost, s));
             SW_TRY(hipStreamSynchronize(s));
             if (used == 0) { sb.done = e; return BK_OK; }
             sb.cap_blocks = used;
-            SW_TRY(dev_malloc(&sb.d_ent, (uint64_t)used * ((uint64_t)(16 * sb.words) << kSwBlkShift)));
+            SW_TRY(sb.d_ent.ensure((uint64_t)used * ((uint64_t)(16 * sb.words) << kSwBlkShift)));
         }
-        launch_swin_fill(ix, sb.d_map, sb.d_ent, sb.words, sb.filled, e, s);
+        launch_swin_fill(ix, sb.d_map.get(), sb.d_ent.get(), sb.words, sb.filled, e, s);
         SW_TRY(hipGetLastError());
         sb.filled = e;
         sb.done = e;
@@ -753,32 +764,34 @@ int swin_fit(bk_ctx *c, SwinBuild &sb, const DevIndex &ix, hipStream_t s)
                                       1344, 1408, 1472, 1536, 1664, 1792, 1920, 2048, 2304, 2560, 3072, 4096, 6144, 8192};
     constexpr int NL = (int)(sizeof(ladder) / sizeof(ladder[0]));
     const uint64_t n = ix.n;
-    unsigned long long *d_cnt = nullptr;
-    SW_TRY(dev_malloc(&d_cnt, NL * 8));
-    SW_TRY(hipMemsetAsync(d_cnt, 0, NL * 8, s));
+    DevBuf<unsigned long long> d_cnt;
+    unsigned long long *brk[kSwLevels];
+    sb.brk_ptrs(brk);
+    SW_TRY(d_cnt.ensure(NL));
+    SW_TRY(hipMemsetAsync(d_cnt.get(), 0, NL * 8, s));
     for (uint64_t a = 0; a < n;) {
         uint64_t e = std::min<uint64_t>(n, (a + sb.range_cap - 64) & ~63ULL);
         const uint64_t len = e - a, n_words = (len >> 6) + 2, n_blocks = (len + (1u << kSwBlkShift) - 1) >> kSwBlkShift;
-        launch_swin_breaks(ix, sb.w, sb.n_levels, sb.d_brk, a, e, n_words, nullptr, s);
+        launch_swin_breaks(ix, sb.w, sb.n_levels, brk, a, e, n_words, nullptr, s);
         for (int q = 0; q < NL; q++) {
             if (ladder[q] > sb.max_run) break;
-            for (int l = 0; l < sb.n_levels; l++) launch_swin_cover(sb.d_brk[l], len, sb.max_run, ladder[q], sb.d_flags, n_blocks, l == 0, s);
-            launch_count_nonzero(sb.d_flags, n_blocks, d_cnt + q, s);
+            for (int l = 0; l < sb.n_levels; l++) launch_swin_cover(brk[l], len, sb.max_run, ladder[q], sb.d_flags.get(), n_blocks, l == 0, s);
+            launch_count_nonzero(sb.d_flags.get(), n_blocks, d_cnt.get() + q, s);
         }
         SW_TRY(hipGetLastError());
         a = e;
     }
     unsigned long long cnt[NL] = {};
-    SW_TRY(hipMemcpyAsync(cnt, d_cnt, NL * 8, hipMemcpyDeviceToHost, s));
+    SW_TRY(hipMemcpyAsync(cnt, d_cnt.get(), NL * 8, hipMemcpyDeviceToHost, s));
     SW_TRY(hipStreamSynchronize(s));
-    free_dev(d_cnt);
+    d_cnt.reset();
     int pick = 0;
     while (pick + 1 < NL && ladder[pick + 1] <= sb.max_run && cnt[pick] > sb.cap_blocks) pick++;
     sb.min_run = ladder[pick];
     const uint64_t blocks = std::min<uint64_t>(cnt[pick], sb.cap_blocks);
     if (blocks == 0) return 1;
     sb.cap_blocks = (uint32_t)blocks;
-    SW_TRY(dev_malloc(&sb.d_ent, blocks * ((uint64_t)(16 * sb.words) << kSwBlkShift)));
+    SW_TRY(sb.d_ent.ensure(blocks * ((uint64_t)(16 * sb.words) << kSwBlkShift)));
     StageClock clk;
     if (clk.on) fprintf(stderr, "biokanga_amd: window array: runs of %u and more suffixes covered whole (the rule at 65: %.1f %% of the suffix array, this: %.1f %%, room for %.1f %%)\n", sb.min_run,
                         100.0 * (double)cnt[0] * 32.0 / (double)n, 100.0 * (double)cnt[pick] * 32.0 / (double)n, 100.0 * (double)blocks * 32.0 / (double)n);
@@ -790,31 +803,26 @@ int swin_end(bk_ctx *c, SwinBuild &sb, hipStream_t s)
 {
     if (sb.ent_alloc.joinable()) sb.ent_alloc.join();
     if (sb.ent_state == 3) return BK_ERR_MEM;
-    if (sb.ent_state == 2 && sb.d_ent == nullptr) sb.d_ent = sb.ent_mem;
-    if (sb.d_ent != nullptr && sb.filled < sb.done) {       // (the ranges that came before the entries' memory did)
-        launch_swin_fill(c->ix, sb.d_map, sb.d_ent, sb.words, sb.filled, sb.done, s);
+    if (sb.d_ent.get() == nullptr) sb.take_ahead();
+    if (sb.d_ent.get() != nullptr && sb.filled < sb.done) {       // (the ranges that came before the entries' memory did)
+        launch_swin_fill(c->ix, sb.d_map.get(), sb.d_ent.get(), sb.words, sb.filled, sb.done, s);
         sb.filled = sb.done;
     }
     uint32_t used = 0;
-    SW_TRY(hipMemcpyAsync(&used, sb.d_used, 4, hipMemcpyDeviceToHost, s));
+    SW_TRY(hipMemcpyAsync(&used, sb.d_used.get(), 4, hipMemcpyDeviceToHost, s));
     SW_TRY(hipStreamSynchronize(s));
     sb.drop_scratch();
     if (sb.done < c->ix.n) return BK_ERR_INTERNAL;
     if (used == 0) return 1;
     const uint64_t block_bytes = (uint64_t)(16 * sb.words) << kSwBlkShift;
-#undef SW_TRY
     const uint64_t n_blocks = (c->ix.n + (1u << kSwBlkShift) - 1) >> kSwBlkShift;
-    c->d_swin = sb.d_ent;
-    c->d_swmap = sb.d_map;
-    sb.d_ent = nullptr;
-    sb.ent_mem = nullptr;
-    sb.d_map = nullptr;
+    c->image.swin = std::move(sb.d_ent);
+    c->image.swmap = std::move(sb.d_map);
     c->swin_w = sb.w[0] | (sb.w[sb.n_levels - 1] << 8) | (sb.n_levels << 16) | (sb.words << 24);
     c->ix.sw_words = sb.words;
     c->swin_bytes = (uint64_t)std::max(used, sb.cap_blocks) * block_bytes + n_blocks * 4;      // (what is allocated: a sliced build's entries were sized before its coverage was known)
     c->swin_covered = (double)used / (double)n_blocks;
-    c->ix.swin = reinterpret_cast<const uint4 *>(c->d_swin);
-    c->ix.swmap = c->d_swmap;
+    publish_index(c);
     c->swin_setup_s = StageClock::now() - sb.t0;
     return BK_OK;
 }
@@ -838,7 +846,8 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
 {
     // (an index of 5-byte elements has no inverse suffix array: its wave kernel forms keep the reference's set of seen keys, and take
     // windows from the array all the same)
-    const bool wide = c->d_sa_hi != nullptr || c->ix.n >= (1ULL << 32);
+    ImageBufs &im = c->image;
+    const bool wide = im.sa_hi.get() != nullptr || c->ix.n >= (1ULL << 32);
     if (!c->use_swin || c->swin_denied || !c->ix.tgt2 || (!wide && !c->ix.isa) || !c->ix.k2 || !c->use_wave) return BK_OK;
     // (.. when asked to - "use_swin" 2, `--window-array on`: making it goes over such an index twice, seconds at 17 Gbp, which a job of
     // BASELINE config 5's size per device does not earn back; the policy's 1 leaves such an index without)
@@ -851,15 +860,15 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
     // entries of three 16-byte words for the kernel family of reads of up to 128 bases, of five for the one of up to 256 (SwGeo)
     const int words = maxlen <= 128 ? 3 : 5;
     const int w_key = w[0] | (w[n_levels - 1] << 8) | (n_levels << 16) | (words << 24);
-    if (wide && c->d_swin && c->ix.sw_words == words) return BK_OK;      // (such an index's array is kept as it was made: its levels follow a batch's phases, which differ a little every time)
-    if (c->d_swin) {
+    if (wide && im.swin.get() && c->ix.sw_words == words) return BK_OK;      // (such an index's array is kept as it was made: its levels follow a batch's phases, which differ a little every time)
+    if (im.swin.get()) {
         // (a partial array made for other core lengths is made again ONCE - the eager build's guess of a hundred bases against what the
         // first batch really holds; after that an array of the right entry size is kept whatever the next batch's longest read: coverage
         // never changes a result, and batches of variable-length reads would otherwise drop and rebuild 25 GB every time their longest
         // read crosses a core length)
-        if (full == (c->d_swmap == nullptr) && (full ? c->ix.sw_words == words : (c->swin_w == w_key || (c->swin_rebuilt && c->ix.sw_words == words)))) return BK_OK;
+        if (full == (im.swmap.get() == nullptr) && (full ? c->ix.sw_words == words : (c->swin_w == w_key || (c->swin_rebuilt && c->ix.sw_words == words)))) return BK_OK;
         c->swin_rebuilt = true;
-        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipStreamSynchronize(s));          // (order: the batches' stream has ended before the array it reads is given back)
         drop_swin(c);
     }
     // (it serves the register-window kernel families of reads of up to 128 and up to 256 bases: every core of reads of up to 100 / 160
@@ -876,8 +885,8 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
     if (full) {
         const uint64_t need = ((c->ix.n + 31) & ~31ULL) * 16 * (uint64_t)words;             // (whole blocks of 32 entries: sw_word_at)
         if ((uint64_t)free_b < need + reserve) { c->swin_denied = true; return BK_OK; }      // (asked once)
-        if (dev_malloc(&c->d_swin, need) != hipSuccess) { (void)hipGetLastError(); c->d_swin = nullptr; c->swin_denied = true; return BK_OK; }
-        launch_build_swin(c->ix, c->d_swin, words, s);
+        if (im.swin.ensure(need) != hipSuccess) { (void)hipGetLastError(); c->swin_denied = true; return BK_OK; }
+        launch_build_swin(c->ix, im.swin.get(), words, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s));
         c->swin_bytes = need;
@@ -897,8 +906,7 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
         if (rb == BK_ERR_INTERNAL) return rb;
         if (rb) { c->swin_denied = true; return BK_OK; }                   // (no room, or nothing worth covering: asked once)
     }
-    c->ix.swin = reinterpret_cast<const uint4 *>(c->d_swin);
-    c->ix.swmap = c->d_swmap;
+    publish_index(c);
     if (full) c->swin_setup_s = StageClock::now() - t0;
     if (clk.on) fprintf(stderr, "biokanga_amd: window array for %.1f %% of the suffix array (runs sharing %d .. %d bases, %d levels), entries of %d bytes, %.2f GB\n", 100.0 * c->swin_covered, w[0], w[n_levels - 1], n_levels, 16 * words, c->swin_bytes / 1e9);
     clk.lap("suffix-ordered windows");
@@ -972,26 +980,25 @@ int bk_ctx_create_ex(bk_ctx **out, const char *sfx_path, int device_id, const bk
     }
     // stage the file image through HBM: bases and suffix array as they are on disk
     // (4-byte suffix array elements are stored as the file holds them: they travel straight to where they stay)
-    uint8_t *d_seq = nullptr, *d_sa = nullptr;
+    DevBuf<uint8_t> d_seq, d_sa;
     const bool sa_in_place = f.el_size == 4;
-    auto cleanup = [&]() { free_dev(d_seq); free_dev(d_sa); };
-    if (dev_malloc(&d_seq, f.concat_len + 16) != hipSuccess ||
-        (sa_in_place ? dev_malloc(&c->d_sa_lo, f.concat_len * 4) : dev_malloc(&d_sa, f.concat_len * f.el_size)) != hipSuccess) {
-        cleanup(); bk_ctx_destroy(c); return BK_ERR_MEM;
+    // (order: image.sa_lo is allocated here, before the upload, not by adopt_device_image)
+    if (d_seq.ensure(f.concat_len + 16) != hipSuccess ||
+        (sa_in_place ? c->image.sa_lo.ensure(f.concat_len) : d_sa.ensure(f.concat_len * f.el_size)) != hipSuccess) {
+        bk_ctx_destroy(c); return BK_ERR_MEM;
     }
     clk.lap("device allocations");
     // (read() into the staging buffers, not through the mapping: its pages would be faulted in one by one, and handed back one by one at exit)
     const int fd = ::open(sfx_path, O_RDONLY);
-    if (fd < 0) { cleanup(); bk_ctx_destroy(c); return BK_ERR_OPNFILE; }
+    if (fd < 0) { bk_ctx_destroy(c); return BK_ERR_OPNFILE; }
     const uint64_t seq_ofs = (uint64_t)(f.seq - (const uint8_t *)f.map_base), sa_ofs = (uint64_t)(f.sa - (const uint8_t *)f.map_base);
-    bool sent = upload_file(d_seq, fd, seq_ofs, f.concat_len, device_id) == BK_OK;
+    bool sent = upload_file(d_seq.get(), fd, seq_ofs, f.concat_len, device_id) == BK_OK;
     clk.lap("upload bases");
     if (sent && sa_in_place) {
         // 4-byte elements: the bases are packed at once, and the suffix array follows in slices - the tables that are one pass over its
         // indexes (k-mer table, second-level keys, inverse suffix array) are made of slice i while slice i + 1 crosses PCIe
-        rc = adopt_device_image(c, d_seq, f.concat_len, nullptr, 4);
-        free_dev(d_seq);
-        d_seq = nullptr;
+        rc = adopt_device_image(c, d_seq.get(), f.concat_len, nullptr, 4);
+        d_seq.reset();           // (order: the staged bases go before tables_begin allocates)
         TablePlan tp;
         if (!rc) rc = tables_begin(c, tp);
         const uint64_t n = f.concat_len;
@@ -1012,19 +1019,19 @@ int bk_ctx_create_ex(bk_ctx **out, const char *sfx_path, int device_id, const bk
                 sb.ent_state = 1;                                   // (its entries come from alloc_ahead's thread, started below)
                 swin_sliced = swin_begin(c, sb, w, n_levels, 3, swin_ahead, n / n_slices + 128, 1, c->stream) == BK_OK;
                 if (!swin_sliced) { (void)hipGetLastError(); sb.ent_state = 0; }
-                else sb.alloc_ahead(device_id, swin_ahead);
+                else sb.alloc_ahead(device_id, swin_ahead);          // (order: the thread's allocation starts after swin_begin's)
             }
         }
         for (uint64_t k = 0; k < n_slices && !rc && sent; k++) {
             // (slices start at multiples of 64 indexes: the k-mer table's builder notes the bucket starts a word of a bitmap at a time)
             const uint64_t i0 = (n * k / n_slices) & ~63ULL, i1 = k + 1 == n_slices ? n : (n * (k + 1) / n_slices) & ~63ULL;
             if (i1 <= i0) continue;
-            sent = upload_file(c->d_sa_lo + i0, fd, sa_ofs + i0 * 4, (i1 - i0) * 4, device_id) == BK_OK;
-            if (sent) rc = tables_range(c, tp, i0, i1, swin_sliced ? sb.d_starts : nullptr);
+            sent = upload_file(c->image.sa_lo.get() + i0, fd, sa_ofs + i0 * 4, (i1 - i0) * 4, device_id) == BK_OK;
+            if (sent) rc = tables_range(c, tp, i0, i1, swin_sliced ? sb.d_starts.get() : nullptr);
             if (sent && !rc && swin_sliced) {
                 DevIndex ix = c->ix;
                 ix.k = tp.k;
-                ix.k2 = c->d_k2;
+                ix.k2 = c->image.k2.get();          // (the keys are not published before tables_end: this copy alone sees them)
                 if (swin_range(c, sb, ix, i1, c->stream) != BK_OK) { (void)hipGetLastError(); swin_sliced = false; }
             }
         }
@@ -1035,16 +1042,16 @@ int bk_ctx_create_ex(bk_ctx **out, const char *sfx_path, int device_id, const bk
             const int re = swin_end(c, sb, c->stream);
             if (re == BK_ERR_INTERNAL) rc = re;
             clk.lap("window array finished");
-            if (clk.on && c->d_swin) fprintf(stderr, "biokanga_amd: window array for %.1f %% of the suffix array, %.2f GB, made behind the upload\n", 100.0 * c->swin_covered, c->swin_bytes / 1e9);
+            if (clk.on && c->image.swin.get()) fprintf(stderr, "biokanga_amd: window array for %.1f %% of the suffix array, %.2f GB, made behind the upload\n", 100.0 * c->swin_covered, c->swin_bytes / 1e9);
         }
     } else if (sent) {
-        sent = upload_file(d_sa, fd, sa_ofs, f.concat_len * f.el_size, device_id) == BK_OK;
+        sent = upload_file(d_sa.get(), fd, sa_ofs, f.concat_len * f.el_size, device_id) == BK_OK;
         clk.lap("upload suffix array");
-        if (sent) rc = adopt_device_image(c, d_seq, f.concat_len, d_sa, (int)f.el_size);
+        if (sent) rc = adopt_device_image(c, d_seq.get(), f.concat_len, d_sa.get(), (int)f.el_size);
         clk.lap("pack target, adopt");
     }
     ::close(fd);
-    cleanup();
+    d_seq.reset(); d_sa.reset();         // (the staged file image goes before finish_ctx allocates)
     if (!sent) { bk_ctx_destroy(c); return BK_ERR_INTERNAL; }
     if (rc) { bk_ctx_destroy(c); return rc; }
     rc = finish_ctx(c, ents.data(), (uint32_t)ents.size());
@@ -1093,52 +1100,41 @@ int bk_ctx_clone(bk_ctx **out, const bk_ctx *src, int device_id)
     c->ktab_is2 = src->ktab_is2;
     c->use_ktab2 = src->use_ktab2;
     c->grow_elem = src->grow_elem;
-    c->ix.ktab2_elem = src->ix.ktab2_elem;
     c->use_k3 = src->use_k3;
     c->sort_lists = src->sort_lists; c->sort_lists_set = src->sort_lists_set;
     c->grow_enabled = src->grow_enabled && src->grow_state.load() != 4; c->grow_after = src->grow_after; c->grow_wait = src->grow_wait;       // (a clone of a grown context has what it grew)
-    c->ktab_bytes = src->ktab_bytes;
-    c->nflag_bytes = src->nflag_bytes;
     c->use_ktab = src->use_ktab; c->k_req = src->k_req; c->use_k2 = src->use_k2; c->use_isa = src->use_isa; c->use_wave = src->use_wave; c->use_tgt2 = src->use_tgt2;
     c->ix.n = src->ix.n;
     c->ix.k = src->ix.k;
     c->ix.flag_shift = src->ix.flag_shift;
     c->ix.nflag_bytes = src->ix.nflag_bytes;
-    const uint64_t n = src->ix.n;
-    const uint64_t nblocks = src->n_tgt4_words / 4;
     bool ok = true;
-    auto dup = [&](auto *&dst, const auto *from, size_t bytes) {
-        if (!ok || !from) return;
-        void *p = nullptr;
-        if (dev_malloc(&p, bytes) != hipSuccess) { ok = false; rc = BK_ERR_MEM; return; }
-        dst = static_cast<std::remove_reference_t<decltype(dst)>>(p);
-        hipError_t e = c->device == src->device ? hipMemcpyAsync(p, from, bytes, hipMemcpyDeviceToDevice, c->stream)
-                                                : hipMemcpyPeerAsync(p, c->device, from, src->device, bytes, c->stream);
+    // a buffer of the source's size with the source's bytes (an empty source leaves the copy empty)
+    auto dup = [&](auto &dst, const auto &from) {
+        if (!ok || !from.get()) return;
+        if (dst.ensure(from.cap()) != hipSuccess) { ok = false; rc = BK_ERR_MEM; return; }
+        const size_t bytes = from.cap() * sizeof(*from.get());
+        hipError_t e = c->device == src->device ? hipMemcpyAsync(dst.get(), from.get(), bytes, hipMemcpyDeviceToDevice, c->stream)
+                                                : hipMemcpyPeerAsync(dst.get(), c->device, from.get(), src->device, bytes, c->stream);
         if (e != hipSuccess) { ok = false; rc = BK_ERR_INTERNAL; }
     };
-    dup(c->d_tgt4, src->d_tgt4, (size_t)src->n_tgt4_words * 8);
-    dup(c->d_sa_lo, src->d_sa_lo, (size_t)n * 4);
-    dup(c->d_sa_hi, src->d_sa_hi, (size_t)n);
-    dup(c->d_ktab, (const uint8_t *)src->d_ktab, src->ktab_bytes);
-    dup(c->d_ktab_hi, src->d_ktab_hi, (size_t)(((((1ULL << (2 * src->ix.k)) + 1) >> 16) + 2) * 8));
-    dup(c->d_k2, src->d_k2, (size_t)k2s_start(n, kK2Levels + 1) * 4);
-    for (int i = 0; i < kMoreKeys; i++) dup(c->d_kx[i], src->d_kx[i], (size_t)k2s_start(n, kK2Levels + 1) * 4);
-    dup(c->d_isa, src->d_isa, (size_t)n * 4);
-    dup(c->d_tgt2, src->d_tgt2, (size_t)nblocks * 16 + 64);
-    dup(c->d_tgt2s, src->d_tgt2s, (size_t)nblocks * 16 + 64);
-    dup(c->d_nflag, src->d_nflag, src->nflag_bytes);
+    ImageBufs &im = c->image;
+    const ImageBufs &sim = src->image;
+    dup(im.tgt4, sim.tgt4);
+    dup(im.sa_lo, sim.sa_lo);
+    dup(im.sa_hi, sim.sa_hi);
+    dup(im.ktab, sim.ktab);
+    dup(im.ktab_hi, sim.ktab_hi);
+    dup(im.k2, sim.k2);
+    for (int i = 0; i < kMoreKeys; i++) dup(im.kx[i], sim.kx[i]);
+    dup(im.isa, sim.isa);
+    dup(im.tgt2, sim.tgt2);
+    dup(im.tgt2s, sim.tgt2s);
+    dup(im.nflag, sim.nflag);
     c->use_swin = src->use_swin;                                      // (the window array is built here when the first batch asks for it)
     if (ok && hipStreamSynchronize(c->stream) != hipSuccess) { ok = false; rc = BK_ERR_INTERNAL; }
     if (!ok) { bk_ctx_destroy(c); return rc; }
-    c->ix.tgt4 = c->d_tgt4; c->ix.sa_lo = c->d_sa_lo; c->ix.sa_hi = c->d_sa_hi;
-    if (c->d_ktab) {
-        if (c->ktab64 && c->d_ktab_hi) { c->ix.ktab32 = (const uint32_t *)c->d_ktab; c->ix.ktab_hi = c->d_ktab_hi; }
-        else if (c->ktab64) c->ix.ktab64 = (const uint64_t *)c->d_ktab;
-        else if (c->ktab_is2) c->ix.ktab2 = (const uint2 *)c->d_ktab;
-        else c->ix.ktab32 = (const uint32_t *)c->d_ktab;
-    }
-    for (int i = 0; i < kMoreKeys; i++) c->ix.kx[i] = c->d_kx[i];
-    c->ix.k2 = c->d_k2; c->ix.isa = c->d_isa; c->ix.tgt2 = c->d_tgt2; c->ix.tgt2s = c->d_tgt2s; c->ix.nflag = c->d_nflag;
+    publish_index(c);
     clk.lap("index image copied from the first device");
     rc = setup_entries(c, src->entries.data(), (uint32_t)src->entries.size());
     if (rc) { bk_ctx_destroy(c); return rc; }
@@ -1150,16 +1146,12 @@ void bk_ctx_destroy(bk_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    grow_drop(c);
+    grow_drop(c);                         // (joins the worker: nothing writes the image from here on)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_dev(c->d_tgt4); free_dev(c->d_sa_lo); free_dev(c->d_sa_hi);
-    free_dev(c->d_snp_planes); free_dev(c->d_snp_tot); free_dev(c->d_ent_start); free_dev(c->d_ent_end); free_dev(c->d_ent_id); free_dev(c->d_id2idx); free_dev(c->d_ktab); free_dev(c->d_ktab_hi); free_dev(c->d_k2); free_dev(c->d_kx[0]); free_dev(c->d_kx[1]); free_dev(c->d_tgt2); free_dev(c->d_tgt2s); free_dev(c->d_nflag);
-    c->release_batch_buffers();           // everything grown on demand (bk_ctx::buf), while the device is current and the stream still there
-    free_dev(c->d_small);
-    free_dev(c->d_isa); free_dev(c->d_swin); free_dev(c->d_swmap); free_dev(c->d_seq_global);
-    free_dev(c->d_seq_counts); free_dev(c->d_ctr); free_dev(c->d_ctr_aux);
+    // every device buffer, while the device is current and the stream still there: image and small fixed buffers, then everything grown on demand (bk_ctx::buf)
+    c->release_image_buffers();
+    c->release_batch_buffers();
     if (c->h_small) (void)hipHostFree(c->h_small);
-    free_dev(c->d_ctl);
     for (void *&t : c->sam_text) if (t) { (void)hipHostFree(t); t = nullptr; }
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);

@@ -12,9 +12,9 @@ int bk_snp_reset(bk_ctx *c)
     if (!c) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)c->ix.n * 6 * sizeof(uint32_t);
-    if (!c->d_snp_planes) HIP_TRY(dev_malloc(&c->d_snp_planes, bytes));
-    if (!c->d_snp_tot) HIP_TRY(dev_malloc(&c->d_snp_tot, 4 * 8));
-    HIP_TRY(clear_dev(c->d_snp_planes, bytes, c->stream));
+    if (!c->fixed.snp_planes.get()) HIP_TRY(c->fixed.snp_planes.ensure((size_t)c->ix.n * 6));
+    if (!c->fixed.snp_tot.get()) HIP_TRY(c->fixed.snp_tot.ensure(4));
+    HIP_TRY(clear_dev(c->fixed.snp_planes.get(), bytes, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BK_OK;
 }
@@ -23,7 +23,7 @@ int bk_snp_pileup(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const u
                   uint64_t n_alns)
 {
     if (!c || (n_alns && (!bases || !offs || !lens || !alns || !nreads))) return BK_ERR_PARAMS;
-    if (!c->d_snp_planes) return BK_ERR_PARAMS;                      // bk_snp_reset() first
+    if (!c->fixed.snp_planes.get()) return BK_ERR_PARAMS;                      // bk_snp_reset() first
     if (!n_alns) return BK_OK;
     uint32_t max_id = 0;
     for (const auto &e : c->entries) max_id = std::max(max_id, e.entry_id);
@@ -45,7 +45,7 @@ int bk_snp_pileup(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const u
     HIP_TRY(hipMemcpyAsync(d_bases.get(), bases + x.lo, x.hi - x.lo, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_offs.get(), x.rel.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_alns.get(), alns, (size_t)n_alns * sizeof(bk_snp_aln), hipMemcpyHostToDevice, s));
-    launch_snp_pileup(c->ix, d_bases.get(), d_offs.get(), c->d_id2idx, d_alns.get(), n_alns, c->d_snp_planes, s);
+    launch_snp_pileup(c->ix, d_bases.get(), d_offs.get(), c->image.id2idx.get(), d_alns.get(), n_alns, c->fixed.snp_planes.get(), s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     return BK_OK;
@@ -54,10 +54,10 @@ int bk_snp_pileup(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const u
 int bk_snp_pileup_device(bk_ctx *c, const void *d_bases, const void *d_offs, uint32_t nreads, const void *d_alns, uint64_t n_alns, int sync)
 {
     if (!c || (n_alns && (!d_bases || !d_offs || !d_alns || !nreads))) return BK_ERR_PARAMS;
-    if (!c->d_snp_planes) return BK_ERR_PARAMS;
+    if (!c->fixed.snp_planes.get()) return BK_ERR_PARAMS;
     if (!n_alns) return BK_OK;
     HIP_TRY(hipSetDevice(c->device));
-    launch_snp_pileup(c->ix, (const uint8_t *)d_bases, (const uint64_t *)d_offs, c->d_id2idx, (const bk_snp_aln *)d_alns, n_alns, c->d_snp_planes, c->stream);
+    launch_snp_pileup(c->ix, (const uint8_t *)d_bases, (const uint64_t *)d_offs, c->image.id2idx.get(), (const bk_snp_aln *)d_alns, n_alns, c->fixed.snp_planes.get(), c->stream);
     HIP_TRY(hipGetLastError());
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
     return BK_OK;
@@ -65,7 +65,7 @@ int bk_snp_pileup_device(bk_ctx *c, const void *d_bases, const void *d_offs, uin
 
 int bk_snp_counts(bk_ctx *c, uint32_t chrom_id, uint32_t loci, uint32_t n, uint32_t *out)
 {
-    if (!c || !out || !c->d_snp_planes) return BK_ERR_PARAMS;
+    if (!c || !out || !c->fixed.snp_planes.get()) return BK_ERR_PARAMS;
     const bk_entry_info *ent = nullptr;
     for (const auto &e : c->entries) if (e.entry_id == chrom_id) { ent = &e; break; }
     if (!ent || (uint64_t)loci + n > ent->seq_len) return BK_ERR_PARAMS;
@@ -73,7 +73,7 @@ int bk_snp_counts(bk_ctx *c, uint32_t chrom_id, uint32_t loci, uint32_t n, uint3
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<uint32_t> d_out;
     HIP_TRY(d_out.ensure((size_t)n * 7));
-    launch_snp_gather(c->ix, c->d_snp_planes, ent->start_ofs + loci, n, d_out.get(), c->stream);
+    launch_snp_gather(c->ix, c->fixed.snp_planes.get(), ent->start_ofs + loci, n, d_out.get(), c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, d_out.get(), (size_t)n * 7 * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -82,7 +82,7 @@ int bk_snp_counts(bk_ctx *c, uint32_t chrom_id, uint32_t loci, uint32_t n, uint3
 
 int bk_snp_centroid_insts(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, uint32_t *num_insts)
 {
-    if (!c || !num_insts || min_reads < 1 || !c->d_snp_planes) return BK_ERR_PARAMS;
+    if (!c || !num_insts || min_reads < 1 || !c->fixed.snp_planes.get()) return BK_ERR_PARAMS;
     const bk_entry_info *ent = nullptr;
     for (const auto &e : c->entries) if (e.entry_id == chrom_id) { ent = &e; break; }
     if (!ent) return BK_ERR_PARAMS;
@@ -91,7 +91,7 @@ int bk_snp_centroid_insts(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, uint3
     HIP_TRY(d_hist.ensure(BK_SNP_CENTROIDS));
     std::vector<uint32_t> h(BK_SNP_CENTROIDS);
     HIP_TRY(hipMemsetAsync(d_hist.get(), 0, BK_SNP_CENTROIDS * 4, c->stream));
-    launch_snp_centroids(c->ix, c->d_snp_planes, ent->start_ofs, (uint32_t)ent->seq_len, (uint32_t)min_reads, d_hist.get(), c->stream);
+    launch_snp_centroids(c->ix, c->fixed.snp_planes.get(), ent->start_ofs, (uint32_t)ent->seq_len, (uint32_t)min_reads, d_hist.get(), c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h.data(), d_hist.get(), BK_SNP_CENTROIDS * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -103,7 +103,7 @@ int bk_snp_sites(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, double min_non
                  bk_snp_chrom *totals)
 {
     if (!c || !sites || !n_sites || !totals || min_reads < 1 || !(min_nonref_prop >= 0.0)) return BK_ERR_PARAMS;
-    if (!c->d_snp_planes) return BK_ERR_PARAMS;
+    if (!c->fixed.snp_planes.get()) return BK_ERR_PARAMS;
     const bk_entry_info *ent = nullptr;
     for (const auto &e : c->entries) if (e.entry_id == chrom_id) { ent = &e; break; }
     if (!ent) return BK_ERR_PARAMS;
@@ -114,13 +114,13 @@ int bk_snp_sites(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, double min_non
     unsigned long long h_tot[4] = {0, 0, 0, 0};
     uint32_t n = 0;
     for (;;) {                                                        // second pass only when the list outgrew its buffer
-        HIP_TRY(hipMemsetAsync(c->d_small, 0, 16 * 4, s));
-        HIP_TRY(hipMemsetAsync(c->d_snp_tot, 0, 4 * 8, s));
-        launch_snp_sites(c->ix, c->d_snp_planes, ent->start_ofs, (uint32_t)ent->seq_len, (uint32_t)min_reads, min_nonref_prop, d_sites.get(),
-                         (uint32_t)d_sites.cap(), c->d_small, c->d_snp_tot, s);
+        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
+        HIP_TRY(hipMemsetAsync(c->fixed.snp_tot.get(), 0, 4 * 8, s));
+        launch_snp_sites(c->ix, c->fixed.snp_planes.get(), ent->start_ofs, (uint32_t)ent->seq_len, (uint32_t)min_reads, min_nonref_prop, d_sites.get(),
+                         (uint32_t)d_sites.cap(), c->fixed.small.get(), c->fixed.snp_tot.get(), s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&n, c->d_small, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h_tot, c->d_snp_tot, sizeof(h_tot), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n, c->fixed.small.get(), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_tot, c->fixed.snp_tot.get(), sizeof(h_tot), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (n <= d_sites.cap()) break;
         HIP_TRY(d_sites.ensure(n));

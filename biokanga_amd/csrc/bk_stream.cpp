@@ -436,7 +436,7 @@ static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads,
     };
     if (e == hipSuccess) {
         e = alloc_slots();
-        if (e == hipErrorOutOfMemory && ctx->d_swin) {
+        if (e == hipErrorOutOfMemory && ctx->image.swin.get()) {
             // the context's window array (half of the HBM) goes before the pipeline is refused its buffers
             (void)hipGetLastError();
             for (Slot &sl : s->slots) {

@@ -134,13 +134,13 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->async_phases = value ? 1 : 0;
         return old;
     }
-    if (n == "swin_resident") return c->d_swin != nullptr ? 1 : 0;      // (read only: whether the window array is in HBM right now)
+    if (n == "swin_resident") return c->image.swin.get() != nullptr ? 1 : 0;      // (read only: whether the window array is in HBM right now)
     if (n == "use_swin") {
         int64_t old = c->use_swin;
         c->use_swin = value < 0 ? 0 : (value > 3 ? 3 : (int)value);
         c->swin_denied = false;
-        if (c->d_swin && (!c->use_swin || (c->use_swin == 3) != (c->d_swmap == nullptr))) {
-            if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (c->image.swin.get() && (!c->use_swin || (c->use_swin == 3) != (c->image.swmap.get() == nullptr))) {
+            if (c->stream) (void)hipStreamSynchronize(c->stream);      // (order: the stream that reads the array has ended before it is given back)
             drop_swin(c);
         }
         return old;
@@ -158,8 +158,8 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
     // (read only) what the window array occupies, what making it took, how much of the suffix array it holds
     if (n == "swin_mbytes") return (int64_t)(c->swin_bytes >> 20);
     if (n == "swin_setup_us") return (int64_t)(c->swin_setup_s * 1e6);
-    if (n == "swin_covered_ppm") return c->d_swin ? (int64_t)(c->swin_covered * 1e6) : 0;
-    if (n == "swin_core_lens") return c->d_swmap ? c->swin_w : 0;      // shortest | longest << 8 | levels << 16 of the core lengths its coverage was made for
+    if (n == "swin_covered_ppm") return c->image.swin.get() ? (int64_t)(c->swin_covered * 1e6) : 0;
+    if (n == "swin_core_lens") return c->image.swmap.get() ? c->swin_w : 0;      // shortest | longest << 8 | levels << 16 of the core lengths its coverage was made for
     if (n == "use_isa") {
         int64_t old = c->use_isa;
         c->use_isa = value ? 1 : 0;
