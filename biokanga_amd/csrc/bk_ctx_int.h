@@ -51,6 +51,7 @@ struct BatchBufs {
     DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
+    DevBuf<uint2> plan;                   // DevBatch::plan: the plan table (bk_plan_table.h; bk_engine.cpp, plan_table_for)
 };
 // the index image in HBM, one owner per allocation; bk::publish_index (bk_image.cpp) sets the pointers of DevIndex from them
 struct ImageBufs {
@@ -147,6 +148,13 @@ struct bk_ctx {
     bool force_rccl = false;                      // bk_seq_counts_allreduce goes through RCCL even on one device ("force_rccl")
     uint64_t rccl_allreduces = 0;                 // .. how many of this context's reductions went through RCCL, the ranks of the last one's communicator
     int rccl_ranks = 0;
+    // the plan table (buf.plan): what it was made for - the longest read, the configuration fields make_plan reads - and the pinned
+    // copy it is uploaded from (the host's own look-ups go there too).  Made again when a batch has a longer read or a field has changed.
+    uint2 *h_plan = nullptr;
+    size_t h_plan_cap = 0;
+    uint32_t plan_maxlen = 0;
+    int plan_key[4] = {-1, -1, -1, -1};   // max_subs, mm_delta, min_core_len, slides_per100
+    hipEvent_t ev_plan = nullptr;         // behind the last upload: the pinned copy is not written before it has been read
     // heavy path scratch (owned by buf.htab, buf.slot_epoch)
     bk::HeavyScratch hs{};
     int max_read_len = 500;

@@ -156,6 +156,9 @@ struct DevBatch {
     uint32_t n_reads;
     uint32_t nw;                // 4-bit words covered by an rd2 row (8 or 16), 0 without rd2
     uint32_t iv_cores;          // cores per strand the interval slots are numbered for (<= kMaxCoresFast: the most a read of this batch can have)
+    const uint2 *plan;          // the geometry of a read of every length in every phase (bk_plan_table.h): entry [phase * plan_stride + length];
+    uint32_t plan_stride;       //   rows are plan_stride entries apart, lengths 0 .. plan_stride - 1; null where a batch runs no kernel that reads it
+    uint32_t plan_n;            //   entries of a row this batch's reads can touch: its longest read + 1 (<= plan_stride; what a kernel stages in LDS)
 };
 
 // The counts of one AlignReads phase over a chunk of reads, in device memory: the phase loop's kernels size themselves by them, so

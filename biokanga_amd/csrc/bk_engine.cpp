@@ -6,6 +6,7 @@
 // Ownership: every buffer this file grows is a bk::DevBuf of bk_ctx::buf (bk_devbuf.h, bk_ctx_int.h) and is grown by one ensure_* function
 // here; a chunk's temporaries are local DevBufs, so an early return frees them.  Nothing here frees device memory by hand.
 #include "bk_engine_int.h"
+#include "bk_plan_table.h"
 
 namespace bk {
 int size_heavy_scratch(bk_ctx *c)
@@ -84,6 +85,51 @@ int ensure_slist(bk_ctx *c, uint64_t lanes, hipStream_t s)
     m.slist_stage.reset();
     HIP_TRY(m.slist.ensure(lanes));
     HIP_TRY(m.slist_stage.ensure(lanes + (kListStripes + 2) * 1024));
+    return BK_OK;
+}
+
+// The plan table (bk_plan_table.h) for reads of up to maxlen bases, in HBM and in its pinned copy: kept from batch to batch, made again
+// only when a batch has a longer read than the table covers or when one of the configuration fields the derivation reads differs from
+// what the table was made with (bk_ctx_set_params -> derive_cfg is their only writer; comparing the fields themselves leaves no setter
+// to forget).  A shorter batch reads the longer table.  The upload goes on the batch's stream and nothing waits for it; making the table
+// again first waits for the previous upload to have left the pinned copy, and growing it for the stream (ensure_slist's rule).  Those
+// waits and allocations belong to the blocking calls and to bk_ctx_reserve, which makes the table for its max_read_len as it sizes the
+// rest of the scratch: the call that only enqueues asks plan_table_covers and refuses a batch the table does not serve as it stands.
+// (The two early returns are unreachable through derive_cfg, which hands out mm_delta 1 or 2 and at most 9 slides per 100 bases - 180
+// cores at 2000 bases against the 1023 the packing holds; they keep a future parameter from becoming a division by zero or a
+// truncated field.)
+bool plan_table_covers(const bk_ctx *c, uint32_t maxlen)
+{
+    const int key[4] = {c->cfg.max_subs, c->cfg.mm_delta, c->cfg.min_core_len, c->cfg.slides_per100};
+    return c->buf.plan.get() != nullptr && maxlen <= c->plan_maxlen && std::equal(key, key + 4, c->plan_key);
+}
+
+int plan_table_for(bk_ctx *c, uint32_t maxlen, hipStream_t s)
+{
+    const int key[4] = {c->cfg.max_subs, c->cfg.mm_delta, c->cfg.min_core_len, c->cfg.slides_per100};
+    if (plan_table_covers(c, maxlen)) return BK_OK;
+    if (c->cfg.mm_delta < 1 || maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
+    const uint32_t cover = std::max(maxlen, std::equal(key, key + 4, c->plan_key) ? c->plan_maxlen : 0u);
+    const int rows = plan_table_rows(c->cfg, (int)cover);
+    if (rows > kMaxPhases + 1) return BK_ERR_INTERNAL;
+    const size_t n = (size_t)rows * (cover + 1);
+    if (!c->ev_plan) HIP_TRY(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(c->ev_plan));
+    c->plan_maxlen = 0;
+    if (n > c->h_plan_cap) {
+        if (c->h_plan) { (void)hipHostFree(c->h_plan); c->h_plan = nullptr; c->h_plan_cap = 0; }
+        HIP_TRY(hipHostMalloc(&c->h_plan, n * sizeof(uint2)));
+        c->h_plan_cap = n;
+    }
+    if (n > c->buf.plan.cap()) {
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(c->buf.plan.ensure(n));
+    }
+    if (!plan_table_fill(c->cfg, (int)cover, rows, c->h_plan)) return BK_ERR_INTERNAL;
+    HIP_TRY(hipMemcpyAsync(c->buf.plan.get(), c->h_plan, n * sizeof(uint2), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->ev_plan, s));
+    std::copy(key, key + 4, c->plan_key);
+    c->plan_maxlen = cover;
     return BK_OK;
 }
 
@@ -373,13 +419,16 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     // bounds of a read of up to maxlen bases: phases, cores per strand in each
     int max_phases = 0, cmax_bound[kMaxPhases + 1] = {0};
     bool cores_fit = true;
+    // (from the plan table, which holds make_plan / phase_params / core_offsets of every length and phase and is kept between batches)
+    { int rp = plan_table_for(c, maxlen, s); if (rp) return rp; }
+    b.plan = c->buf.plan.get();
+    b.plan_stride = c->plan_maxlen + 1;
+    b.plan_n = maxlen + 1;
     for (uint32_t len = 1; len <= maxlen; len++) {
-        const ReadPlan p = make_plan((int)len, c->cfg);
-        max_phases = std::max(max_phases, p.n_phases);
-        for (int ph = 0; ph < p.n_phases && ph <= kMaxPhases; ph++) {
-            int mm, cl, cd, dummy[1];
-            phase_params(p, c->cfg, ph, mm, cl, cd);
-            const int nc = core_offsets((int)len, cl, cd, p.max_slides, dummy, 0);
+        const int n_phases = plan_unpack(c->h_plan[len]).n_phases;
+        max_phases = std::max(max_phases, n_phases);
+        for (int ph = 0; ph < n_phases && ph <= kMaxPhases; ph++) {
+            const int nc = plan_unpack(c->h_plan[(size_t)ph * b.plan_stride + len]).nc;
             if (nc > kMaxCoresFast) cores_fit = false;
             cmax_bound[ph] = std::max(cmax_bound[ph], std::min(nc, (int)kMaxCoresFast));
         }
@@ -649,7 +698,8 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
         const bool plain = c->cfg.max_hits == 1 && !c->params.best_matches && !c->params.micro_indel_len && !c->params.splice_junct_len && !c->params.min_chimeric_len;
         const bool fits = ml >= 1 && ml <= 16u * (uint32_t)kNwLongest && nreads <= c->cap_reads && nreads <= c->chunk_reads && words_per_read(ml) <= c->cap_wpr &&
                           iv_cores_for(c, ml) <= c->cap_iv_cores && rd2w_for(ml) <= c->cap_rd2w &&
-                          (uint64_t)nreads * iv_cores_for(c, ml) * (c->cfg.align_strand == 0 ? 2u : 1u) <= c->buf.slist.cap() && (c->ix.isa != nullptr || c->hs.htab != nullptr);
+                          (uint64_t)nreads * iv_cores_for(c, ml) * (c->cfg.align_strand == 0 ? 2u : 1u) <= c->buf.slist.cap() && (c->ix.isa != nullptr || c->hs.htab != nullptr) &&
+                          plan_table_covers(c, ml);         // (made by bk_ctx_reserve; making it here would allocate and wait)
         const bool main_path = c->use_wave && c->cfg.heavy_thresh <= 100 && c->ix.k2 != nullptr && c->ix.tgt2 != nullptr && !c->debug && c->async_phases;
         if (!plain || !fits || !main_path) return BK_ERR_PARAMS;
     }

@@ -177,6 +177,8 @@ int size_heavy_scratch(bk_ctx *c);
 int ensure_batch_scratch(bk_ctx *c, uint32_t n_reads, uint32_t wpr, uint32_t rd2w = 0, uint32_t iv_cores = kMaxCoresFast);
 int ensure_sort_scratch(bk_ctx *c, uint32_t n, hipStream_t s);
 int ensure_slist(bk_ctx *c, uint64_t lanes, hipStream_t s);          // (waits for `s` before it frees)
+int plan_table_for(bk_ctx *c, uint32_t maxlen, hipStream_t s);       // the plan table (bk_plan_table.h) made or made again where it does not serve reads of maxlen bases; may wait for `s`
+bool plan_table_covers(const bk_ctx *c, uint32_t maxlen);            // .. whether it serves them as it stands
 inline int ensure_seg2(bk_ctx *c, uint32_t n) { HIP_TRY(c->buf.seg2.ensure(n)); return BK_OK; }      // second segments of a chunk, of a pair batch
 // host batches need not be contiguous in their `bases`: the extent lo .. hi the reads reference, their offsets relative to lo, the longest
 struct HostExtent {

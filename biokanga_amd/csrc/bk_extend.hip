@@ -4,6 +4,7 @@
 //   k_extend    lane per read for reads beyond the register-window families
 #include "bk_dev_window.h"
 #include "bk_dev_prof.h"
+#include "bk_plan_table.h"
 
 namespace bk {
 
@@ -139,6 +140,11 @@ __host__ __device__ constexpr bool flat_caches_first(bool wide, int bs, int slot
 __host__ __device__ constexpr bool flat_rows_in_lds(bool wide, int nw, int bs) { return false; }
 // .. but the result bytes of a pass stay at what that form left room for (the target starts of a pass's candidates take their place)
 __host__ __device__ constexpr bool flat_small_pass(bool wide, int nw, int bs) { return !wide && nw <= 8 && bs <= 256; }
+// The geometry of the block's reads comes from the plan table (bk_plan_table.h): this phase's row and the next one's (the hand-on asks how
+// many cores a read has there).  Reads of up to 256 bases: both rows are staged in LDS behind the dynamic arrays, at most 2 x 257 entries =
+// 4.1 KB (2 KB at 128 bases).  The longer families (reads of up to 512 bases: two rows are up to 8 KB) keep their LDS as it is and read
+// the table through the caches.
+__host__ __device__ constexpr bool flat_plan_in_lds(int nw) { return nw <= 16; }
 
 template <bool WIDE, int NW, int BS>
 __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBatch b, const uint32_t *__restrict__ act,
@@ -189,6 +195,9 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
     __shared__ uint32_t s_wsum[BS / 64];
     __shared__ uint32_t s_cnt[4], s_base[4], s_cmax;
     __shared__ unsigned long long s_ctr[3];
+    constexpr bool PLAN_LDS = flat_plan_in_lds(NW);
+    uint2 *s_plan = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(s_dyn) + (size_t)BS * slots_max * (cf ? 6 : 2));     // [2][b.plan_n] (when PLAN_LDS)
+    const uint2 *plan0 = PLAN_LDS ? s_plan : b.plan + (size_t)phase * b.plan_stride, *plan1 = PLAN_LDS ? s_plan + b.plan_n : plan0 + b.plan_stride;
     using EntT = typename FlatEntT<WIDE>::type;
     __shared__ EntT s_es[kLdsEntries], s_ee[kLdsEntries];              // entry table, when it is small enough
     const uint32_t t = threadIdx.x;
@@ -204,6 +213,15 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
     if (ent_lds && t < ix.n_ent) { es_v = ix.ent_start[t]; ee_v = ix.ent_end[t]; }
 
     const uint32_t a = blockIdx.x * blockDim.x + t;
+    // the read's number is asked for before the plan rows are staged, so that the barrier behind the staging waits for one trip to memory
+    // on which both travel, not for one in front of the chain act -> rmeta -> ..
+    uint32_t r_first = 0;
+    if (a < n_act) r_first = act[a];
+    if (PLAN_LDS) {
+        plan_stage(s_plan, b, phase, t, BS);
+        plan_stage(s_plan + b.plan_n, b, phase + 1, t, BS);
+        __syncthreads();
+    }
     const int s0 = cfg.align_strand == 2 ? 1 : 0, s1 = cfg.align_strand == 1 ? 0 : 1;
     // slot q of a read = (strand pass q / cmaxs, core q % cmaxs): the numbering does not depend on the read's own core count,
     // cores it does not have are empty slots
@@ -215,7 +233,7 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
     int len = 0, mm = 0, cl = 1, cd = 1, nc = 0, n_phases = 0;
     bool mine = false;              // this lane's read is resolved here
     if (a < n_act) {
-        r = act[a];
+        r = r_first;
         const uint32_t len_v = b.rmeta[r];
         const bool spec = !WIDE && slots_max <= SPEC;
         uint2 sv[SPEC];
@@ -237,11 +255,9 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
             rb00 = rp[0]; rb01 = rp[1]; rb10 = rp[2]; rb11 = rp[3];
         }
         len = (int)(len_v & kReadLenMask);
-        ReadPlan p = make_plan(len, cfg);
-        n_phases = p.n_phases;
-        int dummy[1];
-        phase_params(p, cfg, phase, mm, cl, cd);
-        nc = core_offsets(len, cl, cd, p.max_slides, dummy, 0);
+        const PlanGeo g = plan_lookup(plan0, b.plan_n, len);
+        n_phases = g.n_phases;
+        mm = g.mm; cl = g.cl; cd = g.cd; nc = g.nc;
         const bool fits = nc <= kMaxCoresFast && len <= 16 * NW && nc <= cmaxs;
         bool is_heavy = !fits;
         if (fits) {
@@ -581,10 +597,7 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
     if (mine) {
         rslt = classify(low_inst, low_mm, nxt, init, cfg.mm_delta, cfg.max_hits);
         if (rslt == BK_HR_NONE && phase + 1 < n_phases) {
-            ReadPlan p = make_plan(len, cfg);
-            int mm2, cl2, cd2, dummy[1];
-            phase_params(p, cfg, phase + 1, mm2, cl2, cd2);
-            int nc2 = core_offsets(len, cl2, cd2, p.max_slides, dummy, 0);
+            const int nc2 = plan_lookup(plan1, b.plan_n, len).nc;
             if (nc2 <= kMaxCoresFast) my_cmax = (uint32_t)nc2;
             dest = 1;
         }
@@ -676,6 +689,7 @@ void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, 
     unsigned blocks = (n_act_bound + (unsigned)bs - 1) / (unsigned)bs;
     if (slots_max < 1) slots_max = 1;
     size_t lds = (size_t)bs * slots_max * (flat_caches_first(wide, bs, slots_max) ? 6 : 2);
+    if (flat_plan_in_lds(nw)) lds += 2 * (size_t)b.plan_n * sizeof(uint2);      // this phase's row of the plan table and the next one's
     StripeSet out;
     out.cnt = stripe_cnt;
     for (int i = 0; i < 3; i++) out.stage[i] = stage[i];

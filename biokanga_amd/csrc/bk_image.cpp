@@ -75,6 +75,8 @@ int derive_cfg(bk_ctx *c)
     default: m += 4; g.slides_per100 = 6; break;
     }
     g.min_core_len = m;
+    // (mm_delta 1 or 2 and at most 9 slides per 100 bases: what the plan table's packing relies on - plan_fits, bk_plan_table.h; a wider
+    // range here is met by plan_table_for's error returns, not by a wrong table)
     // CAligner::Align, Aligner.cpp:341-356
     switch (p.pmode) {
     case 0: g.max_iter = 5000; break;
@@ -1154,6 +1156,8 @@ void bk_ctx_destroy(bk_ctx *c)
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (void *&t : c->sam_text) if (t) { (void)hipHostFree(t); t = nullptr; }
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
+    if (c->h_plan) (void)hipHostFree(c->h_plan);
+    if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
     if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);

@@ -2,6 +2,7 @@
 // (Aligner.cpp:9041-9063) + the first active list, from 1 byte/base reads or from packed 2 bit/base words; the checks of a packed
 // batch; the compaction of striped work lists; 4-bit rows for the reads a general-family kernel is handed.
 #include "bk_dev_util.h"
+#include "bk_plan_table.h"
 
 namespace bk {
 
@@ -331,6 +332,8 @@ __global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b,
     // TR: rows and result records leave through the wave's words of LDS (see the kernel's end): reads of up to 128 bases
     constexpr bool TR = NW == 8 && BK_PREP_TRANSPOSE;
     __shared__ uint4 s_tr[TR ? 4 : 1][TR ? 64 * (NW / 2) : 1];
+    extern __shared__ uint2 s_plan[];                               // phase 0's row of the plan table (bk_plan_table.h): b.plan_n <= 16 NW + 1 entries
+    plan_stage(s_plan, b, 0, threadIdx.x, 256);
     if (threadIdx.x == 0) { s_cnt = 0; s_cmax = 0; }
     __syncthreads();
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -429,12 +432,9 @@ __global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b,
         if (bad || num_ns > max_ns_seq) h.nar = BK_NAR_NS;
         has_n = bad || num_ns > 0;
         if (h.nar != BK_NAR_NS) {
-            ReadPlan p = make_plan(len, cfg);
-            if (p.n_phases > 0) {
-                int mm, cl, cd, ofs[1];
-                phase_params(p, cfg, 0, mm, cl, cd);
-                int nc = core_offsets(len, cl, cd, p.max_slides, ofs, 0);
-                if (nc <= kMaxCoresFast) my_cmax = (uint32_t)nc;
+            const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
+            if (g.n_phases > 0) {
+                if (g.nc <= kMaxCoresFast) my_cmax = (uint32_t)g.nc;
                 go = true;
             }
         }
@@ -662,21 +662,22 @@ void launch_prep(const DevAlignCfg &cfg, const DevBatch &b, uint32_t *act, uint3
         out.cnt = stripe_cnt;
         out.stage[0] = out.stage[1] = out.stage[2] = stage;
         out.cap = stripe_cap(blocks, 256);
+        const size_t plan_lds = (size_t)b.plan_n * sizeof(uint2);       // phase 0's row of the plan table
         if (packed) {
             // the exception list first tells every read how many N it holds (the N policy is decided in the fused kernel), and
             // afterwards writes the codes into 4-bit rows: existing ones, or - lean batches - rows made for just these reads
             launch_fill_u64(reinterpret_cast<unsigned long long *>(b.rmeta), ((uint64_t)b.n_reads + 1) / 2, 0ULL, s);      // (rmeta is allocated in whole 8-byte words)
             if (eblocks) hipLaunchKernelGGL(k_mark_exc, dim3(eblocks), dim3(256), 0, s, b);
-            if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, true>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-            else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, true>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-            else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, true>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-            else hipLaunchKernelGGL((k_prep_fused<kNwLongest, true>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
+            if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+            else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+            else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+            else hipLaunchKernelGGL((k_prep_fused<kNwLongest, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
             if (eblocks && b.rd2 != nullptr) hipLaunchKernelGGL(k_exc_rows, dim3(eblocks), dim3(256), 0, s, b);
             if (eblocks) hipLaunchKernelGGL(k_apply_exc, dim3(eblocks), dim3(256), 0, s, b);
-        } else if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, false>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-        else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, false>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-        else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, false>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
-        else hipLaunchKernelGGL((k_prep_fused<kNwLongest, false>), dim3(blocks), dim3(256), 0, s, cfg, b, out);
+        } else if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+        else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+        else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+        else hipLaunchKernelGGL((k_prep_fused<kNwLongest, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
         launch_compact(out, &act, &act_cnt, 1, cmax, s);
         return;
     }

@@ -6,6 +6,7 @@
 
 #include "bk_dev_k2.h"
 #include "bk_dev_prof.h"
+#include "bk_plan_table.h"
 
 namespace bk {
 
@@ -62,13 +63,19 @@ __global__ void __launch_bounds__(256) k_search(DevIndex ix, DevAlignCfg cfg, De
 // Pass A with ILP searches per lane, written stage by stage so that the loads of a stage (read row, k-mer table, second-level
 // keys) of all ILP searches are in flight together: item u of a lane is search number tid + u * (lanes of the grid), i.e. every u
 // maps neighbouring lanes to neighbouring searches.  Same records and work list for every ILP (order aside).
+// What a read's cores look like in this phase comes from the plan table (bk_plan_table.h): the phase's row is staged in LDS when the
+// block starts - at most kMaxReadLenAbs + 1 entries, 16 KB, beside a few words of static LDS, so every batch's row fits and no lane goes
+// to memory for it.  An item's (read, strand, core) comes from the block's cursor and reciprocals the launch passes (item_decode): no
+// lane divides by a runtime number.
 
 template <int ILP>
 __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg cfg, DevBatch b, const uint32_t *__restrict__ act,
                                                       const uint32_t *__restrict__ p_n_act, int phase, int cmax, int nstr, int lazy,
-                                                      StripeSet out)
+                                                      StripeSet out, ItemGeo ig)
 {
     __shared__ uint32_t s_cnt, s_base;
+    extern __shared__ uint2 s_plan[];                       // this phase's row of the plan table: b.plan_n entries
+    plan_stage(s_plan, b, phase, threadIdx.x, 256);         // (the first tile's barrier stands between these stores and the look-ups)
 #if defined(BK_PROF) && BK_PROF == 2
     PROF_BEGIN;
 #endif
@@ -78,7 +85,8 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
     const uint64_t total = (uint64_t)n_act * per_read;
     constexpr uint64_t stride = 256;                        // item u of a lane: tile start + lane + 256 u - neighbouring lanes, neighbouring searches
     const int k = ix.k;
-  for (uint64_t tile0 = (uint64_t)blockIdx.x * (256 * ILP); tile0 < total; tile0 += (uint64_t)gridDim.x * (256 * ILP)) {
+    ItemCursor cur = item_cursor((uint64_t)blockIdx.x * (256 * ILP), per_read);       // (block-uniform; ig's step is the grid's stride below)
+  for (uint64_t tile0 = (uint64_t)blockIdx.x * (256 * ILP); tile0 < total; tile0 += (uint64_t)gridDim.x * (256 * ILP), item_advance(cur, ig)) {
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
     bool on[ILP], push[ILP], have_code[ILP];
@@ -96,22 +104,20 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
     // stage 1: the item, its read row
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
-        const uint64_t tid = tile0 + threadIdx.x + (uint64_t)u * stride;
         on[u] = false; push[u] = false; have_code[u] = false; slot[u] = 0; p0[u] = 0; q2raw[u] = 0; first[u] = 0; nval[u] = 0; cl[u] = 1; lo[u] = hi[u] = 0;
         cix[u] = kNoIv32; cv[u] = make_uint2(0, kNoIv32); cached[u] = false;
-        if (tid < total) {
-            const uint64_t a = tid / per_read;
-            const uint32_t rem = (uint32_t)(tid - a * per_read);
-            const int si = (int)(rem / (uint32_t)cmax), c = (int)(rem % (uint32_t)cmax);
+        uint64_t a;
+        int si, c;
+        item_decode(cur, threadIdx.x + (uint32_t)u * (uint32_t)stride, ig, a, si, c);
+        if (a < n_act) {                                    // (the item's number is below n_act * per_read)
             const uint32_t r = act[a];
             const uint32_t meta = b.rmeta[r];
             const int len = (int)(meta & kReadLenMask);
             const int strand_c = cfg.align_strand == 2 ? 1 : si;
             if (b.iv32 != nullptr && c == 0 && phase > 0) cv[u] = b.iv32[(uint32_t)strand_c * b.n_reads + r];     // (requested with the length)
-            ReadPlan p = make_plan(len, cfg);
-            int mm, cd, dummy[1];
-            phase_params(p, cfg, phase, mm, cl[u], cd);
-            const int nc = core_offsets(len, cl[u], cd, p.max_slides, dummy, 0);
+            const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
+            const int cd = g.cd, nc = g.nc;
+            cl[u] = g.cl;
             if (c < nc && nc <= kMaxCoresFast) {
                 on[u] = true;
                 if (b.iv32 != nullptr && c == 0 && cl[u] >= k + kK2Bases) {
@@ -278,12 +284,14 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
 template <bool WIDE>
 __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, DevBatch b, int phase, int lazy,
                                                   const uint32_t *__restrict__ list, const uint32_t *__restrict__ sorted, uint32_t n_sorted,
-                                                  const uint32_t *__restrict__ p_n_list)
+                                                  const uint32_t *__restrict__ p_n_list, SlotGeo sg)
 {
     // the work list's length lives in device memory; its first min(length, n_sorted) items are taken from `sorted` (the grouped copy:
     // the launch had to size the sort before the length was known), the others from the list as pass A left it - the order of the
     // items never changes a result
     __shared__ uint64_t s_lv[kK2Levels + 1];                // where the sampled levels of the keys start (k2s_start)
+    extern __shared__ uint2 s_plan[];                       // this phase's row of the plan table, as in pass A: every batch's row fits in LDS
+    plan_stage(s_plan, b, phase, threadIdx.x, 256);
     if (threadIdx.x <= (unsigned)kK2Levels) s_lv[threadIdx.x] = threadIdx.x ? k2s_start(ix.n, (int)threadIdx.x) : 0;
     __syncthreads();
     const uint32_t n_list = *p_n_list;
@@ -295,14 +303,16 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
     unsigned long long d_k2 = 0, d_deep = 0, d_sa = 0;
     struct Fin { unsigned long long &a, &b, &c; DevBatch &bb; __device__ ~Fin() { if (a + b) atomicAdd(&bb.ctr[ctr_stripe() + 5], a + b); if (c) atomicAdd(&bb.ctr[ctr_stripe() + 6], c); } } fin{d_k2, d_deep, d_sa, b};
 #endif
-    const uint64_t slot = i < n_grouped ? sorted[i] : list[i];
-    const uint32_t r = b.act[(uint32_t)(slot % b.iv_stride)], sc = (uint32_t)(slot / b.iv_stride);
-    const int strand = (int)(sc / b.iv_cores), c = (int)(sc % b.iv_cores);
+    const uint32_t slot32 = i < n_grouped ? sorted[i] : list[i];
+    const uint64_t slot = slot32;
+    uint32_t a;
+    int strand, c;
+    slot_decode(slot32, sg, a, strand, c);                  // (reciprocals of iv_stride and iv_cores from the launch)
+    const uint32_t r = b.act[a];
     const uint32_t meta = b.rmeta[r];
     const int len = (int)(meta & kReadLenMask);
-    ReadPlan p = make_plan(len, cfg);
-    int mm, cl, cd;
-    phase_params(p, cfg, phase, mm, cl, cd);
+    const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
+    const int cl = g.cl, cd = g.cd;
     const int my_ofs = c * cd < len - cl ? c * cd : len - cl;
     const RdRow rdw = read_row(b, r, strand, (meta & kReadHasN) != 0);
     uint64_t first;
@@ -457,7 +467,10 @@ void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
     out.cnt = stripe_cnt;
     out.stage[0] = out.stage[1] = out.stage[2] = stage;
     out.cap = stripe_cap((unsigned)tiles, (unsigned)per);             // (stripes go by tile number)
-    hipLaunchKernelGGL(k_search_a_ilp<2>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, act, p_n_act, phase, cmax, nstr, lazy, out);
+    static_assert(256 * ilp <= (int)kItemMaxLaneOfs, "a lane's offset within a tile must stay in item_decode's range");
+    const ItemGeo ig = item_geo_make((uint32_t)(cmax * nstr), (uint32_t)cmax, (uint64_t)blocks * per);
+    const size_t lds = (size_t)b.plan_n * sizeof(uint2);           // the phase's row of the plan table
+    hipLaunchKernelGGL(k_search_a_ilp<ilp>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, act, p_n_act, phase, cmax, nstr, lazy, out, ig);
     launch_compact(out, &list, &list_cnt, 1, nullptr, s);
 }
 
@@ -467,8 +480,10 @@ void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
 {
     if (!n_bound) return;
     unsigned blocks = (unsigned)std::min<uint64_t>((n_bound + 255) / 256, 32768);
-    if (ix.sa_hi) hipLaunchKernelGGL(k_search_b<true>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list);
-    else hipLaunchKernelGGL(k_search_b<false>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list);
+    const SlotGeo sg = slot_geo_make(b.iv_stride, b.iv_cores);
+    const size_t lds = (size_t)b.plan_n * sizeof(uint2);
+    if (ix.sa_hi) hipLaunchKernelGGL(k_search_b<true>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg);
+    else hipLaunchKernelGGL(k_search_b<false>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg);
 }
 
 // the interval records of the slots a phase can use - [strand][core][position in the active list] for every core below cmax - set

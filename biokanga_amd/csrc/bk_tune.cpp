@@ -26,6 +26,11 @@ int bk_ctx_reserve(bk_ctx *c, uint32_t max_batch_reads, uint32_t max_read_len)
     }
     if (c->sort_lists) { rc = ensure_sort_scratch(c, n, c->stream); if (rc) return rc; }      // (grown when a phase's list is longer)
     if (c->use_wave && c->ix.isa == nullptr) { rc = size_heavy_scratch(c); if (rc) return rc; }     // hash-set dedupe of the wave kernel
+    // the plan table for reads of up to max_read_len bases under the parameters as they stand, in HBM when the call returns: a batch on
+    // any stream may read it, and the call that only enqueues never makes it
+    rc = plan_table_for(c, max_read_len, c->stream);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BK_OK;
 }
 

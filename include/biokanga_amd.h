@@ -183,7 +183,8 @@ int  bk_ctx_clone(bk_ctx **out, const bk_ctx *src, int device_id);
 void bk_ctx_destroy(bk_ctx *ctx);
 
 /* Sizes the context's batch scratch (read rows, interval records, work lists, sort buffers) for batches of up to max_batch_reads reads
- * of up to max_read_len bases NOW, so that no allocation is left for the first batch to pay inside T_align - the reference sizes its
+ * of up to max_read_len bases NOW, and makes the table of the reads' core geometry per length under the parameters as they stand, so that
+ * no allocation is left for the first batch to pay inside T_align - the reference sizes its
  * per-thread scratch before its workers start, too (CAligner::LocateCoredApprox, Aligner.cpp:8771-8790).  Optional for the blocking
  * calls and the pipeline (batches grow the scratch on demand), required by bk_align_batch_device_async. */
 int  bk_ctx_reserve(bk_ctx *ctx, uint32_t max_batch_reads, uint32_t max_read_len);
@@ -258,8 +259,10 @@ int  bk_align_batch_device(bk_ctx *ctx, const void *d_bases, const void *d_offs,
  * one behind an event recorded there) sees the results without the host ever waiting: the counts the phases produce - reads still
  * unaligned, work items, reads for the wave kernel - stay in device memory and the kernels size themselves by them
  * (the reference's workers never leave their loop either, Aligner.cpp:8943-9527).
- * Needs: the scratch in place for batches of this size and read length (bk_ctx_reserve), max_read_len >= the longest read of the
- * batch (the kernel family is picked by it; a longer read is reported by the NEXT call as BK_ERR_PARAMS), reads of at most 512
+ * Needs: the scratch in place for batches of this size and read length (bk_ctx_reserve - called again after bk_ctx_set_params has changed
+ * -s / -e / -M: the geometry table it makes goes by them), max_read_len >= the longest read of the
+ * batch (the kernel family is picked by it; a longer read is reported by the NEXT call as BK_ERR_PARAMS - its records are not to be
+ * used: the search gave it the core geometry of a read of max_read_len bases), reads of at most 512
  * bases, the default result form (no multi-loci lists, -a / -A / -c, -N), one batch of a context in flight per stream - the
  * scratch belongs to the context.  Otherwise BK_ERR_PARAMS before anything is launched: use the blocking call. */
 int  bk_align_batch_device_async(bk_ctx *ctx, const void *d_bases, const void *d_offs, const void *d_lens,
