@@ -147,10 +147,18 @@ def devtest_lib():
                        ("bkdt_window2i", [i32, i32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp]),
                        ("bkdt_window_rare", [i32, vp, u32, i32, vp, vp, vp, u32, vp, vp, vp, vp]),
                        ("bkdt_adaptive_trim", [i32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]),
-                       ("bkdt_pe_window", [i32, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp])):
+                       ("bkdt_pe_window", [i32, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+                       ("bkdt_search_bits", [vp, vp, vp, vp, u32, vp]),
+                       ("bkdt_search_cmp", [vp, vp, vp, vp, u32, vp]),
+                       ("bkdt_search_ktab", [vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, i32, vp, u32, vp]),
+                       ("bkdt_search_core", [vp, vp, vp, vp, vp, ctypes.c_uint64, i32, vp, vp, vp, u32, vp]),
+                       ("bkdt_search_k2", [vp, vp, ctypes.c_uint64, vp, u32, vp]),
+                       ("bkdt_search_entries", [vp, vp, vp, u32, vp, vp, u32, vp])):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
+    lib.bkdt_k2_layout.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    lib.bkdt_k2_layout.restype = None
     c = (u32 * 4)()
     lib.bkdt_consts(c)
     lib.kLdsSet, lib.kLdsSetFill, lib.kLdsEmpty, lib.kTombBit = (int(x) for x in c)

@@ -1,11 +1,13 @@
-// devtest.hip - test-only kernels around the device helpers of biokanga_amd/csrc (bk_dev_sets.h, bk_dev_window.h, bk_dev_trim.h), included as
-// they stand.  Built as biokanga_amd/lib/libbk_devtest.so (csrc/Makefile); tests/helpers.py devtest_lib() loads it.  Every launcher takes raw
+// devtest.hip - test-only kernels around the device helpers of biokanga_amd/csrc (bk_dev_sets.h, bk_dev_window.h, bk_dev_trim.h, and the search
+// primitives of bk_dev_util.h and bk_dev_k2.h), included as they stand.  Built as biokanga_amd/lib/libbk_devtest.so (csrc/Makefile); tests/helpers.py devtest_lib() loads it.  Every launcher takes raw
 // device pointers, launches on the null stream, synchronises and returns the hipError_t.  The helpers' probe loops end only at a free
 // slot: the caller keeps an LDS set within kLdsSetFill keys and an HBM table at most half full (tombstones counted), epochs in
 // [1, kTombBit).
 #include "../../biokanga_amd/csrc/bk_dev_sets.h"
 #include "../../biokanga_amd/csrc/bk_dev_window.h"
 #include "../../biokanga_amd/csrc/bk_dev_trim.h"
+#include "../../biokanga_amd/csrc/bk_dev_k2.h"
+#include "dev_search_eval.h"
 
 using namespace bk;
 
@@ -148,6 +150,42 @@ __global__ void __launch_bounds__(64) k_pe_window(const uint64_t *__restrict__ r
     }
 }
 
+// the search primitives (tests/test_gpu_dev_search.py): one case per lane - dev_search_eval.h turns a case into the call of the function under
+// test, the same text the CPU twin runs - neighbouring lanes with other functions, lengths, offsets and caps, so the loops diverge inside a wave
+__global__ void __launch_bounds__(64) k_search_bits(bkt::CtxA x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_a(x, cs[i]);
+}
+__global__ void __launch_bounds__(64) k_search_cmp(bkt::CtxB x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_b(x, cs[i]);
+}
+__global__ void __launch_bounds__(64) k_search_ktab(bkt::CtxC x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_c(x, cs[i]);
+}
+__global__ void __launch_bounds__(64) k_search_core(bkt::CtxD x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_d(x, cs[i]);
+}
+__global__ void __launch_bounds__(64) k_search_k2(bkt::CtxE x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_e(x, cs[i]);
+}
+// the entry table goes to LDS as in the kernels that look entries up (every lane of the block reaches lds_entries_load's barrier)
+__global__ void __launch_bounds__(64) k_find_entry(bkt::CtxF x, const bkt::Case *__restrict__ cs, uint32_t n, bkt::Res *__restrict__ out)
+{
+    __shared__ LdsEntries le;
+    lds_entries_load(le, x.ix);
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) out[i] = bkt::eval_f(x, le, cs[i], i);
+}
+
 int finish()
 {
     hipError_t e = hipGetLastError();
@@ -245,6 +283,74 @@ int bkdt_pe_window(int atw, const uint64_t *rows, uint32_t row_words, const int 
     else if (atw == 8) hipLaunchKernelGGL((k_pe_window<8>), grid, block, 0, 0, rows, row_words, len, t, tgt4, max_mm, min_put, order, n, key_out, t5, t3, ok_out, mm_out);
     else hipLaunchKernelGGL((k_pe_window<32>), grid, block, 0, 0, rows, row_words, len, t, tgt4, max_mm, min_put, order, n, key_out, t5, t3, ok_out, mm_out);
     return finish();
+}
+
+// ---- the search primitives.  cases: n records of bkt::Case, out: n of bkt::Res (dev_search_eval.h says what a case's fields mean per group).
+// Every array is as long as the CPU twin's (tests/cpp/dev_search_host.cpp `dump`), its padding words included.
+int bkdt_search_bits(const uint64_t *w, const uint64_t *rd4, const uint64_t *rd2, const void *cases, uint32_t n, void *out)
+{
+    if (n == 0) return 0;
+    const bkt::CtxA x{w, rd4, rd2};
+    hipLaunchKernelGGL(k_search_bits, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+int bkdt_search_cmp(const uint64_t *rd4, const uint64_t *rd2, const uint64_t *tgt4, const void *cases, uint32_t n, void *out)
+{
+    if (n == 0) return 0;
+    const bkt::CtxB x{rd4, rd2, tgt4};
+    hipLaunchKernelGGL(k_search_cmp, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+// one table of order k (4^k + 1 entries) in its four forms - 32-bit starts, 64-bit starts, ktab_hi + offsets, {start, anything} pairs - each
+// under a DevIndex of its own with everything else zero, and the index without a table
+int bkdt_search_ktab(const uint32_t *tab32, const uint64_t *tab64, const uint64_t *pk_hi, const uint32_t *pk_lo, const void *tab2, const uint32_t *sa_lo,
+                     const uint8_t *sa_hi, uint64_t n_index, int k, const void *cases, uint32_t n, void *out)
+{
+    if (n == 0) return 0;
+    bkt::CtxC x;
+    bkt::index_views(x, tab32, tab64, pk_hi, pk_lo, (const uint2 *)tab2, sa_lo, sa_hi, n_index, k);
+    hipLaunchKernelGGL(k_search_ktab, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+// tgt4 is followed by sequence-end words; tab32 or tab64 (or neither, k = 0)
+int bkdt_search_core(const uint64_t *tgt4, const uint32_t *sa_lo, const uint8_t *sa_hi, const uint32_t *tab32, const uint64_t *tab64, uint64_t n_index, int k,
+                     const uint64_t *rd4, const uint64_t *rd2, const void *cases, uint32_t n, void *out)
+{
+    if (n == 0) return 0;
+    bkt::CtxD x;
+    bkt::index_search(x, tgt4, sa_lo, sa_hi, tab32, tab64, n_index, k, rd4, rd2);
+    hipLaunchKernelGGL(k_search_core, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+// k2: the n_keys keys and their sampled levels, k2s_start(n_keys, kK2Levels + 1) words
+int bkdt_search_k2(const uint64_t *tgt4, const uint32_t *k2, uint64_t n_keys, const void *cases, uint32_t n, void *out)
+{
+    if (n == 0) return 0;
+    bkt::CtxE x;
+    bkt::k2_ctx(x, tgt4, k2, n_keys);
+    hipLaunchKernelGGL(k_search_k2, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+// hits: n records of bk_hit, where write_result puts case i's record
+int bkdt_search_entries(const uint64_t *ent_start, const uint64_t *ent_end, const uint32_t *ent_id, uint32_t n_ent, void *hits, const void *cases, uint32_t n,
+                        void *out)
+{
+    if (n == 0) return 0;
+    bkt::CtxF x;
+    bkt::index_entries(x, ent_start, ent_end, ent_id, n_ent, (bk_hit *)hits);
+    hipLaunchKernelGGL(k_find_entry, dim3((n + 63) / 64), dim3(64), 0, 0, x, (const bkt::Case *)cases, n, (bkt::Res *)out);
+    return finish();
+}
+
+// {kK2Levels, words of a key array of n keys with its levels}
+void bkdt_k2_layout(uint64_t n, uint64_t *out2)
+{
+    out2[0] = kK2Levels; out2[1] = k2s_start(n, kK2Levels + 1);
 }
 
 }  // extern "C"
