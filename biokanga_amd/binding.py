@@ -14,7 +14,7 @@ EXPORTED_SYMBOLS = [
     "bk_version", "bk_strerror", "bk_device_count", "bk_ctx_create", "bk_ctx_create_from_device",
     "bk_ctx_clone", "bk_ctx_destroy", "bk_ctx_set_params", "bk_ctx_tune", "bk_num_entries", "bk_get_entry",
     "bk_dataset_name", "bk_concat_len", "bk_sfx_el_size", "bk_min_core_len", "bk_align_batch",
-    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
+    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_site_octamers", "bk_site_octamers_device", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
     "bk_host_alloc", "bk_host_free", "bk_stream_create", "bk_stream_submit", "bk_stream_wait", "bk_stream_batch_loci",
     "bk_stream_batch_seg2", "bk_stream_release", "bk_stream_drain", "bk_stream_get_stats", "bk_stream_destroy",
     "bk_packed_words", "bk_pack_reads", "bk_align_batch_packed", "bk_stream_submit_packed", "bk_sam_format", "bk_batch_loci_trims", "bk_stream_batch_loci_trims", "bk_stream_submit_device", "bk_sam_prepare", "bk_sam_prep_free",
@@ -66,6 +66,9 @@ SNP_ALN_DTYPE = np.dtype([("read_idx", "<u4"), ("chrom_id", "<u4"), ("loci", "<u
 assert SNP_ALN_DTYPE.itemsize == 20
 SNP_SITE_DTYPE = np.dtype([("loci", "<u4"), ("num_ref", "<u4"), ("non_ref", "<u4", (5,)), ("win_mismatches", "<u4"), ("win_matches", "<u4"), ("ref_base", "<u4")])
 assert SNP_SITE_DTYPE.itemsize == 40
+SITE_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("match_loci", "<u4"), ("match_len", "<u2"), ("strand", "u1"), ("_r", "u1")])
+SITE_RES_DTYPE = np.dtype([("codes", "<u4"), ("site", "<u4")])
+assert SITE_REQ_DTYPE.itemsize == 12 and SITE_RES_DTYPE.itemsize == 8
 
 ENTRY_DTYPE = np.dtype([("entry_id", "<u4"), ("seq_len", "<u4"), ("start_ofs", "<u8"), ("end_ofs", "<u8"),
                         ("name", "S81"), ("_pad", "S7")])
@@ -222,6 +225,10 @@ def load_library():
     lib.bk_snp_counts.restype = i32
     lib.bk_snp_sites.argtypes = [vp, u32, i32, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), vp]
     lib.bk_snp_sites.restype = i32
+    lib.bk_site_octamers.argtypes = [vp, vp, u64, i32, vp]
+    lib.bk_site_octamers.restype = i32
+    lib.bk_site_octamers_device.argtypes = [vp, vp, u64, i32, vp, i32]
+    lib.bk_site_octamers_device.restype = i32
     lib.bk_seq_counts.argtypes = [vp, vp, u32, i32]
     lib.bk_seq_counts.restype = i32
     lib.bk_seq_counts_allreduce.argtypes = [ctypes.POINTER(vp), i32, vp, u32, i32]
@@ -603,6 +610,21 @@ class Aligner:
             return np.zeros(0, dtype=SNP_SITE_DTYPE), tot
         raw = np.ctypeslib.as_array(ctypes.cast(ps, ctypes.POINTER(ctypes.c_uint8)), shape=(n.value * SNP_SITE_DTYPE.itemsize,))
         return raw.view(SNP_SITE_DTYPE).copy(), tot
+
+    def site_octamers(self, reqs, rel_ofs):
+        """start-site octamers of SITE_REQ_DTYPE alignments (CAligner::ProcessSiteProbabilites' gather): SITE_RES_DTYPE, one per request"""
+        reqs = np.ascontiguousarray(reqs, dtype=SITE_REQ_DTYPE)
+        out = np.zeros(len(reqs), dtype=SITE_RES_DTYPE)
+        rc = self.lib.bk_site_octamers(self.h, reqs.ctypes.data, len(reqs), int(rel_ofs), out.ctypes.data)
+        if rc:
+            raise BkError(rc, "bk_site_octamers")
+        return out
+
+    def site_octamers_device(self, d_reqs_ptr, n, rel_ofs, d_out_ptr, sync=True):
+        """site_octamers on SITE_REQ_DTYPE records already in HBM, SITE_RES_DTYPE results left there (raw device pointers)"""
+        rc = self.lib.bk_site_octamers_device(self.h, d_reqs_ptr, n, int(rel_ofs), d_out_ptr, 1 if sync else 0)
+        if rc:
+            raise BkError(rc, "bk_site_octamers_device")
 
     def pair(self, bases, offs, lens, hits, pe, seg2=None):
         """PE association in place on `hits` (PE1/PE2 interleaved; the output of align() for the same reads).  seg2 = batch_seg2() of that

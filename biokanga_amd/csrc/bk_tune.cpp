@@ -77,6 +77,12 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->chunk_reads = (uint32_t)value;
         return old;
     }
+    if (n == "site_chunk") {               // requests bk_site_octamers stages at a time
+        int64_t old = (int64_t)c->site_chunk;
+        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
+        c->site_chunk = (uint64_t)value;
+        return old;
+    }
     if (n == "kmer_bits" || n == "use_ktab") {
         int64_t old = n == "use_ktab" ? c->use_ktab : c->ix.k;
         if (n == "use_ktab") c->use_ktab = value ? 1 : 0;

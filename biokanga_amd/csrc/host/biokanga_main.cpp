@@ -8,7 +8,7 @@
 //   biokanga index -i genome.fa[.gz] [-i more.fa] -o genome.sfx -r name [-l minseqlen] [-d descr] [-t title] [-T threads] [--device n]
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
-//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-T host threads] [-F logfile] [--device n | --devices 0-7]
+//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-T host threads] [-F logfile] [--device n | --devices 0-7]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -48,6 +48,7 @@
 #include "multi_assign.h"
 #include "post_filters.h"
 #include "snp.h"
+#include "site_prefs.h"
 #include "read_loader.h"
 #include "contaminants.h"
 #include "report.h"
@@ -213,6 +214,8 @@ struct AlignOpts {
     bk_pe_params PE{};
     bk_align_params P{};
     SnpOpts snp;
+    std::string site_prefs_path;           // -8: start-site octamer preferences into this file (empty: none)
+    int site_prefs_ofs = -4;               // -9, cDfltRelSiteStartOfs
     std::vector<regex_t> re_excl, re_incl;
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
@@ -334,6 +337,17 @@ int read_align_opts(Args &a, AlignOpts &o)
     if (a.has("O") && o.fmt == 6) {                 // kanga.cpp:1015-1021
         diag("Error: Output induced substitution mode '-O<file>' not available in '-M6' output mode\n");
         return 1;
+    }
+    // -8 / -9 start-site octamer preferences (kanga.cpp:1029-1043)
+    o.site_prefs_ofs = a.has("9") ? a.num("9", -4) : -4;
+    if (abs(o.site_prefs_ofs) > BK_SITE_MAX_OFS) {
+        diag("Error: offset read start sites '-9%d' when processing site octamer preferencing must be in range -100..100\n", o.site_prefs_ofs);
+        return 1;
+    }
+    if (a.has("8")) {
+        o.site_prefs_path = a.str("8");
+        while (!o.site_prefs_path.empty() && (o.site_prefs_path.front() == '"' || o.site_prefs_path.front() == '\'')) o.site_prefs_path.erase(0, 1);      // CUtility::TrimQuotes
+        while (!o.site_prefs_path.empty() && (o.site_prefs_path.back() == '"' || o.site_prefs_path.back() == '\'')) o.site_prefs_path.pop_back();
     }
     o.min_len = a.num("l", 50), o.max_len = a.num("L", 500);
     o.trim5 = a.num("y", 0), o.trim3 = a.num("Y", 0);
@@ -832,8 +846,9 @@ int cmd_align(int argc, char **argv, int first)
         {"quality", "g"}, {"device", "device"}, {"devices", "devices"}, {"window-array", "window-array"}, {"index-image", "index-image"}, {"rptsamseqsthres", "4"}, {"pair", "u"}, {"pairminlen", "d"}, {"pairmaxlen", "D"},
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
-        {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H", "EXN", a, err)) {
+        {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H89", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
@@ -864,6 +879,17 @@ int cmd_align(int argc, char **argv, int first)
         contam_trims.keep = true;
     }
     ContamTrimming *const ct = with_contam ? &contam_trims : nullptr;
+    if (!o.site_prefs_path.empty()) {               // (parameter lines, kanga.cpp:1290-1293)
+        char line[4300];
+        snprintf(line, sizeof(line), "Offset read start sites when processing site octamer preferencing: %d\nAligned read octamer site preferencing into this file: '%s'\n",
+                 o.site_prefs_ofs, o.site_prefs_path.c_str());
+        fputs(line, stdout);
+        if (g_logfile) fputs(line, g_logfile);
+        OutBuf sp_file;                             // the reference creates the file before it loads anything (an empty one stays when no read is accepted)
+        sp_file.open(o.site_prefs_path.c_str());
+        if (sp_file.fd < 0) { diag("Fatal: unable to create '%s'", o.site_prefs_path.c_str()); return 1; }
+        sp_file.close();
+    }
 
     // index images travel to the devices (one loader thread each) while this thread parses the reads: the two longest serial steps
     // of a run overlap (the reference loads its reads in the background of the alignment instead, Aligner.cpp:4820-4860)
@@ -1263,13 +1289,51 @@ int cmd_align(int argc, char **argv, int first)
     }
 
     // SortReadHits(eRSMHitMatch): index in load (ReadID) order -> reference order
+    std::vector<uint32_t> order;
+    // -8: CAligner::ProcessSiteProbabilites, called between ReportAlignStats - which leaves the reads sorted - and the writers
+    // (Aligner.cpp:706), when reads were accepted.  The visited reads' Seg[0] as it stands (MatchLoci / MatchLen, not the flank-trimmed
+    // start) goes to the first device, which gathers the eight target bases of every start site; the sequential rest is site_prefs.h.
+    bk::SitePrefs site_prefs;
+    const bool with_site_prefs = !o.site_prefs_path.empty() && nar[1] > 0;
+    if (with_site_prefs) {
+        sorted_order(order);
+        diag("Processing for alignment site probabilities...");
+        HostClock clk;
+        // (by all threads: a stretch of the sorted order each - counted, placed by a prefix sum, then filled)
+        const int nt = std::max(1, o.nthreads);
+        auto visited = [&](uint32_t i) { return hits[i].nar == BK_NAR_ACCEPTED && !has_seg2(i); };
+        std::vector<size_t> first((size_t)nt + 1, 0);
+        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) { size_t c = 0; for (size_t k = lo; k < hi; k++) c += visited(order[k]); first[(size_t)t + 1] = c; });
+        for (int t = 0; t < nt; t++) first[(size_t)t + 1] += first[(size_t)t];
+        bk::RawVec<bk_site_req> reqs(first[(size_t)nt]);
+        bk::RawVec<uint32_t> rec_of(first[(size_t)nt]);
+        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
+            size_t at = first[(size_t)t];
+            for (size_t k = lo; k < hi; k++) {
+                const uint32_t i = order[k];
+                if (!visited(i)) continue;
+                const bk_hit &h = hits[i];
+                reqs[at] = bk_site_req{h.chrom_id, h.match_loci, h.match_len, h.strand, 0};
+                rec_of[at++] = i;
+            }
+        });
+        bk::RawVec<bk_site_res> res(reqs.size());
+        clk.lap("site requests made");
+        const int sprc = bk_site_octamers(ctx, reqs.data(), reqs.size(), o.site_prefs_ofs, res.data());
+        if (sprc) { diag("Fatal: the start-site octamer gather failed: %s", bk_strerror(sprc)); destroy_ctxs(); return 1; }
+        clk.lap("site octamers gathered (device)");
+        bk::site_prefs_pass(reqs.data(), res.data(), rec_of.data(), reqs.size(), nr, site_prefs);
+        bk::site_prefs_scale(site_prefs);
+        clk.lap("site preferences counted and scaled");
+        diag("Completed alignment site probabilities");
+    }
     diag("Reporting of aligned result set started...");
     diag("Sorting alignments by ascending chrom.loci");
-    std::vector<uint32_t> order;
-    sorted_order(order);
+    if (!with_site_prefs) sorted_order(order);
 
     Report R{a, rs, hits, ents, species, n_ent, src, seg2, trims, multi_dist, order, o.pe_mode, o.ml_mode, o.max_ml, o.fmt, o.nthreads, o.micro_indel, o.splice_len, o.max_rpt_sam_seqs};
     R.ctx = ctx;
+    R.site_prefs = with_site_prefs ? &site_prefs : nullptr;
     R.pre = pre.fd >= 0 ? &pre : nullptr;
     S.done_with_head_start();
     R.restore_reads = restore_reads;
@@ -1280,6 +1344,15 @@ int cmd_align(int argc, char **argv, int first)
     const std::string opath = a.str("o");
     int rr = (o.fmt >= 5 && opath.size() > 5 && !strcasecmp(opath.c_str() + opath.size() - 4, ".bam")) ? report_bam(R, opath) : report_text(R);
     if (R.sam_prep) { bk_sam_prep_free(R.sam_prep); R.sam_prep = nullptr; }        // (the report took another path)
+    if (rr == 0 && with_site_prefs) {               // WriteSitePrefs, behind the writers and the -O statistics (Aligner.cpp:743)
+        std::string csv;
+        bk::site_prefs_csv(site_prefs, csv);
+        OutBuf sp_file;
+        sp_file.open(o.site_prefs_path.c_str());
+        const bool opened = sp_file.fd >= 0;
+        if (opened) { sp_file.put(csv); sp_file.close(); }
+        if (!opened || sp_file.failed) { diag("Fatal error: unable to write the site preferences to '%s'", o.site_prefs_path.c_str()); rr = -85; }
+    }
     // SNPs: the file is only opened for '-M0' .. '-M5' (Aligner.cpp:4488), and only processed when reads were accepted (:746)
     if (rr == 0 && o.snp.min_reads > 0 && o.fmt <= 5) {
         o.snp.path = a.has("S") ? a.str("S") : opath + ".snp";

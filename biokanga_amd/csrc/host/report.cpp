@@ -777,8 +777,8 @@ int report_text(Report &R)
         diag("Completed reporting SAM %llu read alignments", (unsigned long long)n_reported);
     } else {
         // -M0..3 CSV (loci; 1: + match sequence, 2: + read sequence, 3: + both) and -M4 UCSC BED
-        // (CAligner::WriteReadHits, Aligner.cpp:6336-6660); the site-preference score column is 0 as in the
-        // reference when no -8 preferences are computed
+        // (CAligner::WriteReadHits, Aligner.cpp:6336-6660); the score column comes from the -8 site preferences (:6447), and is 0 as in
+        // the reference when none are computed
         static const char up[8] = {'A', 'C', 'G', 'T', 'N', 'N', 'N', 'N'};
         bk::SfxFile sf;
         if (fmt == 1 || fmt == 3) {
@@ -833,12 +833,12 @@ int report_text(Report &R)
                             const bk_seg2 &g = seg2[RD(i)];
                             const bool sj = (g.flags & 4) != 0;
                             const uint32_t end1 = g.match_loci + g.match_len;          // AdjAlignEndLoci + 1
-                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\t%s\t0\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1,
-                                             sj ? "arj" : "ari", (char)h.strand, h.match_loci, end1, (unsigned)h.match_len, (unsigned)g.match_len, g.match_loci - h.match_loci);
+                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\t%s\t%d\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1,
+                                             sj ? "arj" : "ari", R.score(h, i), (char)h.strand, h.match_loci, end1, (unsigned)h.match_len, (unsigned)g.match_len, g.match_loci - h.match_loci);
                             (sj ? M.jct : M.ind).append(line, (size_t)m);
                         } else {
-                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\tar\t0\t%c\n", ents[h.chrom_id - 1].name, a_start(h, i), a_start(h, i) + a_len(h, i),
-                                             (char)h.strand);
+                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\tar\t%d\t%c\n", ents[h.chrom_id - 1].name, a_start(h, i), a_start(h, i) + a_len(h, i),
+                                             R.score(h, i), (char)h.strand);
                             M.out.append(line, (size_t)m);
                         }
                         M.n++;
@@ -849,9 +849,9 @@ int report_text(Report &R)
                     for (int sg = 0; sg < (two ? 2 : 1); sg++) {
                         const uint32_t s_loci = sg ? seg2[RD(i)].match_loci : a_start(h, i), s_len = sg ? seg2[RD(i)].match_len : a_len(h, i);
                         const uint32_t s_mm = sg ? seg2[RD(i)].mismatches : a_mm(h, i), s_rofs = sg ? seg2[RD(i)].read_ofs : TL(i);       // ReadOfs + TrimLeft
-                        int m = snprintf(line, sizeof(line), "%u,\"%s\",\"%s\",\"%s\",%u,%u,%u,\"%c\",0,0,1,%u,\"N/A\",\"%s\"", i + 1,
+                        int m = snprintf(line, sizeof(line), "%u,\"%s\",\"%s\",\"%s\",%u,%u,%u,\"%c\",%d,0,1,%u,\"N/A\",\"%s\"", i + 1,
                                          two ? ((seg2[RD(i)].flags & 4) ? "arj" : "ari") : "ar", species.c_str(),
-                                         ents[h.chrom_id - 1].name, s_loci, s_loci + s_len - 1, (unsigned)s_len, (char)h.strand, (unsigned)s_mm, rs.name(RD(i)));
+                                         ents[h.chrom_id - 1].name, s_loci, s_loci + s_len - 1, (unsigned)s_len, (char)h.strand, R.score(h, i), (unsigned)s_mm, rs.name(RD(i)));
                         rec.assign(line, (size_t)m);
                         if (fmt >= 2) {                                          // the read as loaded, from the segment's read offset
                             const uint8_t *sq = rs.bases.data() + rs.offs[RD(i)];

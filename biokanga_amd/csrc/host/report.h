@@ -5,6 +5,7 @@
 #include "../../../include/biokanga_amd.h"
 #include "cli_common.h"
 #include "post_filters.h"
+#include "site_prefs.h"
 
 namespace bkcli {
 
@@ -24,6 +25,7 @@ struct Report {
     const std::vector<uint32_t> &order;           // records in the reference's output order
     int pe_mode, ml_mode, max_ml, fmt, nthreads, micro_indel, splice_len, max_rpt_sam_seqs;
     bk_ctx *ctx = nullptr;                        // a context whose device formats plain SAM records (bk_sam_format); may be null
+    const bk::SitePrefs *site_prefs = nullptr;    // -8: the table the BED / CSV score column is taken from (null: the column is 0)
     SamPrealloc *pre = nullptr;                   // SAM text: the output file, created early and being preallocated; may be null
     bk_sam_prep *sam_prep = nullptr;              // the device formatter's head start (bk_sam_prepare), consumed or freed by report_text / report_bam
     // the reads in the packed form the alignment was fed from, as the head start was given them (bk_sam_job.pk_*); the arrays themselves
@@ -43,6 +45,7 @@ struct Report {
     uint32_t TR(size_t i) const { return trims.empty() ? 0u : trims.right[i]; }
     uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci
     uint32_t a_len(const bk_hit &h, size_t i) const { return (uint32_t)h.match_len - TL(i) - TR(i); }                      // AdjHitLen
+    int score(const bk_hit &h, size_t i) const { return site_prefs ? site_prefs->score(h.strand, i) : 0; }                // Aligner.cpp:6447
     uint32_t a_mm(const bk_hit &h, size_t i) const { return trims.empty() ? h.mismatches : trims.mismatches[i]; }         // TrimMismatches
 };
 

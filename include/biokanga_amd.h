@@ -229,7 +229,7 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "force_rccl" (bk_seq_counts_allreduce goes through RCCL - a communicator of one rank - even when every context sits on one device; how many
  *   of a context's reductions did, and the ranks of the last one's communicator: "rccl_allreduces", "rccl_ranks", read only)
  *   "debug_stop_phase" (test hook, see bk_debug_intervals)
- *   "chunk_reads" (reads per pass over the phases)   "max_read_len"
+ *   "chunk_reads" (reads per pass over the phases)   "max_read_len"   "site_chunk" (requests bk_site_octamers stages at a time)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -495,6 +495,32 @@ int  bk_snp_counts(bk_ctx *ctx, uint32_t chrom_id, uint32_t loci, uint32_t n, ui
  * non-ACGT base in the window are skipped) - tsSNPCentroid.NumInsts of OutputSNPs (Aligner.cpp:6934-6953).  num_insts: 16384 uint32. */
 #define BK_SNP_CENTROIDS 16384
 int  bk_snp_centroid_insts(bk_ctx *ctx, uint32_t chrom_id, int32_t min_reads, uint32_t *num_insts);
+
+/* ---- start-site octamer preferences (-8 / -9) --------------------------------------------------- */
+/* The gather of CAligner::ProcessSiteProbabilites (biokanga/Aligner.cpp:8121-8172) on the GPU: for every alignment the eight target
+ * bases at its start site - MatchLoci + rel_ofs for '+', MatchLoci + MatchLen - 1 - rel_ofs - 7 for '-', in the reference's 32-bit
+ * unsigned arithmetic, then its end clamp (site + 8 >= sequence length: site = length - 9) - from the 4-bit target resident in HBM.
+ * For '-' the eight bases are reverse-complemented.  The sequential rest of that routine (PrevLoci, the counts, the scaling, the
+ * writer) is host policy above this boundary (biokanga_amd/csrc/host/site_prefs.h). */
+typedef struct bk_site_req {     /* one alignment: Seg[0] as it stands */
+    uint32_t chrom_id;           /* Seg[0].ChromID                                                          */
+    uint32_t match_loci;         /* Seg[0].MatchLoci                                                        */
+    uint16_t match_len;          /* Seg[0].MatchLen                                                         */
+    uint8_t  strand;             /* '+' | '-'                                                               */
+    uint8_t  reserved;
+} bk_site_req;                   /* 12 bytes */
+typedef struct bk_site_res {
+    uint32_t codes;              /* eight 3-bit base codes in buffer order, the first in bits 23..21, the last in bits 2..0 (all of
+                                  * them < 4: codes is the octamer's index); bit 31: the site lies outside the sequence, nothing fetched */
+    uint32_t site;               /* the site (HitLoci) after the clamp                                      */
+} bk_site_res;                   /* 8 bytes */
+#define BK_SITE_MAX_OFS 100      /* cMaxSitePrefOfs */
+/* host arrays, blocking; staged through buffers of the context in chunks.  BK_ERR_PARAMS before anything is launched: |rel_ofs| >
+ * BK_SITE_MAX_OFS, a chrom_id that is no sequence of the index, a strand other than '+' / '-' */
+int  bk_site_octamers(bk_ctx *ctx, const bk_site_req *reqs, uint64_t n, int32_t rel_ofs, bk_site_res *out);
+/* the same HBM to HBM on the context's GPU (d_out 8-byte aligned); asynchronous on the context's stream unless `sync`.  The caller
+ * guarantees the requests (one whose chrom_id is no sequence of the index comes back as "nothing fetched") */
+int  bk_site_octamers_device(bk_ctx *ctx, const void *d_reqs, uint64_t n, int32_t rel_ofs, void *d_out, int sync);
 
 /* ---- SAM records formatted on the device -------------------------------------------------------------------------
  * CAligner::ReportBAMread (biokanga/Aligner.cpp:5768-6126; CSAMfile::AddAlignment, SAMfile.cpp:2100-2283) prints one text line per
