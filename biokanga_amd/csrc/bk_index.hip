@@ -237,6 +237,9 @@ __device__ __forceinline__ uint64_t tgt2_bases32(const uint64_t *__restrict__ tg
     return (a << sh) | ((bq >> 1) >> (63 - sh));
 }
 
+// bases of a second-level key in front of its trailing t's
+__device__ __forceinline__ int swin_key_known(uint32_t key) { return kK2Bases - ((__ffs((int)~(key >> 2)) - 1) >> 1); }
+
 // the suffix array indexes [a, e) (a multiple of 64): bit i - a of a level's bitmap.  The range is taken for itself - a run starts at a
 // and one ends at e - so that an array can be made range by range, behind the suffix array's upload.  starts (optional): the bucket-start
 // bitmap k_build_ktab left (else k_swin_bucket_starts adds those bits)
@@ -255,8 +258,11 @@ __global__ void __launch_bounds__(256) k_swin_breaks(DevIndex ix, SwinLevels lv,
             if (a == kK2Above || c == kK2Above) shared = 0;
             else {
                 const uint32_t x = (a ^ c) & ~3u;
-                if (x) shared = k + (__clz((int)x) >> 1);
-                else if ((a | c) & 3u) shared = deep_from - 1;   // an N or a sequence end among the 15 bases: no deeper than the keys
+                // a key with an N or a sequence end among its 15 bases holds it as t, like everything behind it: only the bases in front of such
+                // a key's trailing t's are known to be the suffix's own
+                const int known = min((a & 3u) ? swin_key_known(a) : kK2Bases, (c & 3u) ? swin_key_known(c) : kK2Bases);
+                if (x) shared = k + min(__clz((int)x) >> 1, known);
+                else if ((a | c) & 3u) shared = k + known;
                 else if (w_max > deep_from) {
                     const bool wide_el = ix.sa_hi != nullptr;
                     const uint64_t pa = (wide_el ? sa_get<true>(ix, i - 1) : (uint64_t)ix.sa_lo[i - 1]) + (uint64_t)deep_from, pb = (wide_el ? sa_get<true>(ix, i) : (uint64_t)ix.sa_lo[i]) + (uint64_t)deep_from;

@@ -166,6 +166,50 @@ def devtest_lib():
     return lib
 
 
+_indextest = None
+
+
+def indextest_lib():
+    """biokanga_amd/lib/libbk_indextest.so: the index set-up kernels of bk_index.hip under test-only entry points (tests/hip/indextest.hip),
+    built by biokanga_amd/csrc/Makefile with everything else.  A missing library is an error.  Every entry point takes raw device
+    pointers (torch tensors' data_ptr()) with the sizes of the buffers behind them and returns the hipError_t."""
+    global _indextest
+    if _indextest is not None:
+        return _indextest
+    so = os.path.join(ROOT, "biokanga_amd", "lib", "libbk_indextest.so")
+    if not os.path.exists(so):
+        raise RuntimeError(f"{so} is missing: build it (make -C biokanga_amd/csrc)")
+    lib = ctypes.CDLL(so)
+    vp, u32, u64, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+    for name, args in (("bkit_pack_target", [vp, u64, vp, u64]),
+                       ("bkit_pack_target2", [vp, u64, vp, u64, vp, u64, i32]),
+                       ("bkit_split_sa5", [vp, u64, vp, vp]),
+                       ("bkit_build_ktab", [vp, u64, vp, vp, u64, vp, u64, i32, i32, i32, u64, u64, vp, u64]),
+                       ("bkit_build_k2", [vp, u64, vp, vp, u64, i32, vp, vp, vp, u64, vp, u64, u64, i32]),
+                       ("bkit_build_k2_levels", [vp, u64, u64]),
+                       ("bkit_make_ktab2", [vp, vp, u64, u64, vp, vp]),
+                       ("bkit_fill_ktab2_y", [vp, vp, u64, vp]),
+                       ("bkit_pack_ktab64", [vp, u64, vp, vp, u64, vp]),
+                       ("bkit_build_isa", [vp, u64, vp, u64, u64]),
+                       ("bkit_count_nonzero", [vp, u64, vp]),
+                       ("bkit_build_swin", [vp, u64, vp, vp, u64, vp, u64, i32]),
+                       ("bkit_swin_fill", [vp, u64, vp, vp, u64, vp, u64, vp, u64, i32, u64, u64]),
+                       ("bkit_swin_map", [vp, vp, u64, u32, vp, vp]),
+                       ("bkit_swin_breaks", [vp, vp, u64, vp, u64, i32, vp, vp, vp, vp, u64, i32, ctypes.POINTER(i32), i32, vp, u64, u64, u64, u64, vp, u64]),
+                       ("bkit_swin_cover", [vp, u64, u64, u32, u32, vp, u64, i32])):
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ctypes.c_int
+    lib.bkit_consts.argtypes = [ctypes.POINTER(u32)]
+    lib.bkit_consts.restype = None
+    c = (u32 * 10)()
+    lib.bkit_consts(c)
+    (lib.kSwBlkShift, lib.kSwMinRun, lib.kSwHead, lib.kSwLevels, lib.kTab2BitmapMax, lib.kK2Levels, lib.kK2Bases, lib.kSwPre3, lib.kSwPre5,
+     lib.kMaxReadLenAbs) = (int(x) for x in c)
+    _indextest = lib
+    return lib
+
+
 class OracleSfx:
     def __init__(self, path=None, *, seq=None, sa=None, el_size=4, entries=None):
         """path: a .sfx file; or seq (uint8, 1 B/base incl. EOS) + sa (raw little-endian element bytes or
