@@ -210,6 +210,51 @@ def indextest_lib():
     return lib
 
 
+_preptest = None
+
+
+class PrepBatch(ctypes.Structure):
+    """bkpt_batch of tests/hip/preptest.hip: device pointers (0 = null) and the sizes of the buffers behind them"""
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("bases", "bases_bytes", "pk_words", "pk_words_n", "pk_exc", "pk_nexc", "pk_read0", "offs", "lens", "rd4", "rd4_words", "rd2", "rd2_words",
+                 "rmeta", "rmeta_words", "out", "out_recs", "plan", "plan_rows", "plan_stride", "plan_n", "wpr", "n_reads", "nw")]
+
+
+def preptest_lib():
+    """biokanga_amd/lib/libbk_preptest.so: the read preparation kernels of bk_prep.hip under test-only entry points (tests/hip/preptest.hip),
+    built by biokanga_amd/csrc/Makefile with everything else.  A missing library is an error.  Every entry point takes raw device
+    pointers (torch tensors' data_ptr()) with the sizes of the buffers behind them and returns the hipError_t."""
+    global _preptest
+    if _preptest is not None:
+        return _preptest
+    so = os.path.join(ROOT, "biokanga_amd", "lib", "libbk_preptest.so")
+    if not os.path.exists(so):
+        raise RuntimeError(f"{so} is missing: build it (make -C biokanga_amd/csrc)")
+    lib = ctypes.CDLL(so)
+    vp, u32, u64, i32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+    pb, pi, pu64 = ctypes.POINTER(PrepBatch), ctypes.POINTER(i32), ctypes.POINTER(u64)
+    for name, args in (("bkpt_plan_fill", [pi, i32, i32, vp]),
+                       ("bkpt_prep", [pb, pi, vp, u64, vp, vp, vp, u64, vp, u64]),
+                       ("bkpt_pack_rows", [pb, vp, u64]),
+                       ("bkpt_expand_rd4", [pb, vp, u64]),
+                       ("bkpt_compact", [pu64, u64, u32, vp, u64, pu64, pu64, pu64, i32, vp]),
+                       ("bkpt_widen_lens", [vp, u64, vp, u64, vp, u64]),
+                       ("bkpt_packed_extent", [vp, vp, u64, vp]),
+                       ("bkpt_check_exc", [vp, u64, vp, u32, vp]),
+                       ("bkpt_max_len", [vp, u64, vp])):
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ctypes.c_int
+    lib.bkpt_consts.argtypes = [ctypes.POINTER(u32)]
+    lib.bkpt_consts.restype = None
+    c = (u32 * 8)()
+    lib.bkpt_consts(c)
+    (lib.kListStripes, lib.kNwLong, lib.kNwLongest, lib.kPackedPadWords, lib.kMaxCoresFast, lib.kReadHasN, lib.kMaxReadLenAbs,
+     lib.sizeof_hit) = (int(x) for x in c)
+    _preptest = lib
+    return lib
+
+
 class OracleSfx:
     def __init__(self, path=None, *, seq=None, sa=None, el_size=4, entries=None):
         """path: a .sfx file; or seq (uint8, 1 B/base incl. EOS) + sa (raw little-endian element bytes or
