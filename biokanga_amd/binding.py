@@ -14,7 +14,7 @@ EXPORTED_SYMBOLS = [
     "bk_version", "bk_strerror", "bk_device_count", "bk_ctx_create", "bk_ctx_create_from_device",
     "bk_ctx_clone", "bk_ctx_destroy", "bk_ctx_set_params", "bk_ctx_tune", "bk_num_entries", "bk_get_entry",
     "bk_dataset_name", "bk_concat_len", "bk_sfx_el_size", "bk_min_core_len", "bk_align_batch",
-    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_site_octamers", "bk_site_octamers_device", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
+    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_site_octamers", "bk_site_octamers_device", "bk_primer_correct", "bk_primer_correct_device", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
     "bk_host_alloc", "bk_host_free", "bk_stream_create", "bk_stream_submit", "bk_stream_wait", "bk_stream_batch_loci",
     "bk_stream_batch_seg2", "bk_stream_release", "bk_stream_drain", "bk_stream_get_stats", "bk_stream_destroy",
     "bk_packed_words", "bk_pack_reads", "bk_align_batch_packed", "bk_stream_submit_packed", "bk_sam_format", "bk_batch_loci_trims", "bk_stream_batch_loci_trims", "bk_stream_submit_device", "bk_sam_prepare", "bk_sam_prep_free",
@@ -35,11 +35,13 @@ class AlignParams(ctypes.Structure):
                 ("align_strand", ctypes.c_int32), ("pmode", ctypes.c_int32),
                 ("max_ns", ctypes.c_int32), ("max_ml", ctypes.c_int32),
                 ("clamp_ml", ctypes.c_int32), ("best_matches", ctypes.c_int32),
-                ("micro_indel_len", ctypes.c_int32), ("splice_junct_len", ctypes.c_int32), ("min_chimeric_len", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+                ("micro_indel_len", ctypes.c_int32), ("splice_junct_len", ctypes.c_int32), ("min_chimeric_len", ctypes.c_int32), ("orphan_core_subs1", ctypes.c_int32)]
 
     def __init__(self, max_subs=10, min_edit_dist=1, align_strand=0, pmode=0, max_ns=1, max_ml=1, clamp_ml=0, best_matches=0,
-                 micro_indel_len=0, splice_junct_len=0, min_chimeric_len=0):
+                 micro_indel_len=0, splice_junct_len=0, min_chimeric_len=0, orphan_core_subs=None):
         super().__init__()
+        # -6: the rate the PE orphan recovery's cores come from (the user's -s) while max_subs is the initial rate; None: max_subs serves both
+        self.orphan_core_subs1 = 0 if orphan_core_subs is None else int(orphan_core_subs) + 1
         self.min_chimeric_len = min_chimeric_len
         self.splice_junct_len = splice_junct_len
         self.micro_indel_len = micro_indel_len
@@ -69,6 +71,12 @@ assert SNP_SITE_DTYPE.itemsize == 40
 SITE_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("match_loci", "<u4"), ("match_len", "<u2"), ("strand", "u1"), ("_r", "u1")])
 SITE_RES_DTYPE = np.dtype([("codes", "<u4"), ("site", "<u4")])
 assert SITE_REQ_DTYPE.itemsize == 12 and SITE_RES_DTYPE.itemsize == 8
+PRIMER_KLEN = 12
+PRIMER_UNTOUCHED, PRIMER_CORRECTED, PRIMER_REJECTED, PRIMER_BAD = 0, 1, 2, 0x80
+PRIMER_REQ_DTYPE = np.dtype([("codes", "<u8"), ("chrom_id", "<u4"), ("match_loci", "<u4"), ("match_len", "<u2"), ("strand", "u1"), ("low_mm", "u1"),
+                             ("max_mms", "u1"), ("_r", "u1", (3,))])
+PRIMER_RES_DTYPE = np.dtype([("codes", "<u8"), ("mask", "<u2"), ("status", "u1"), ("mismatches", "u1"), ("n_corrected", "u1"), ("_r", "u1", (3,))])
+assert PRIMER_REQ_DTYPE.itemsize == 24 and PRIMER_RES_DTYPE.itemsize == 16
 
 ENTRY_DTYPE = np.dtype([("entry_id", "<u4"), ("seq_len", "<u4"), ("start_ofs", "<u8"), ("end_ofs", "<u8"),
                         ("name", "S81"), ("_pad", "S7")])
@@ -229,6 +237,10 @@ def load_library():
     lib.bk_site_octamers.restype = i32
     lib.bk_site_octamers_device.argtypes = [vp, vp, u64, i32, vp, i32]
     lib.bk_site_octamers_device.restype = i32
+    lib.bk_primer_correct.argtypes = [vp, vp, u64, vp]
+    lib.bk_primer_correct.restype = i32
+    lib.bk_primer_correct_device.argtypes = [vp, vp, u64, vp, i32]
+    lib.bk_primer_correct_device.restype = i32
     lib.bk_seq_counts.argtypes = [vp, vp, u32, i32]
     lib.bk_seq_counts.restype = i32
     lib.bk_seq_counts_allreduce.argtypes = [ctypes.POINTER(vp), i32, vp, u32, i32]
@@ -625,6 +637,21 @@ class Aligner:
         rc = self.lib.bk_site_octamers_device(self.h, d_reqs_ptr, n, int(rel_ofs), d_out_ptr, 1 if sync else 0)
         if rc:
             raise BkError(rc, "bk_site_octamers_device")
+
+    def primer_correct(self, reqs):
+        """5' primer artefact correction of PRIMER_REQ_DTYPE requests (the per-read half of CAligner::PCR5PrimerCorrect): PRIMER_RES_DTYPE, one per request"""
+        reqs = np.ascontiguousarray(reqs, dtype=PRIMER_REQ_DTYPE)
+        out = np.zeros(len(reqs), dtype=PRIMER_RES_DTYPE)
+        rc = self.lib.bk_primer_correct(self.h, reqs.ctypes.data, len(reqs), out.ctypes.data)
+        if rc:
+            raise BkError(rc, "bk_primer_correct")
+        return out
+
+    def primer_correct_device(self, d_reqs_ptr, n, d_out_ptr, sync=True):
+        """primer_correct on PRIMER_REQ_DTYPE records already in HBM, PRIMER_RES_DTYPE results left there (raw device pointers)"""
+        rc = self.lib.bk_primer_correct_device(self.h, d_reqs_ptr, n, d_out_ptr, 1 if sync else 0)
+        if rc:
+            raise BkError(rc, "bk_primer_correct_device")
 
     def pair(self, bases, offs, lens, hits, pe, seg2=None):
         """PE association in place on `hits` (PE1/PE2 interleaved; the output of align() for the same reads).  seg2 = batch_seg2() of that

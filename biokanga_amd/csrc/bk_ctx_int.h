@@ -50,6 +50,8 @@ struct BatchBufs {
     DevBuf<bk_snp_site> snp_sites;        // site list of the last bk_snp_sites call
     DevBuf<bk_site_req> site_reqs;        // bk_site_octamers: one chunk of requests and its results
     DevBuf<bk_site_res> site_res;
+    DevBuf<bk_primer_req> primer_reqs;    // bk_primer_correct: one chunk of requests and its results (made by its first call)
+    DevBuf<bk_primer_res> primer_res;
     DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
@@ -168,6 +170,7 @@ struct bk_ctx {
     bool debug = false;      // BK_DEBUG in the environment when the context was created: per-phase counts on stderr
     uint32_t chunk_reads = 64u << 20;
     uint64_t site_chunk = 8u << 20;       // bk_site_octamers stages this many requests at a time ("site_chunk")
+    uint64_t primer_chunk = 8u << 20;     // .. and bk_primer_correct this many ("primer_chunk")
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)

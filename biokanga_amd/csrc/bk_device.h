@@ -125,6 +125,7 @@ struct DevAlignCfg {            // derived once per context (CAligner::LocateCor
     int max_subs, mm_delta, align_strand, max_ns, max_hits;
     int min_core_len, slides_per100, max_iter;
     int heavy_thresh;           // intervals longer than this go to the wave-per-read kernel
+    int orphan_core_subs;       // the rate the orphan recovery's cores come from: max_subs unless -6 aligns at a higher rate than -s (bk_align_params)
 };
 
 struct DevBatch {

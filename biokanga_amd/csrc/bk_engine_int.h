@@ -44,6 +44,7 @@ void launch_packed_extent(const uint64_t *offs, const uint32_t *lens, uint32_t n
 void launch_snp_pileup(const DevIndex &ix, const uint8_t *bases, const uint64_t *offs, const uint32_t *id2idx, const bk_snp_aln *alns, uint64_t n_alns,
                        uint32_t *planes, hipStream_t s);
 void launch_site_octamers(const DevIndex &ix, const bk_site_req *reqs, uint64_t n, int32_t rel_ofs, bk_site_res *out, hipStream_t s);      // bk_sites.hip
+void launch_primer_correct(const DevIndex &ix, const bk_primer_req *reqs, uint64_t n, bk_primer_res *out, hipStream_t s);      // bk_primer.hip
 void launch_snp_gather(const DevIndex &ix, const uint32_t *planes, uint64_t g0, uint32_t n, uint32_t *out, hipStream_t s);
 void launch_snp_centroids(const DevIndex &ix, const uint32_t *planes, uint64_t g0, uint32_t chrom_len, uint32_t min_reads, uint32_t *hist, hipStream_t s);
 void launch_snp_sites(const DevIndex &ix, const uint32_t *planes, uint64_t g0, uint32_t chrom_len, uint32_t min_reads, double min_prop,

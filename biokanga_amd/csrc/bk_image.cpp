@@ -42,7 +42,8 @@ int derive_cfg(bk_ctx *c)
 {
     const bk_align_params &p = c->params;
     if (p.max_subs < 0 || p.max_subs > 25 || p.min_edit_dist < 1 || p.min_edit_dist > 2 || p.align_strand < 0 ||
-        p.align_strand > 2 || p.pmode < 0 || p.pmode > 3 || p.max_ns < 0 || p.max_ns > 5)
+        p.align_strand > 2 || p.pmode < 0 || p.pmode > 3 || p.max_ns < 0 || p.max_ns > 5 ||
+        p.orphan_core_subs1 < 0 || p.orphan_core_subs1 > 26)
         return BK_ERR_PARAMS;
     if (p.max_ml < 0 || p.max_ml > BK_MAX_ML) return BK_ERR_PARAMS;
     if (p.best_matches && p.max_ml < 2) return BK_ERR_PARAMS;
@@ -56,6 +57,7 @@ int derive_cfg(bk_ctx *c)
     if (p.splice_junct_len != 0 && (p.splice_junct_len < 25 || p.splice_junct_len > 100000)) return BK_ERR_PARAMS;   // cMin/cMaxJunctAlignSep
     DevAlignCfg &g = c->cfg;
     g.max_subs = p.max_subs;
+    g.orphan_core_subs = p.orphan_core_subs1 > 0 ? p.orphan_core_subs1 - 1 : p.max_subs;
     g.mm_delta = p.min_edit_dist;
     g.align_strand = p.align_strand;
     g.max_ns = p.max_ns;

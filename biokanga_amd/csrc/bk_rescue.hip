@@ -635,8 +635,8 @@ __global__ void __launch_bounds__(256) k_pe_orphan(DevIndex ix, DevAlignCfg cfg,
             if (end_put - start_put >= 1000) {
                 // cores of the read located through the suffix array (IterateExactsRange, :3382-3474)
                 int match_len = read_len - 1;
-                int m = cfg.max_subs == 0 ? 0 : (int)(0.5 + (double)(match_len * cfg.max_subs) / 100.0);
-                if (cfg.max_subs != 0 && m < 1) m = 1;
+                int m = cfg.orphan_core_subs == 0 ? 0 : (int)(0.5 + (double)(match_len * cfg.orphan_core_subs) / 100.0);      // (m_MaxSubs, Aligner.cpp:3256,3354)
+                if (cfg.orphan_core_subs != 0 && m < 1) m = 1;
                 if (m > 63) m = 63;
                 int core_len = read_len / (cfg.mm_delta == 1 ? m + 1 : m + 2);
                 if (core_len < cfg.min_core_len) core_len = cfg.min_core_len;

@@ -8,7 +8,7 @@
 //   biokanga index -i genome.fa[.gz] [-i more.fa] -o genome.sfx -r name [-l minseqlen] [-d descr] [-t title] [-T threads] [--device n]
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
-//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-T host threads] [-F logfile] [--device n | --devices 0-7]
+//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-T host threads] [-F logfile] [--device n | --devices 0-7]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -49,6 +49,7 @@
 #include "post_filters.h"
 #include "snp.h"
 #include "site_prefs.h"
+#include "primer_correct.h"
 #include "read_loader.h"
 #include "contaminants.h"
 #include "report.h"
@@ -216,6 +217,8 @@ struct AlignOpts {
     SnpOpts snp;
     std::string site_prefs_path;           // -8: start-site octamer preferences into this file (empty: none)
     int site_prefs_ofs = -4;               // -9, cDfltRelSiteStartOfs
+    int primer_subs = 0;                   // -6: align at min(-s + this, 15), then correct 5' primer artefacts back under -s (0: off)
+    int user_subs = 10;                    // -s as given (m_MaxSubs); P.max_subs is the rate the reads are aligned at (m_InitalAlignSubs)
     std::vector<regex_t> re_excl, re_incl;
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
@@ -322,8 +325,30 @@ int read_align_opts(Args &a, AlignOpts &o)
     o.P.pmode = a.num("m", 0);
     o.P.align_strand = a.num("Q", 0);
     o.P.min_edit_dist = a.num("e", 1);
-    o.P.max_subs = a.num("s", 10);                  // cDfltAllowedSubs per 100bp
+    o.P.max_subs = o.user_subs = a.num("s", 10);    // cDfltAllowedSubs per 100bp
     if (o.splice_len > 0 && o.min_chim == 0 && o.min_flank == 0) o.min_flank = o.P.max_subs;      // MinFlankExacts = MaxSubs (kanga.cpp:810-811)
+    // -6 5' primer artefact correction (kanga.cpp:784-795): the reads are aligned at the initial rate, the orphan recovery's cores and
+    // the correction pass keep the user's (Aligner.cpp:208-213,3256,611)
+    o.primer_subs = a.num("6", 0);
+    if (o.primer_subs < 0 || o.primer_subs > bk::kMaxPrimerSubs) {
+        diag("Error: PCR primer correction subs '-6%d' specified outside of range 0..%d\n", o.primer_subs, bk::kMaxPrimerSubs);
+        return 1;
+    }
+    if (o.primer_subs != 0 && o.min_chim != 0) { diag("Error: PCR primer correction subs not allowed when also specifying chimeric trimming\n"); return 1; }
+    if (o.primer_subs != 0 && o.ml_mode == 5) {
+        // (every locus of a read is a record of its own there, each corrected against its own locus in a copy of the read the reference
+        // makes for it: the records here share their read's bases)
+        diag("Error: PCR primer correction subs '-6%d' is not available when reporting all multiloci alignments '-r5'", o.primer_subs);
+        return 1;
+    }
+    if (o.primer_subs != 0) {
+        if (o.user_subs < 0 || o.user_subs > bk::kMaxAllowedSubs) {
+            diag("Error: Max allowed substitutions per 100bp read length '-s%d' specified outside of range %d..%d\n", o.user_subs, 0, bk::kMaxAllowedSubs);
+            return 1;
+        }
+        o.P.max_subs = bk::primer_initial_subs(o.user_subs, o.primer_subs);
+        o.P.orphan_core_subs1 = o.user_subs + 1;
+    }
     o.P.min_chimeric_len = o.min_chim;
     o.P.max_ns = a.num("n", 1);
     o.P.max_ml = o.max_ml;
@@ -847,8 +872,8 @@ int cmd_align(int argc, char **argv, int first)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H89", "EXN", a, err)) {
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H896", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
@@ -889,6 +914,12 @@ int cmd_align(int argc, char **argv, int first)
         sp_file.open(o.site_prefs_path.c_str());
         if (sp_file.fd < 0) { diag("Fatal: unable to create '%s'", o.site_prefs_path.c_str()); return 1; }
         sp_file.close();
+    }
+    if (o.primer_subs > 0) {                        // (parameter line, kanga.cpp:1146-1147)
+        char line[80];
+        snprintf(line, sizeof(line), "correcting PCR 5' artefacts : %d\n", o.primer_subs);
+        fputs(line, stdout);
+        if (g_logfile) fputs(line, g_logfile);
     }
 
     // index images travel to the devices (one loader thread each) while this thread parses the reads: the two longest serial steps
@@ -1031,7 +1062,9 @@ int cmd_align(int argc, char **argv, int first)
     bk_sam_prep *sam_prep = nullptr;
     bk_sam_job pk_job{};
     struct PrepGuard { bk_sam_prep *&p; Submission &S; ~PrepGuard() { if (p) { S.done_with_head_start(); bk_sam_prep_free(p); p = nullptr; } } } prep_guard{sam_prep, S};      // (not consumed: given back)
-    if (pre.fd >= 0 && nr == rs.lens.size()) {
+    // (-6 overwrites bases of the read store further down: no head start then - the formatter uploads the byte form, corrected, when
+    // the records are written, and the bases are never dropped: may_drop_bases needs the head start)
+    if (pre.fd >= 0 && nr == rs.lens.size() && o.primer_subs == 0) {
         bk_sam_job hj{};
         hj.bases = rs.bases.data(); hj.n_bases = rs.bases.size(); hj.offs = rs.offs.data(); hj.lens = rs.lens.data();
         hj.names = rs.names.data(); hj.n_name_bytes = rs.names.size(); hj.name_ofs = rs.name_ofs.data(); hj.n_reads = nr;
@@ -1164,6 +1197,49 @@ int cmd_align(int argc, char **argv, int first)
         const size_t n_dup = bk::reduce_pcr_duplicates(hits, ord, [&](size_t i) { return a_start(hits[i], i); }, [&](size_t i) { return a_len(hits[i], i); }, o.pcr_win);
         diag("Removed %zu potential PCR artefact reads", n_dup);
     }
+    if (o.primer_subs > 0) {
+        // CAligner::PCR5PrimerCorrect(m_MaxSubs), between -k and the flank trimmer (Aligner.cpp:608-617): the reads still above the user's
+        // rate go to the first device with their first twelve bases; its answers patch the read store and the records (primer_correct.h).
+        // The reference sorts behind the pass since LowMMCnt is a sort key: every sorted_order() below is made from the records as they stand
+        diag("PCR 5' Primer correction processing started..");
+        diag("Starting PCR 5' %dbp primer correction processing targeting substitution rate of %d ...", BK_PRIMER_KLEN, o.user_subs);
+        HostClock clk;
+        const int nt = std::max(1, o.nthreads);
+        auto selected = [&](size_t i) { return bk::primer_selects(hits[i], has_seg2(i), rs.lens[RD(i)], o.user_subs); };
+        std::vector<size_t> first((size_t)nt + 1, 0);
+        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) { size_t c = 0; for (size_t i = lo; i < hi; i++) c += selected(i); first[(size_t)t + 1] = c; });
+        for (int t = 0; t < nt; t++) first[(size_t)t + 1] += first[(size_t)t];
+        bk::RawVec<bk_primer_req> reqs(first[(size_t)nt]);
+        bk::RawVec<uint32_t> rec_of(first[(size_t)nt]);
+        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
+            size_t at = first[(size_t)t];
+            for (size_t i = lo; i < hi; i++) {
+                if (!selected(i)) continue;
+                reqs[at] = bk::primer_request(hits[i], rs.bases.data() + rs.offs[RD(i)], rs.lens[RD(i)], o.user_subs);
+                rec_of[at++] = (uint32_t)i;
+            }
+        });
+        bk::RawVec<bk_primer_res> res(reqs.size());
+        clk.lap("primer correction requests made");
+        const int prc = bk_primer_correct(ctx, reqs.data(), reqs.size(), res.data());
+        if (prc) { diag("Fatal: the 5' primer correction failed: %s", bk_strerror(prc)); destroy_ctxs(); return 1; }
+        clk.lap("primer windows compared (device)");
+        // (the pass writes Seg[0].Mismatches, not TrimMismatches - which the CSV writers and the -O statistics print, and which only the
+        // flank trimmer computes again, for the reads it trims, :1788: the counts as they stood before the pass are kept as the trims')
+        if (trims.empty()) {
+            trims.left.assign(nr, 0); trims.right.assign(nr, 0); trims.mismatches.resize(nr);
+            for (size_t i = 0; i < nr; i++) trims.mismatches[i] = hits[i].mismatches;
+        }
+        bk::PrimerStats pst;
+        for (size_t k = 0; k < reqs.size(); k++) {
+            const size_t i = rec_of[k];
+            if (bk::primer_apply(res[k], hits[i], rs.bases.data() + rs.offs[RD(i)], pst)) { diag("Fatal: the 5' primer correction turned a request down"); destroy_ctxs(); return 1; }
+        }
+        clk.lap("primer corrections applied");
+        diag("Completed PCR 5' primer correction, %llu reads with %llu bases corrected, %llu reads with excessive substitutions rejected",
+             (unsigned long long)pst.reads, (unsigned long long)pst.bases, (unsigned long long)pst.rejected);
+        diag("PCR 5' Primer correction processing completed");
+    }
     if (o.min_flank > 0) {
         diag("Starting 5' and 3' flank sequence autotrim processing...");
         bk::SfxFile sft;
@@ -1279,7 +1355,7 @@ int cmd_align(int argc, char **argv, int first)
          (unsigned long long)(nr - nar[1]), (unsigned long long)nar[2]);
     diag("Read nonalignment reason summary:");
     for (int k = 0; k < 20; k++) diag("   %llu (%s) %s", (unsigned long long)nar[k], kNarTag[k], kNarDescr[k]);
-    if (!o.pe_mode && !o.ml_mode && !o.micro_indel && !o.splice_len && !o.min_chim && o.pcr_win < 0 && !o.min_flank && o.re_excl.empty() && o.re_incl.empty()) {
+    if (!o.pe_mode && !o.ml_mode && !o.micro_indel && !o.splice_len && !o.min_chim && o.pcr_win < 0 && !o.min_flank && !o.primer_subs && o.re_excl.empty() && o.re_incl.empty()) {
         // nothing above changed an acceptance: the per-sequence counts the devices kept (summed over them by the exchange step)
         // must add up to the accepted reads counted here
         uint64_t tot = 0;

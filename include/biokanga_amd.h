@@ -63,7 +63,9 @@ typedef struct bk_align_params {
                              *     (CSfxArrayV3::LocateSpliceJuncts); second segments through bk_batch_seg2(), flags bit 2      */
     int32_t min_chimeric_len;/* -c  0, or 50..99: reads nothing else aligned may be placed end-trimmed, keeping at least this percentage of
                              *     their length (chimeric form of LocateCoreMultiples); trims through bk_batch_seg2(), flags bit 3 */
-    int32_t reserved2;
+    int32_t orphan_core_subs1;/* -6  0: nothing; r + 1: the paired-end orphan recovery derives its core length from rate r per 100 bp (the user's -s,
+                             *     m_MaxSubs at Aligner.cpp:3256,3354) while max_subs - then the initial rate min(s + n, 15) - stays what
+                             *     its alignments may carry (pPars->MaxSubs, :3275,3373).  One more than the rate: -s0 -6 n is legal     */
 } bk_align_params;
 
 /* per-read result: the tsReadHit fields written by ProcCoredApprox (Aligner.cpp:9311-9479) and
@@ -230,6 +232,7 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   of a context's reductions did, and the ranks of the last one's communicator: "rccl_allreduces", "rccl_ranks", read only)
  *   "debug_stop_phase" (test hook, see bk_debug_intervals)
  *   "chunk_reads" (reads per pass over the phases)   "max_read_len"   "site_chunk" (requests bk_site_octamers stages at a time)
+ *   "primer_chunk" (requests bk_primer_correct stages at a time; "primer_buf_bytes": what its staging holds now, read only)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -521,6 +524,41 @@ int  bk_site_octamers(bk_ctx *ctx, const bk_site_req *reqs, uint64_t n, int32_t 
 /* the same HBM to HBM on the context's GPU (d_out 8-byte aligned); asynchronous on the context's stream unless `sync`.  The caller
  * guarantees the requests (one whose chrom_id is no sequence of the index comes back as "nothing fetched") */
 int  bk_site_octamers_device(bk_ctx *ctx, const void *d_reqs, uint64_t n, int32_t rel_ofs, void *d_out, int sync);
+
+/* ---- 5' primer artefact correction (-6) ----------------------------------------------------------- */
+/* The per-read half of CAligner::PCR5PrimerCorrect (biokanga/Aligner.cpp:2052-2088) on the GPU: the first BK_PRIMER_KLEN bases of a
+ * read as loaded against the target it aligned to - the target's bases from MatchLoci for '+'; for '-' the last BK_PRIMER_KLEN bases
+ * of the match, reversed, codes 0..3 complemented - from the 4-bit target resident in HBM.  Mismatches (read code & 7 against what
+ * GetSeq answers; the indexer cleared the FASTA's lower-case flag, so that is 0..4) are corrected left to right until the count is
+ * down to max_mms; a read that cannot get there is rejected.  Which records are asked about, and what becomes of the answers, is host
+ * policy above this boundary (biokanga_amd/csrc/host/primer_correct.h). */
+#define BK_PRIMER_KLEN 12        /* KLen of PCR5PrimerCorrect (Aligner.h:782) */
+typedef struct bk_primer_req {
+    uint64_t codes;              /* the read's first 12 base codes (& 7), 3 bits each, the first in bits 35..33, the last in bits 2..0 */
+    uint32_t chrom_id;           /* Seg[0].ChromID                                                          */
+    uint32_t match_loci;         /* Seg[0].MatchLoci                                                        */
+    uint16_t match_len;          /* Seg[0].MatchLen (= the read's length), >= BK_PRIMER_KLEN                 */
+    uint8_t  strand;             /* '+' | '-'                                                               */
+    uint8_t  low_mm;             /* LowMMCnt                                                                */
+    uint8_t  max_mms;            /* (rate * ReadLen + 50) / 100                                             */
+    uint8_t  reserved[3];
+} bk_primer_req;                 /* 24 bytes */
+enum { BK_PRIMER_UNTOUCHED = 0, BK_PRIMER_CORRECTED = 1, BK_PRIMER_REJECTED = 2, BK_PRIMER_BAD = 0x80 };
+typedef struct bk_primer_res {
+    uint64_t codes;              /* the 12 codes afterwards, laid out as in the request (corrected ones hold the target's code) */
+    uint16_t mask;               /* corrected positions: bit k = base k of the read                         */
+    uint8_t  status;             /* BK_PRIMER_*; BK_PRIMER_BAD: no such sequence or a window outside it, nothing fetched */
+    uint8_t  mismatches;         /* the new LowMMCnt (the request's where nothing was corrected)            */
+    uint8_t  n_corrected;        /* bases corrected                                                         */
+    uint8_t  reserved[3];
+} bk_primer_res;                 /* 16 bytes */
+/* host arrays, blocking; staged through buffers of the context in chunks (made by the first call: a run without -6 allocates nothing).
+ * BK_ERR_PARAMS before anything is launched: a chrom_id that is no sequence of the index, a strand other than '+' / '-',
+ * match_len < BK_PRIMER_KLEN, a match that leaves its sequence.  n == 0 launches nothing */
+int  bk_primer_correct(bk_ctx *ctx, const bk_primer_req *reqs, uint64_t n, bk_primer_res *out);
+/* the same HBM to HBM on the context's GPU (d_reqs 8-byte, d_out 16-byte aligned); asynchronous on the context's stream unless `sync`.
+ * The caller guarantees the requests (a bad one comes back BK_PRIMER_BAD, nothing fetched) */
+int  bk_primer_correct_device(bk_ctx *ctx, const void *d_reqs, uint64_t n, void *d_out, int sync);
 
 /* ---- SAM records formatted on the device -------------------------------------------------------------------------
  * CAligner::ReportBAMread (biokanga/Aligner.cpp:5768-6126; CSAMfile::AddAlignment, SAMfile.cpp:2100-2283) prints one text line per
