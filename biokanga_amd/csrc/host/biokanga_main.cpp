@@ -708,14 +708,16 @@ int align_reads(const std::vector<bk_ctx *> &ctxs, std::vector<bk_stream *> &st,
 }
 
 // CAligner::ProcCoredApprox for MLMode != eMLdefault (Aligner.cpp:9241-9424): what becomes of the reads that aligned to more than one
-// locus (-r1 statistics, -r2 random pick, -r3 / -r4 clustering, -r5 every locus its own record).  `src` maps the records of -r5 back
-// to their reads; `nr` is the record count afterwards.
-// `rec_trims` (with -c only): per record the end trims its placement carries - those of the locus chosen for it, or of the read's own
+// locus (-r1 statistics, -r2 random pick, -r3 / -r4 clustering, -r5 every locus its own record).  rec.src maps the records of -r5 back
+// to their reads (the records then replace the reads in A.hits, which rec views).
+// rec.rec_trims (with -c only): per record the end trims its placement carries - those of the locus chosen for it, or of the read's own
 // unique chimeric placement.
-void resolve_multi_loci(const AlignOpts &o, const ReadStore &rs, AlignedSet &A, std::vector<uint32_t> &src, std::vector<int> &multi_dist, size_t &nr,
-                        std::vector<bk_loci_trims> &rec_trims, const std::vector<uint8_t> *chrom_ok)
+void resolve_multi_loci(const AlignOpts &o, const ReadStore &rs, AlignedSet &A, bk::RecordSet &rec, std::vector<int> &multi_dist, const std::vector<uint8_t> *chrom_ok)
 {
     std::vector<bk_hit> &hits = A.hits;
+    std::vector<uint32_t> &src = rec.src;
+    std::vector<bk_loci_trims> &rec_trims = rec.rec_trims;
+    const size_t nr = hits.size();
     const std::vector<uint64_t> &l_offs = A.l_offs;
     const std::vector<bk_loci> &loci = A.loci;
     const bool with_trims = o.P.min_chimeric_len > 0;
@@ -836,7 +838,6 @@ void resolve_multi_loci(const AlignOpts &o, const ReadStore &rs, AlignedSet &A, 
         diag("Treating accepted %llu multialigned reads as uniquely aligned %llu source reads in subsequent processing",
              (unsigned long long)n_multi, (unsigned long long)(n_loci - n_uniq));
         hits.swap(recs);
-        nr = hits.size();
     }
 }
 
@@ -860,9 +861,75 @@ time_t g_t0 = 0;
     _exit(rc);
 }
 
-int cmd_align(int argc, char **argv, int first)
-{
+// The contexts of a run, one per device: destroyed here and nowhere else (a large run ends in end_process() without coming by).
+struct Contexts {
+    std::vector<bk_ctx *> v;
+    ~Contexts()
+    {
+        if (v.empty()) return;
+        HostClock clk;
+        for (bk_ctx *c : v) bk_ctx_destroy(c);
+        clk.lap("contexts destroyed");
+    }
+};
+
+// One `align` run, from its options to its files.  The members stand in the order the run makes them and go in the reverse one:
+//  - the contexts outlive everything that works on a device: the head start's worker thread (joined by PrepGuard, or by the releaser
+//    thread that Submission and Unlock join) reads its context until it ends
+//  - Unlock is declared after the read store and A: runs before either goes - the releaser thread may still be giving the read store's
+//    bases back
+//  - PrepGuard goes before Unlock and Submission: it waits until the releaser has looked at the head start, then gives it back
+struct AlignRun {
+    // the options, and what follows from them and the input files' sizes before anything is loaded
     Args a;
+    AlignOpts o;
+    DeviceContam contam;                           // -H: the loaders' matcher, on the first device
+    ContamTrimming contam_trims;
+    ContamTrimming *ct = nullptr;                  // (null without -H)
+    uint64_t est_reads = 0, plain_bytes = 0;
+    bool all_plain = true, long_run = false;
+    std::string opath;                             // -o
+    bool sam_plain = false, pre_early = false;     // SAM text into a regular file / whose pages are made from the start of the run on
+    uint32_t ctx_flags = 0;                        // bk_image_policy and its overrides
+    std::string wa;                                // --window-array as given
+    bool wa_off = false, want_array = false;
+    // the contexts, one per device, and the threads that load their index images
+    size_t ndev = 1;
+    Contexts ctxs;
+    bk_ctx *ctx = nullptr;                         // the first device's
+    std::vector<int> ctx_rc;
+    std::vector<std::thread> loaders;
+    int load_rc = 0;                               // what the read loader returned while they ran
+    // the index's entries
+    std::string species;
+    uint32_t n_ent = 0;
+    std::vector<bk_entry_info> ents;
+    Submission S;
+    SamPrealloc pre;
+    ReadStore rs;
+    AlignedSet A;
+    struct Unlock { Submission &S; ~Unlock() { if (S.releaser.joinable()) S.releaser.join(); S.release_results(); } } unlock_results{S};
+    // the SAM formatter's head start on the device
+    bk_sam_prep *sam_prep = nullptr;
+    bk_sam_job pk_job{};
+    struct PrepGuard { bk_sam_prep *&p; Submission &S; ~PrepGuard() { if (p) { S.done_with_head_start(); bk_sam_prep_free(p); p = nullptr; } } } prep_guard{sam_prep, S};      // (not consumed: given back)
+    bool bases_dropped = false;
+    // the records, and what the steps behind the alignment make of them
+    bk::RecordSet rec{A.hits, A.seg2, {}, {}, {}};
+    std::vector<int> multi_dist;
+    std::vector<uint8_t> chrom_ok;                 // -Z / -z: AcceptThisChromID by chrom_id (empty: no expressions)
+    uint64_t nar[20] = {0};                        // ReportAlignStats: records per NAR
+    std::vector<uint32_t> order;                   // SortReadHits(eRSMHitMatch): index in load (ReadID) order -> reference order
+    bk::SitePrefs site_prefs;                      // -8
+    bool with_site_prefs = false;
+
+    std::vector<const char *> entry_names() const { std::vector<const char *> n; for (const bk_entry_info &e : ents) n.push_back(e.name); return n; }
+};
+
+// Every stage below: 0, or 1 after its error message has been logged.
+
+int parse_align_args(int argc, char **argv, int first, Args &a)
+{
     std::string err;
     std::map<std::string, std::string> ln = {
         {"mode", "m"}, {"alignstrand", "Q"}, {"editdelta", "e"}, {"substitutions", "s"}, {"maxns", "n"}, {"trim5", "y"},
@@ -882,189 +949,205 @@ int cmd_align(int argc, char **argv, int first)
                         "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full]\n", g_proc.c_str());
         return 1;
     }
-    if (a.has("F")) g_logfile = fopen(a.str("F").c_str(), "a");
-    diag("Subprocess align Version %s starting", kProgVer);
-    AlignOpts o;
-    if (read_align_opts(a, o)) return 1;
-    // -H: the contaminants file is read and its matcher made on the first device before anything else (CAligner::Align loads it in front of
-    // the index, Aligner.cpp:253-270); the matcher needs no index, so it trims the reads while the index image is still travelling
-    DeviceContam contam;
-    ContamTrimming contam_trims;
-    const bool with_contam = a.has("H") && !a.str("H").empty();
-    if (with_contam) {
-        const std::string cf = a.str("H");
-        char line[4200];
-        snprintf(line, sizeof(line), "Contaminant sequences file: '%s'\n", cf.c_str());      // (a parameter line: no time stamp in front)
-        fputs(line, stdout);
-        if (g_logfile) fputs(line, g_logfile);
-        std::vector<ContamEntry> entries;
-        if (load_contaminants(cf, entries)) { diag("Unable to load contaminate sequences file '%s'", cf.c_str()); return 1; }
-        if (const int crc = contam.create(o.devices[0], entries)) { diag("Fatal: unable to set up the contaminant matcher on device %d: %s", o.devices[0], bk_strerror(crc)); return 1; }
-        contam_trims.matcher = &contam;
-        contam_trims.keep = true;
-    }
-    ContamTrimming *const ct = with_contam ? &contam_trims : nullptr;
+    return 0;
+}
+
+// -H: the contaminants file is read and its matcher made on the first device before anything else (CAligner::Align loads it in front of
+// the index, Aligner.cpp:253-270); the matcher needs no index, so it trims the reads while the index image is still travelling
+int make_contam_matcher(AlignRun &r)
+{
+    if (!r.a.has("H") || r.a.str("H").empty()) return 0;
+    const std::string cf = r.a.str("H");
+    param_line("Contaminant sequences file: '%s'\n", cf.c_str());
+    std::vector<ContamEntry> entries;
+    if (load_contaminants(cf, entries)) { diag("Unable to load contaminate sequences file '%s'", cf.c_str()); return 1; }
+    if (const int crc = r.contam.create(r.o.devices[0], entries)) { diag("Fatal: unable to set up the contaminant matcher on device %d: %s", r.o.devices[0], bk_strerror(crc)); return 1; }
+    r.contam_trims.matcher = &r.contam;
+    r.contam_trims.keep = true;
+    r.ct = &r.contam_trims;
+    return 0;
+}
+
+int print_param_lines(const AlignOpts &o)
+{
     if (!o.site_prefs_path.empty()) {               // (parameter lines, kanga.cpp:1290-1293)
-        char line[4300];
-        snprintf(line, sizeof(line), "Offset read start sites when processing site octamer preferencing: %d\nAligned read octamer site preferencing into this file: '%s'\n",
-                 o.site_prefs_ofs, o.site_prefs_path.c_str());
-        fputs(line, stdout);
-        if (g_logfile) fputs(line, g_logfile);
+        param_line("Offset read start sites when processing site octamer preferencing: %d\nAligned read octamer site preferencing into this file: '%s'\n",
+                   o.site_prefs_ofs, o.site_prefs_path.c_str());
         OutBuf sp_file;                             // the reference creates the file before it loads anything (an empty one stays when no read is accepted)
         sp_file.open(o.site_prefs_path.c_str());
         if (sp_file.fd < 0) { diag("Fatal: unable to create '%s'", o.site_prefs_path.c_str()); return 1; }
         sp_file.close();
     }
-    if (o.primer_subs > 0) {                        // (parameter line, kanga.cpp:1146-1147)
-        char line[80];
-        snprintf(line, sizeof(line), "correcting PCR 5' artefacts : %d\n", o.primer_subs);
-        fputs(line, stdout);
-        if (g_logfile) fputs(line, g_logfile);
-    }
+    if (o.primer_subs > 0) param_line("correcting PCR 5' artefacts : %d\n", o.primer_subs);      // (kanga.cpp:1146-1147)
+    return 0;
+}
 
-    // index images travel to the devices (one loader thread each) while this thread parses the reads: the two longest serial steps
-    // of a run overlap (the reference loads its reads in the background of the alignment instead, Aligner.cpp:4820-4860)
-    diag("Loading suffix array file '%s'", a.str("I").c_str());
-    const size_t ndev = o.devices.size();
-    std::vector<bk_ctx *> ctxs(ndev, nullptr);
-    std::vector<int> ctx_rc(ndev, 0);
-    std::vector<std::thread> loaders;
-    // the first device reads the .sfx and builds the tables; the others receive the finished image device to device (xGMI)
-    // The image pays from BK_POLICY_MIN_READS reads per device on (bk_image_policy).  The decision is made HERE, from the size of
-    // the input files, before a single read is parsed: the array then comes with the index image (made behind the slices of the suffix
-    // array's upload) instead of in front of the first batch.  A FASTA record of a 100-base read is about 120 bytes, a FASTQ one about
-    // 250; gzip'd files hold about four times their size.
-    uint64_t est_reads = 0, plain_bytes = 0;
-    bool all_plain = true;
+// The image pays from BK_POLICY_MIN_READS reads per device on (bk_image_policy).  The decision is made HERE, from the size of
+// the input files, before a single read is parsed: the array then comes with the index image (made behind the slices of the suffix
+// array's upload) instead of in front of the first batch.  A FASTA record of a 100-base read is about 120 bytes, a FASTQ one about
+// 250; gzip'd files hold about four times their size.
+void estimate_input(AlignRun &r)
+{
     for (const char *opt : {"i", "u"})
-        if (a.has(opt))
-            for (const std::string &fn : a.v[opt]) {
+        if (r.a.has(opt))
+            for (const std::string &fn : r.a.v[opt]) {
                 // (gzip'd files too: they are inflated whole like plain ones are mapped, and say - bgzip'd ones exactly - how much text they hold)
                 const uint64_t text = bk::text_bytes_estimate(fn);
                 if (!text) continue;
                 const bool fq = fn.find(".fq") != std::string::npos || fn.find(".fastq") != std::string::npos;
-                est_reads += text / (fq ? 250 : 120);
-                plain_bytes += text;
-                all_plain = all_plain && o.nthreads > 1;
+                r.est_reads += text / (fq ? 250 : 120);
+                r.plain_bytes += text;
+                r.all_plain = r.all_plain && r.o.nthreads > 1;
             }
-    Submission S;
-    if (all_plain && plain_bytes >= (256u << 20)) S.start_early(plain_bytes, (uint32_t)std::max(15, o.min_len));
+    r.long_run = r.est_reads / r.ndev >= kLongRunMinReads;
+}
+
+void start_early_buffers(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    if (r.all_plain && r.plain_bytes >= (256u << 20)) r.S.start_early(r.plain_bytes, (uint32_t)std::max(15, o.min_len));
     // SAM text goes into a file of known approximate size.  A large plain-text input tells that size now (a record is the read's name and
     // bases - and qualities - as the input holds them plus about 31 bytes, 55 for a paired end; a FASTA record of 100 bases is 117 bytes):
     // the file's pages are allocated, zeroed and mapped by background threads from here on - 7 GB for 50 M reads of 100 bases, which the
-    // writers would otherwise wait for.  Other inputs: once the reads are loaded (below).
-    SamPrealloc pre;
-    const std::string opath0 = a.str("o");
+    // writers would otherwise wait for.  Other inputs: once the reads are loaded (start_sam_file_late).
+    r.opath = r.a.str("o");
     struct stat ost;
-    const bool out_special = stat(opath0.c_str(), &ost) == 0 && !S_ISREG(ost.st_mode);      // a FIFO, /dev/fd/N of a process substitution, /dev/null
-    const bool sam_plain = o.fmt >= 5 && !out_special && !(opath0.size() > 5 && !strcasecmp(opath0.c_str() + opath0.size() - 4, ".bam")) &&
-                           !(opath0.size() > 3 && !strcasecmp(opath0.c_str() + opath0.size() - 3, ".gz"));
-    const bool pre_early = sam_plain && all_plain && plain_bytes >= bk::env::sam_early_min(256ULL << 20);      // (tests lower the input size from which the file is started early)
-    const uint64_t pre_early_est = (1u << 20) + plain_bytes + plain_bytes / (o.pe_mode ? 2 : 3);
-    if (pre_early) pre.start(opath0.c_str(), pre_early_est, 2);
-    const bool long_run = est_reads / ndev >= kLongRunMinReads;
-    // bk_image_policy, from the reads a device is going to align; --window-array on | off and --index-image lean | full override its two halves
-    uint32_t ctx_flags = bk_image_policy(est_reads / ndev);
-    const std::string wa = a.has("window-array") ? a.str("window-array") : std::string();
-    const bool wa_off = wa == "off" || wa == "0" || wa == "no";
-    if (wa_off) ctx_flags &= ~BK_CTX_WINDOW_ARRAY_EAGER;
-    else if (!wa.empty()) ctx_flags |= BK_CTX_WINDOW_ARRAY_EAGER;
-    const bool want_array = (ctx_flags & BK_CTX_WINDOW_ARRAY_EAGER) != 0;
-    const std::string img = a.has("index-image") ? a.str("index-image") : std::string();
-    if (img == "full") ctx_flags &= ~(BK_CTX_GROW_IMAGE | BK_CTX_LEAN_IMAGE);
-    else if (img == "lean") ctx_flags = (ctx_flags & ~BK_CTX_GROW_IMAGE) | BK_CTX_LEAN_IMAGE;
-    loaders.emplace_back([&]() {
-        ctx_rc[0] = bk_ctx_create_ex(&ctxs[0], a.str("I").c_str(), o.devices[0], &o.P, ctx_flags);
-        if (ctx_rc[0] || ndev == 1) return;
+    const bool out_special = stat(r.opath.c_str(), &ost) == 0 && !S_ISREG(ost.st_mode);      // a FIFO, /dev/fd/N of a process substitution, /dev/null
+    r.sam_plain = o.fmt >= 5 && !out_special && !is_bam_name(r.opath) && !is_gz_name(r.opath);
+    r.pre_early = r.sam_plain && r.all_plain && r.plain_bytes >= bk::env::sam_early_min(256ULL << 20);      // (tests lower the input size from which the file is started early)
+    const uint64_t pre_early_est = (1u << 20) + r.plain_bytes + r.plain_bytes / (o.pe_mode ? 2 : 3);
+    if (r.pre_early) r.pre.start(r.opath.c_str(), pre_early_est, 2);
+}
+
+// bk_image_policy, from the reads a device is going to align; --window-array on | off and --index-image lean | full override its two halves
+void choose_index_image(AlignRun &r)
+{
+    r.ctx_flags = bk_image_policy(r.est_reads / r.ndev);
+    r.wa = r.a.has("window-array") ? r.a.str("window-array") : std::string();
+    r.wa_off = r.wa == "off" || r.wa == "0" || r.wa == "no";
+    if (r.wa_off) r.ctx_flags &= ~BK_CTX_WINDOW_ARRAY_EAGER;
+    else if (!r.wa.empty()) r.ctx_flags |= BK_CTX_WINDOW_ARRAY_EAGER;
+    r.want_array = (r.ctx_flags & BK_CTX_WINDOW_ARRAY_EAGER) != 0;
+    const std::string img = r.a.has("index-image") ? r.a.str("index-image") : std::string();
+    if (img == "full") r.ctx_flags &= ~(BK_CTX_GROW_IMAGE | BK_CTX_LEAN_IMAGE);
+    else if (img == "lean") r.ctx_flags = (r.ctx_flags & ~BK_CTX_GROW_IMAGE) | BK_CTX_LEAN_IMAGE;
+}
+
+int load_all_reads(AlignRun &r, int nthreads, ReadStore &into)
+{
+    const AlignOpts &o = r.o;
+    return o.pe_mode ? load_reads_pe(r.a.v["i"], r.a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, nthreads, into, r.ct)
+                     : load_reads(r.a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, nthreads, into, r.ct);
+}
+
+// index images travel to the devices (one loader thread each) while this thread parses the reads: the two longest serial steps
+// of a run overlap (the reference loads its reads in the background of the alignment instead, Aligner.cpp:4820-4860).
+// The loader threads run from here until pack_reads_and_join_index() has joined them: nothing returns early in between, which is
+// why this stage keeps its result in load_rc.
+void load_reads_behind_index(AlignRun &r)
+{
+    // the first device reads the .sfx and builds the tables; the others receive the finished image device to device (xGMI)
+    r.ctxs.v.assign(r.ndev, nullptr);
+    r.ctx_rc.assign(r.ndev, 0);
+    r.loaders.emplace_back([&r]() {
+        r.ctx_rc[0] = bk_ctx_create_ex(&r.ctxs.v[0], r.a.str("I").c_str(), r.o.devices[0], &r.o.P, r.ctx_flags);
+        if (r.ctx_rc[0] || r.ndev == 1) return;
         std::vector<std::thread> cloners;
-        for (size_t d = 1; d < ndev; d++) cloners.emplace_back([&, d]() { ctx_rc[d] = bk_ctx_clone(&ctxs[d], ctxs[0], o.devices[d]); });
+        for (size_t d = 1; d < r.ndev; d++) cloners.emplace_back([&r, d]() { r.ctx_rc[d] = bk_ctx_clone(&r.ctxs.v[d], r.ctxs.v[0], r.o.devices[d]); });
         for (auto &t : cloners) t.join();
     });
-    auto destroy_ctxs = [&]() { for (bk_ctx *c : ctxs) bk_ctx_destroy(c); };
-    ReadStore rs;
-    int rc;
     // (the index loader's threads - the HIP runtime coming up, four feeding the upload - the page-locking of the packed reads' buffers and
     // the output file's pages run meanwhile: the parser leaves them their share of the cores, or a CPU quota stalls all of them in turn)
-    const int parse_threads = std::max(std::min(o.nthreads, 4), o.nthreads - 6);
-    if (o.pe_mode) rc = load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs, ct);
-    else rc = load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, parse_threads, rs, ct);
-    contam.destroy();                               // (its staging and device buffers have served)
-    // .. and, still behind the index load: the reads packed for the boundary, the result array page-locked
-    AlignedSet A;
-    // (declared after the read store and A: runs before either goes - the releaser thread may still be giving the read store's bases back)
-    struct Unlock { Submission &S; ~Unlock() { if (S.releaser.joinable()) S.releaser.join(); S.release_results(); } } unlock_results{S};
-    if (!rc && rs.size()) rc = prepare_submission(o, rs, ndev, long_run, A, S);
-    if (!rc && pre_early) pre.add_threads(2);       // (two while the parser's threads allocate their own memory, four from here on)
-    { HostClock jc; for (auto &t : loaders) t.join(); jc.lap("waited for the index image"); }
-    for (size_t d = 0; d < ndev; d++)
-        if (ctx_rc[d]) { diag("Fatal: unable to load genome assembly suffix array: %s", bk_strerror(ctx_rc[d])); destroy_ctxs(); return 1; }
-    if (rc) { destroy_ctxs(); return 1; }
-    bk_ctx *ctx = ctxs[0];
-    std::string species = bk_dataset_name(ctx);
-    uint32_t n_ent = bk_num_entries(ctx);
-    std::vector<bk_entry_info> ents(n_ent);
-    for (uint32_t i = 0; i < n_ent; i++) bk_get_entry(ctx, i, &ents[i]);
-    diag("Genome Assembly Name: '%s'", species.c_str());
-    diag("Genome assembly suffix array loaded");
+    const int parse_threads = std::max(std::min(r.o.nthreads, 4), r.o.nthreads - 6);
+    r.load_rc = load_all_reads(r, parse_threads, r.rs);
+    r.contam.destroy();                             // (its staging and device buffers have served)
+}
 
-    size_t nr = rs.size();
+// .. and, still behind the index load: the reads packed for the boundary, the result array page-locked
+int pack_reads_and_join_index(AlignRun &r)
+{
+    int rc = r.load_rc;
+    if (!rc && r.rs.size()) rc = prepare_submission(r.o, r.rs, r.ndev, r.long_run, r.A, r.S);
+    if (!rc && r.pre_early) r.pre.add_threads(2);   // (two while the parser's threads allocate their own memory, four from here on)
+    { HostClock jc; for (auto &t : r.loaders) t.join(); jc.lap("waited for the index image"); }
+    for (size_t d = 0; d < r.ndev; d++)
+        if (r.ctx_rc[d]) { diag("Fatal: unable to load genome assembly suffix array: %s", bk_strerror(r.ctx_rc[d])); return 1; }
+    if (rc) return 1;
+    r.ctx = r.ctxs.v[0];
+    r.species = bk_dataset_name(r.ctx);
+    r.n_ent = bk_num_entries(r.ctx);
+    r.ents.resize(r.n_ent);
+    for (uint32_t i = 0; i < r.n_ent; i++) bk_get_entry(r.ctx, i, &r.ents[i]);
+    diag("Genome Assembly Name: '%s'", r.species.c_str());
+    diag("Genome assembly suffix array loaded");
+    return 0;
+}
+
+void tune_and_describe_image(AlignRun &r)
+{
     // (the other devices' contexts, copies of the first's image, make their window arrays when their first batch arrives)
     // (--window-array on asks for it whatever the index: one of 5-byte elements gets it only so - "use_swin" 2 -, the policy's own
     // choice leaves it without: making it goes over a 17 Gbp index twice)
-    for (bk_ctx *c : ctxs) (void)bk_ctx_tune(c, "use_swin", want_array ? ((!wa.empty() && !wa_off) ? 2 : 1) : 0);
+    for (bk_ctx *c : r.ctxs.v) (void)bk_ctx_tune(c, "use_swin", r.want_array ? ((!r.wa.empty() && !r.wa_off) ? 2 : 1) : 0);
     diag("Index image: %s, suffix-ordered window array %s (%zu reads per device, %llu estimated from the input files' sizes; every table comes with the index from %llu reads per device on; --index-image lean | full and --window-array on | off override)",
-         (ctx_flags & BK_CTX_LEAN_IMAGE) ? "lean" : ((ctx_flags & BK_CTX_GROW_IMAGE) ? "lean, grows on a long run" : "every table"),
-         !want_array ? "off" : ((bk_sfx_el_size(ctx) == 5 && (wa.empty() || wa_off)) ? "off (an index of 5-byte elements gets it with --window-array on only)" : "on"), nr / ctxs.size(),
-         (unsigned long long)(est_reads / ndev), (unsigned long long)BK_POLICY_MIN_READS);
-    // (the SAM file of any other large run is started now: name + bases (+ qualities) + about 31 bytes per record, 55 for a paired end)
-    if (sam_plain && pre.fd < 0) {
-        if (nr >= (size_t)bk::env::sam_device_min(200000ULL)) {               // (tests lower the size from which the large-run machinery is used)
-            uint64_t est = (1u << 20) + rs.name_bytes() + 40ULL * nr + (o.pe_mode ? 24ULL * nr : 0) + (uint64_t)n_ent * 128;
-            est += (uint64_t)(a.num("g", 3) != 3 ? 2 : 1) * rs.base_bytes();
-            pre.start(opath0.c_str(), est);
-        }
-    }
-    // CAligner::AcceptThisChromID (Aligner.cpp:2651-2715): a sequence passes unless an exclude expression matches its name, and - with include
-    // expressions present - only if one of those does too (exclusion first: not the rule of FiltByChroms further down)
-    std::vector<uint8_t> chrom_ok;
-    if (!o.re_excl.empty() || !o.re_incl.empty()) {
-        chrom_ok.assign(n_ent + 1, 1);
-        for (uint32_t c = 1; c <= n_ent; c++) {
-            regmatch_t mc;
-            bool ok = true;
-            for (regex_t &re : o.re_excl) if (!regexec(&re, ents[c - 1].name, 1, &mc, 0)) { ok = false; break; }
-            if (ok && !o.re_incl.empty()) {
-                ok = false;
-                for (regex_t &re : o.re_incl) if (!regexec(&re, ents[c - 1].name, 1, &mc, 0)) { ok = true; break; }
-            }
-            chrom_ok[c] = ok ? 1 : 0;
-        }
-    }
+         (r.ctx_flags & BK_CTX_LEAN_IMAGE) ? "lean" : ((r.ctx_flags & BK_CTX_GROW_IMAGE) ? "lean, grows on a long run" : "every table"),
+         !r.want_array ? "off" : ((bk_sfx_el_size(r.ctx) == 5 && (r.wa.empty() || r.wa_off)) ? "off (an index of 5-byte elements gets it with --window-array on only)" : "on"), r.rs.size() / r.ctxs.v.size(),
+         (unsigned long long)(r.est_reads / r.ndev), (unsigned long long)BK_POLICY_MIN_READS);
+}
+
+// (the SAM file of any other large run is started now: name + bases (+ qualities) + about 31 bytes per record, 55 for a paired end)
+void start_sam_file_late(AlignRun &r)
+{
+    const size_t nr = r.rs.size();
+    if (!r.sam_plain || r.pre.fd >= 0) return;
+    if (nr < (size_t)bk::env::sam_device_min(200000ULL)) return;                // (tests lower the size from which the large-run machinery is used)
+    uint64_t est = (1u << 20) + r.rs.name_bytes() + 40ULL * nr + (r.o.pe_mode ? 24ULL * nr : 0) + (uint64_t)r.n_ent * 128;
+    est += (uint64_t)(g_qual_mode != 3 ? 2 : 1) * r.rs.base_bytes();
+    r.pre.start(r.opath.c_str(), est);
+}
+
+// -Z / -z by CAligner::AcceptThisChromID (chrom_accept_table: exclusion first, not the rule of FiltByChroms further down)
+int make_accept_table(AlignRun &r)
+{
+    if (r.o.re_excl.empty() && r.o.re_incl.empty()) return 0;
+    const std::vector<uint8_t> ok = bk::chrom_accept_table(r.entry_names(), r.o.re_excl, r.o.re_incl);
+    r.chrom_ok.assign(1, 1);                        // (indexed by chrom_id, which counts from 1)
+    r.chrom_ok.insert(r.chrom_ok.end(), ok.begin(), ok.end());
     // the paired-end rules consult the filters while they pair (AcceptProvPE, the orphan recovery's anchors, the single-end acceptance)
-    if (o.pe_mode && !chrom_ok.empty())
-        for (bk_ctx *c : ctxs)
-            if ((rc = bk_ctx_set_chrom_filter(c, chrom_ok.data(), (uint32_t)chrom_ok.size())) != BK_OK) { diag("Error: chromosome filter table: %s", bk_strerror(rc)); destroy_ctxs(); return 1; }
+    if (r.o.pe_mode)
+        for (bk_ctx *c : r.ctxs.v)
+            if (const int rc = bk_ctx_set_chrom_filter(c, r.chrom_ok.data(), (uint32_t)r.chrom_ok.size())) { diag("Error: chromosome filter table: %s", bk_strerror(rc)); return 1; }
+    return 0;
+}
+
+int run_alignment(AlignRun &r)
+{
+    const size_t nr = r.rs.size();
     // the pipelines' device buffers and the contexts' batch scratch are in place before the clock of T_align starts (the reference sizes its
     // per-thread scratch before its workers start, Aligner.cpp:8771-8790)
     std::vector<bk_stream *> streams;
-    if (nr && open_pipelines(ctxs, o, S, streams)) { destroy_ctxs(); return 1; }
-    diag("Now aligning with minimum core size of %dbp...\n", bk_min_core_len(ctx));
-    if (o.pe_mode) diag("Paired end association and partner alignment processing runs with the alignment of each batch");
-    rc = nr ? align_reads(ctxs, streams, o, rs, S, A) : BK_OK;
-    if (rc) { destroy_ctxs(); return 1; }
-    if (!nr) A.seq_counts.assign(n_ent, 0);
-    std::vector<bk_hit> &hits = A.hits;
-    std::vector<bk_seg2> &seg2 = A.seg2;
+    if (nr && open_pipelines(r.ctxs.v, r.o, r.S, streams)) return 1;
+    diag("Now aligning with minimum core size of %dbp...\n", bk_min_core_len(r.ctx));
+    if (r.o.pe_mode) diag("Paired end association and partner alignment processing runs with the alignment of each batch");
+    if (nr && align_reads(r.ctxs.v, streams, r.o, r.rs, r.S, r.A)) return 1;
+    if (!nr) r.A.seq_counts.assign(r.n_ent, 0);
     diag("Alignment of %zu from %zu loaded completed", nr, nr);
-    // the SAM records of a large run are formatted by the device (report.cpp): what it needs of the reads travels there while the
-    // host resolves, filters and sorts.  The head start is given the READS, in every mode: -r5's records are made later and come with
-    // the job of bk_sam_format, which names the read of each (bk_sam_job.src, n_src_reads = the reads handed over here)
-    bk_sam_prep *sam_prep = nullptr;
-    bk_sam_job pk_job{};
-    struct PrepGuard { bk_sam_prep *&p; Submission &S; ~PrepGuard() { if (p) { S.done_with_head_start(); bk_sam_prep_free(p); p = nullptr; } } } prep_guard{sam_prep, S};      // (not consumed: given back)
+    return 0;
+}
+
+// the SAM records of a large run are formatted by the device (report.cpp): what it needs of the reads travels there while the
+// host resolves, filters and sorts.  The head start is given the READS, in every mode: -r5's records are made later and come with
+// the job of bk_sam_format, which names the read of each (bk_sam_job.src, n_src_reads = the reads handed over here)
+void start_sam_head(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    const Args &a = r.a;
+    ReadStore &rs = r.rs;
+    Submission &S = r.S;
+    const size_t nr = rs.size();
     // (-6 overwrites bases of the read store further down: no head start then - the formatter uploads the byte form, corrected, when
     // the records are written, and the bases are never dropped: may_drop_bases needs the head start)
-    if (pre.fd >= 0 && nr == rs.lens.size() && o.primer_subs == 0) {
+    if (r.pre.fd >= 0 && r.rec.size() == rs.lens.size() && o.primer_subs == 0) {
         bk_sam_job hj{};
         hj.bases = rs.bases.data(); hj.n_bases = rs.bases.size(); hj.offs = rs.offs.data(); hj.lens = rs.lens.data();
         hj.names = rs.names.data(); hj.n_name_bytes = rs.names.size(); hj.name_ofs = rs.name_ofs.data(); hj.n_reads = nr;
@@ -1074,355 +1157,366 @@ int cmd_align(int argc, char **argv, int first)
             hj.pk_words = S.words; hj.n_pk_words = S.n_words; hj.pk_lens16 = S.lens16; hj.pk_exc = S.exc_job.data(); hj.n_pk_exc = S.exc_job.size();
             hj.bases = nullptr; hj.n_bases = 0; hj.offs = nullptr; hj.lens = nullptr;
         }
-        pk_job = hj;
-        const uint64_t per_rec = (rs.name_bytes() + (uint64_t)(a.num("g", 3) != 3 ? 2 : 1) * rs.base_bytes()) / std::max<size_t>(nr, 1) + 64 + (o.pe_mode ? 24 : 0);
-        if (bk_sam_prepare(ctx, &hj, (uint32_t)std::min<uint64_t>(per_rec + per_rec / 8, 1u << 20), &sam_prep) != BK_OK) { sam_prep = nullptr; pk_job = bk_sam_job{}; }
+        r.pk_job = hj;
+        const uint64_t per_rec = (rs.name_bytes() + (uint64_t)(g_qual_mode != 3 ? 2 : 1) * rs.base_bytes()) / std::max<size_t>(nr, 1) + 64 + (o.pe_mode ? 24 : 0);
+        if (bk_sam_prepare(r.ctx, &hj, (uint32_t)std::min<uint64_t>(per_rec + per_rec / 8, 1u << 20), &r.sam_prep) != BK_OK) { r.sam_prep = nullptr; r.pk_job = bk_sam_job{}; }
     }
     // The read store's bases - 5 GB of a 50 M-read run, a third of a second to hand back at the exit - have served too once the device
     // holds the packed reads, unless an output of this run still reads them (-j / -J, -O, SNP calling); should the device decline
     // after all, the host formatter loads them again (restore_reads)
-    bool bases_dropped = false;
     // (.. and only when every read file can be read a second time - a FIFO or a process substitution cannot: should the device decline
     // the SAM records, the host formatter reloads the reads)
     bool inputs_regular = true;
     for (const char *opt : {"i", "u"})
         if (a.has(opt))
-            for (const std::string &fn : a.v[opt]) { struct stat ist; inputs_regular = inputs_regular && stat(fn.c_str(), &ist) == 0 && S_ISREG(ist.st_mode); }
+            for (const std::string &fn : a.v.at(opt)) { struct stat ist; inputs_regular = inputs_regular && stat(fn.c_str(), &ist) == 0 && S_ISREG(ist.st_mode); }
     // (.. and not in the modes whose later steps read the bases on the host: the flank trimmer of -x / -A, the .jct / .ind files of -A / -a,
     // -c's and -r5's records - there the read store stays whole)
     const bool host_reads_bases = o.ml_mode == 5 || o.micro_indel || o.splice_len || o.min_chim || o.min_flank;
-    const bool may_drop_bases = inputs_regular && !host_reads_bases && pk_job.pk_words != nullptr && sam_prep != nullptr && !a.has("j") && !a.has("J") && !a.has("O") && o.snp.min_reads <= 0;
+    const bool may_drop_bases = inputs_regular && !host_reads_bases && r.pk_job.pk_words != nullptr && r.sam_prep != nullptr && !a.has("j") && !a.has("J") && !a.has("O") && o.snp.min_reads <= 0;
     if (nr)
-        S.release_packed_in_background(pk_job.pk_words != nullptr ? sam_prep : nullptr,
-                                       may_drop_bases ? std::function<void()>([&rs, &bases_dropped]() { bk::RawVec<uint8_t> none; rs.bases.swap(none); bases_dropped = true; })
+        S.release_packed_in_background(r.pk_job.pk_words != nullptr ? r.sam_prep : nullptr,
+                                       may_drop_bases ? std::function<void()>([&r]() { bk::RawVec<uint8_t> none; r.rs.bases.swap(none); r.bases_dropped = true; })
                                                       : std::function<void()>());
-    auto restore_reads = [&]() -> int {
-        if (S.releaser.joinable()) S.releaser.join();
-        if (!bases_dropped) return 0;
-        diag("The device declined the SAM records: loading the reads again for the host's formatter");
-        ReadStore again;
-        // (-H: the cuts the first load found are used again, nothing is matched a second time)
-        contam_trims.matcher = nullptr;
-        contam_trims.replay_at = 0;
-        const int rl = o.pe_mode ? load_reads_pe(a.v["i"], a.v["u"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again, ct)
-                                 : load_reads(a.v["i"], o.trim5, o.trim3, o.min_len, o.max_len, o.nthreads, again, ct);
-        if (rl || again.size() != rs.size()) return 1;
-        rs.bases.swap(again.bases); rs.offs.swap(again.offs); rs.used_bases = again.used_bases;
-        bases_dropped = false;
-        return 0;
-    };
+}
 
-    std::vector<uint32_t> src;                     // -r5: record -> read it came from (records replace the reads)
-    std::vector<int> multi_dist((size_t)o.max_ml, 0);
-    std::vector<bk_loci_trims> rec_trims;          // -c with -r: per record (after -r5's expansion) the trims of the placement it took
-    if (o.ml_mode) resolve_multi_loci(o, rs, A, src, multi_dist, nr, rec_trims, chrom_ok.empty() ? nullptr : &chrom_ok);
-    auto RD = [&](size_t i) -> size_t { return src.empty() ? i : (size_t)src[i]; };
-    auto has_seg2 = [&](size_t i) -> bool { return !seg2.empty() && (seg2[RD(i)].flags & 5); };       // FlgInDel or FlgSplice
+// the read store's bases back, should start_sam_head() have dropped them and the device decline the SAM records after all
+int restore_reads(AlignRun &r)
+{
+    ReadStore &rs = r.rs;
+    if (r.S.releaser.joinable()) r.S.releaser.join();
+    if (!r.bases_dropped) return 0;
+    diag("The device declined the SAM records: loading the reads again for the host's formatter");
+    ReadStore again;
+    // (-H: the cuts the first load found are used again, nothing is matched a second time)
+    r.contam_trims.matcher = nullptr;
+    r.contam_trims.replay_at = 0;
+    const int rl = load_all_reads(r, r.o.nthreads, again);
+    if (rl || again.size() != rs.size()) return 1;
+    rs.bases.swap(again.bases); rs.offs.swap(again.offs); rs.used_bases = again.used_bases;
+    r.bases_dropped = false;
+    return 0;
+}
+
+void resolve_multi_and_count_pairs(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    r.multi_dist.assign((size_t)o.max_ml, 0);
+    if (o.ml_mode) resolve_multi_loci(o, r.rs, r.A, r.rec, r.multi_dist, r.chrom_ok.empty() ? nullptr : &r.chrom_ok);
     if (o.pe_mode) {
         // CAligner::ProcessPairedEnds ran on the device with each batch (reads are held interleaved PE1,PE2, Aligner.cpp:11349-11355)
+        const std::vector<bk_hit> &hits = r.rec.hits;
+        const size_t nr = r.rec.size();
         size_t n_pe = 0;
         for (size_t i = 0; i < nr; i += 2) n_pe += (hits[i].flags & 0x80) && (hits[i + 1].flags & 0x80);
         diag("From %zu paired reads there were %zu accepted as paired", nr / 2, n_pe);
     }
+}
 
-    // per-record flank trims in READ orientation (tsSegLoci.TrimLeft / TrimRight / TrimMismatches of Seg[0]), host/post_filters.h
-    bk::FlankTrims trims;
-    auto TL = [&](size_t i) -> uint32_t { return trims.empty() ? 0u : trims.left[i]; };
-    auto TR = [&](size_t i) -> uint32_t { return trims.empty() ? 0u : trims.right[i]; };
-    auto a_start = [&](const bk_hit &h, size_t i) -> uint32_t { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); };      // AdjStartLoci
-    auto a_len = [&](const bk_hit &h, size_t i) -> uint32_t { return (uint32_t)h.match_len - TL(i) - TR(i); };                     // AdjHitLen
-    auto is_chimeric = [&](size_t i) -> bool {                                                          // FlgChimeric: trims come with the hit
-        if (!rec_trims.empty()) return rec_trims[i].chimeric != 0;
-        return !seg2.empty() && (seg2[RD(i)].flags & 8);
-    };
-    if (o.min_chim) {
-        // chimeric placements keep the trims AdaptiveTrim found (ProcCoredApprox :9292-9299); the flank trimmer leaves them alone (:1641)
-        if (trims.empty()) {
-            trims.left.assign(nr, 0); trims.right.assign(nr, 0); trims.mismatches.resize(nr);
-            for (size_t i = 0; i < nr; i++) trims.mismatches[i] = hits[i].mismatches;
+// -c: chimeric placements keep the trims AdaptiveTrim found (ProcCoredApprox :9292-9299); the flank trimmer leaves them alone (:1641)
+void keep_chimeric_trims(bk::RecordSet &rec)
+{
+    rec.ensure_trims();
+    size_t n_ch = 0;
+    for (size_t i = 0; i < rec.size(); i++)
+        if (rec.hits[i].nar == BK_NAR_ACCEPTED && rec.is_chimeric(i)) {
+            rec.trims.left[i] = rec.rec_trims.empty() ? rec.seg2[rec.RD(i)].match_len : rec.rec_trims[i].left;
+            rec.trims.right[i] = rec.rec_trims.empty() ? rec.seg2[rec.RD(i)].read_ofs : rec.rec_trims[i].right;
+            n_ch++;
         }
-        size_t n_ch = 0;
-        for (size_t i = 0; i < nr; i++)
-            if (hits[i].nar == BK_NAR_ACCEPTED && is_chimeric(i)) {
-                trims.left[i] = rec_trims.empty() ? seg2[RD(i)].match_len : rec_trims[i].left;
-                trims.right[i] = rec_trims.empty() ? seg2[RD(i)].read_ofs : rec_trims[i].right;
-                n_ch++;
-            }
-        diag("Of the accepted aligned reads, %zu were chimeric", n_ch);
-    }
-    // CAligner::SortHitMatch (Aligner.cpp:10069-10114), ties left to the replica of the reference's sort.  The comparator's fields are
-    // packed into three words per record first (NAR | NumHits class: 1 before the others | NumHits | ChromID, then AdjStartLoci |
-    // AdjHitLen, then Strand | LowMMCnt; records whose NumHits is not 1 compare equal beyond NumHits, so their other fields stay 0): the
-    // quicksort then walks keys lying next to each other instead of chasing record indexes through the result array - same
-    // comparisons, same outcome, same order
-    struct SortRec { uint64_t hi, lo; uint32_t tail, idx; };
+    diag("Of the accepted aligned reads, %zu were chimeric", n_ch);
+}
+
+// CAligner::SortHitMatch (Aligner.cpp:10069-10114), ties left to the replica of the reference's sort.  The comparator's fields are
+// packed into three words per record first (NAR | NumHits class: 1 before the others | NumHits | ChromID, then AdjStartLoci |
+// AdjHitLen, then Strand | LowMMCnt; records whose NumHits is not 1 compare equal beyond NumHits, so their other fields stay 0): the
+// quicksort then walks keys lying next to each other instead of chasing record indexes through the result array - same
+// comparisons, same outcome, same order
+struct SortRec { uint64_t hi, lo; uint32_t tail, idx; };
+void sorted_order(const bk::RecordSet &rec, int nthreads, std::vector<uint32_t> &ord)
+{
+    const size_t nr = rec.size();
     auto sort_cmp = [](const SortRec &x, const SortRec &y) -> int {
         if (x.hi != y.hi) return x.hi < y.hi ? -1 : 1;
         if (x.lo != y.lo) return x.lo < y.lo ? -1 : 1;
         if (x.tail != y.tail) return x.tail < y.tail ? -1 : 1;
         return 0;
     };
-    auto sorted_order = [&](std::vector<uint32_t> &ord) {
-        bk::RawVec<SortRec> recs(nr);
-        auto fill = [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                const bk_hit &p = hits[i];
-                SortRec &r = recs[i];
-                r.idx = (uint32_t)i;
-                if (p.num_hits == 1) {
-                    r.hi = ((uint64_t)p.nar << 41) | (uint64_t)p.chrom_id;
-                    r.lo = ((uint64_t)a_start(p, i) << 32) | (uint64_t)a_len(p, i);
-                    r.tail = ((uint32_t)p.strand << 8) | (uint32_t)(uint8_t)(p.low_mm + 128);
-                } else {
-                    r.hi = ((uint64_t)p.nar << 41) | (1ULL << 40) | ((uint64_t)p.num_hits << 32);
-                    r.lo = 0;
-                    r.tail = 0;
-                }
+    bk::RawVec<SortRec> recs(nr);
+    auto fill = [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            const bk_hit &p = rec.hits[i];
+            SortRec &r = recs[i];
+            r.idx = (uint32_t)i;
+            if (p.num_hits == 1) {
+                r.hi = ((uint64_t)p.nar << 41) | (uint64_t)p.chrom_id;
+                r.lo = ((uint64_t)rec.a_start(p, i) << 32) | (uint64_t)rec.a_len(p, i);
+                r.tail = ((uint32_t)p.strand << 8) | (uint32_t)(uint8_t)(p.low_mm + 128);
+            } else {
+                r.hi = ((uint64_t)p.nar << 41) | (1ULL << 40) | ((uint64_t)p.num_hits << 32);
+                r.lo = 0;
+                r.tail = 0;
             }
-        };
-        HostClock clk;
-        par_ranges(nr, o.nthreads, [&](size_t lo, size_t hi, int) { fill(lo, hi); });
-        clk.lap("sort records filled");
-        bk::ref_order_sort(recs.data(), (int64_t)nr, sort_cmp, o.nthreads);
-        clk.lap("sorted (the reference's order of equal records)");
-        ord.resize(nr);
-        par_ranges(nr, o.nthreads, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; i++) ord[i] = recs[i].idx; });
-        clk.lap("order taken");
+        }
     };
-    if (o.pcr_win >= 0 && !o.pe_mode) {
-        // CAligner::ReducePCRduplicates runs on the sorted set, before the flank trimmer (Aligner.cpp:598-610)
-        diag("Processing to reduce PCR differential amplification artefacts processing started..");
-        std::vector<uint32_t> ord;
-        sorted_order(ord);
-        const size_t n_dup = bk::reduce_pcr_duplicates(hits, ord, [&](size_t i) { return a_start(hits[i], i); }, [&](size_t i) { return a_len(hits[i], i); }, o.pcr_win);
-        diag("Removed %zu potential PCR artefact reads", n_dup);
+    HostClock clk;
+    par_ranges(nr, nthreads, [&](size_t lo, size_t hi, int) { fill(lo, hi); });
+    clk.lap("sort records filled");
+    bk::ref_order_sort(recs.data(), (int64_t)nr, sort_cmp, nthreads);
+    clk.lap("sorted (the reference's order of equal records)");
+    ord.resize(nr);
+    par_ranges(nr, nthreads, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; i++) ord[i] = recs[i].idx; });
+    clk.lap("order taken");
+}
+
+// -k: CAligner::ReducePCRduplicates runs on the sorted set, before the flank trimmer (Aligner.cpp:598-610)
+void reduce_pcr_artefacts(AlignRun &r)
+{
+    bk::RecordSet &rec = r.rec;
+    diag("Processing to reduce PCR differential amplification artefacts processing started..");
+    std::vector<uint32_t> ord;
+    sorted_order(rec, r.o.nthreads, ord);
+    const size_t n_dup = bk::reduce_pcr_duplicates(rec.hits, ord, [&](size_t i) { return rec.a_start(rec.hits[i], i); }, [&](size_t i) { return rec.a_len(rec.hits[i], i); }, r.o.pcr_win);
+    diag("Removed %zu potential PCR artefact reads", n_dup);
+}
+
+// -6: CAligner::PCR5PrimerCorrect(m_MaxSubs), between -k and the flank trimmer (Aligner.cpp:608-617): the reads still above the user's
+// rate go to the first device with their first twelve bases; its answers patch the read store and the records (primer_correct.h).
+// The reference sorts behind the pass since LowMMCnt is a sort key: every sorted_order() after it is made from the records as they stand
+int correct_primer_artefacts(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    ReadStore &rs = r.rs;
+    bk::RecordSet &rec = r.rec;
+    std::vector<bk_hit> &hits = rec.hits;
+    diag("PCR 5' Primer correction processing started..");
+    diag("Starting PCR 5' %dbp primer correction processing targeting substitution rate of %d ...", BK_PRIMER_KLEN, o.user_subs);
+    HostClock clk;
+    bk::RawVec<bk_primer_req> reqs;
+    bk::RawVec<uint32_t> rec_of;
+    par_select(rec.size(), o.nthreads, [&](size_t i) { return bk::primer_selects(hits[i], rec.has_seg2(i), rs.lens[rec.RD(i)], o.user_subs); },
+               [&](size_t at, size_t i) {
+                   reqs[at] = bk::primer_request(hits[i], rs.bases.data() + rs.offs[rec.RD(i)], rs.lens[rec.RD(i)], o.user_subs);
+                   rec_of[at] = (uint32_t)i;
+               },
+               [&](size_t n) { reqs.resize(n); rec_of.resize(n); });
+    bk::RawVec<bk_primer_res> res(reqs.size());
+    clk.lap("primer correction requests made");
+    const int prc = bk_primer_correct(r.ctx, reqs.data(), reqs.size(), res.data());
+    if (prc) { diag("Fatal: the 5' primer correction failed: %s", bk_strerror(prc)); return 1; }
+    clk.lap("primer windows compared (device)");
+    // (the pass writes Seg[0].Mismatches, not TrimMismatches - which the CSV writers and the -O statistics print, and which only the
+    // flank trimmer computes again, for the reads it trims, :1788: the counts as they stood before the pass are kept as the trims')
+    rec.ensure_trims();
+    bk::PrimerStats pst;
+    for (size_t k = 0; k < reqs.size(); k++) {
+        const size_t i = rec_of[k];
+        if (bk::primer_apply(res[k], hits[i], rs.bases.data() + rs.offs[rec.RD(i)], pst)) { diag("Fatal: the 5' primer correction turned a request down"); return 1; }
     }
-    if (o.primer_subs > 0) {
-        // CAligner::PCR5PrimerCorrect(m_MaxSubs), between -k and the flank trimmer (Aligner.cpp:608-617): the reads still above the user's
-        // rate go to the first device with their first twelve bases; its answers patch the read store and the records (primer_correct.h).
-        // The reference sorts behind the pass since LowMMCnt is a sort key: every sorted_order() below is made from the records as they stand
-        diag("PCR 5' Primer correction processing started..");
-        diag("Starting PCR 5' %dbp primer correction processing targeting substitution rate of %d ...", BK_PRIMER_KLEN, o.user_subs);
-        HostClock clk;
-        const int nt = std::max(1, o.nthreads);
-        auto selected = [&](size_t i) { return bk::primer_selects(hits[i], has_seg2(i), rs.lens[RD(i)], o.user_subs); };
-        std::vector<size_t> first((size_t)nt + 1, 0);
-        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) { size_t c = 0; for (size_t i = lo; i < hi; i++) c += selected(i); first[(size_t)t + 1] = c; });
-        for (int t = 0; t < nt; t++) first[(size_t)t + 1] += first[(size_t)t];
-        bk::RawVec<bk_primer_req> reqs(first[(size_t)nt]);
-        bk::RawVec<uint32_t> rec_of(first[(size_t)nt]);
-        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
-            size_t at = first[(size_t)t];
-            for (size_t i = lo; i < hi; i++) {
-                if (!selected(i)) continue;
-                reqs[at] = bk::primer_request(hits[i], rs.bases.data() + rs.offs[RD(i)], rs.lens[RD(i)], o.user_subs);
-                rec_of[at++] = (uint32_t)i;
-            }
-        });
-        bk::RawVec<bk_primer_res> res(reqs.size());
-        clk.lap("primer correction requests made");
-        const int prc = bk_primer_correct(ctx, reqs.data(), reqs.size(), res.data());
-        if (prc) { diag("Fatal: the 5' primer correction failed: %s", bk_strerror(prc)); destroy_ctxs(); return 1; }
-        clk.lap("primer windows compared (device)");
-        // (the pass writes Seg[0].Mismatches, not TrimMismatches - which the CSV writers and the -O statistics print, and which only the
-        // flank trimmer computes again, for the reads it trims, :1788: the counts as they stood before the pass are kept as the trims')
-        if (trims.empty()) {
-            trims.left.assign(nr, 0); trims.right.assign(nr, 0); trims.mismatches.resize(nr);
-            for (size_t i = 0; i < nr; i++) trims.mismatches[i] = hits[i].mismatches;
-        }
-        bk::PrimerStats pst;
-        for (size_t k = 0; k < reqs.size(); k++) {
-            const size_t i = rec_of[k];
-            if (bk::primer_apply(res[k], hits[i], rs.bases.data() + rs.offs[RD(i)], pst)) { diag("Fatal: the 5' primer correction turned a request down"); destroy_ctxs(); return 1; }
-        }
-        clk.lap("primer corrections applied");
-        diag("Completed PCR 5' primer correction, %llu reads with %llu bases corrected, %llu reads with excessive substitutions rejected",
-             (unsigned long long)pst.reads, (unsigned long long)pst.bases, (unsigned long long)pst.rejected);
-        diag("PCR 5' Primer correction processing completed");
-    }
-    if (o.min_flank > 0) {
-        diag("Starting 5' and 3' flank sequence autotrim processing...");
-        bk::SfxFile sft;
-        std::string serr;
-        if (bk::sfx_open(a.str("I").c_str(), sft, &serr) != 0) { diag("Fatal: %s", serr.c_str()); destroy_ctxs(); return 1; }
-        bk::auto_trim_flanks(hits, [&](size_t i) { return has_seg2(i) || is_chimeric(i); }, [&](size_t i) { return rs.bases.data() + rs.offs[RD(i)]; },
-                             [&](size_t i) -> const uint8_t * {
-                                 const bk_hit &h = hits[i];
-                                 return (h.chrom_id >= 1 && h.chrom_id <= n_ent) ? sft.seq + ents[h.chrom_id - 1].start_ofs + h.match_loci : nullptr;
-                             },
-                             o.min_flank, o.pe_mode != 0, o.nthreads, trims);
-        diag("Finished 5' and 3' flank sequence autotriming, %zu plus strand and %zu minus strand aligned reads removed", trims.removed_plus,
-             trims.removed_minus);
-    }
-    // orphan junction filters, splice junctions first (Aligner.cpp:630-650)
-    if (o.splice_len) {
+    clk.lap("primer corrections applied");
+    diag("Completed PCR 5' primer correction, %llu reads with %llu bases corrected, %llu reads with excessive substitutions rejected",
+         (unsigned long long)pst.reads, (unsigned long long)pst.bases, (unsigned long long)pst.rejected);
+    diag("PCR 5' Primer correction processing completed");
+    return 0;
+}
+
+// -x (and forced by -A): CAligner::AutoTrimFlanks
+int trim_flanks(AlignRun &r)
+{
+    const ReadStore &rs = r.rs;
+    bk::RecordSet &rec = r.rec;
+    diag("Starting 5' and 3' flank sequence autotrim processing...");
+    bk::SfxFile sft;
+    std::string serr;
+    if (bk::sfx_open(r.a.str("I").c_str(), sft, &serr) != 0) { diag("Fatal: %s", serr.c_str()); return 1; }
+    bk::auto_trim_flanks(rec.hits, [&](size_t i) { return rec.has_seg2(i) || rec.is_chimeric(i); }, [&](size_t i) { return rs.bases.data() + rs.offs[rec.RD(i)]; },
+                         [&](size_t i) -> const uint8_t * {
+                             const bk_hit &h = rec.hits[i];
+                             return (h.chrom_id >= 1 && h.chrom_id <= r.n_ent) ? sft.seq + r.ents[h.chrom_id - 1].start_ofs + h.match_loci : nullptr;
+                         },
+                         r.o.min_flank, r.o.pe_mode != 0, r.o.nthreads, rec.trims);
+    diag("Finished 5' and 3' flank sequence autotriming, %zu plus strand and %zu minus strand aligned reads removed", rec.trims.removed_plus,
+         rec.trims.removed_minus);
+    return 0;
+}
+
+// orphan junction filters, splice junctions first (Aligner.cpp:630-650)
+void remove_orphan_junctions(AlignRun &r)
+{
+    if (r.o.splice_len) {
         diag("Removal of orphan splice junction processing started..");
-        auto r = bk::remove_orphan_segs(hits, seg2, 4, 7);
-        diag("From %zu reads with putative splice junctions %zu orphans were removed", r.first, r.second);
+        auto n = bk::remove_orphan_segs(r.rec.hits, r.rec.seg2, 4, 7);
+        diag("From %zu reads with putative splice junctions %zu orphans were removed", n.first, n.second);
     }
-    if (o.micro_indel) {
+    if (r.o.micro_indel) {
         diag("Removal of orphan microInDels processing started..");
-        auto r = bk::remove_orphan_segs(hits, seg2, 1, 8);
-        diag("From %zu reads with putative microIndels %zu orphans were removed", r.first, r.second);
+        auto n = bk::remove_orphan_segs(r.rec.hits, r.rec.seg2, 1, 8);
+        diag("From %zu reads with putative microIndels %zu orphans were removed", n.first, n.second);
     }
+}
 
-    if (!o.re_excl.empty() || !o.re_incl.empty()) {
-        // CAligner::FiltByChroms (Aligner.cpp:4019-4120): a sequence stays if an include expression matches its name, or - with no
-        // include expressions at all - if no exclude expression does; accepted reads on the others become eNARChromFilt
-        diag("Now filtering matches by chromosome");
-        std::vector<uint8_t> keep(n_ent + 1, 1);
-        for (uint32_t c = 1; c <= n_ent; c++) {
-            regmatch_t mc;
-            bool ok = false;
-            for (regex_t &re : o.re_incl) if (!regexec(&re, ents[c - 1].name, 1, &mc, 0)) { ok = true; break; }
-            if (!ok && o.re_incl.empty()) {
-                ok = true;
-                for (regex_t &re : o.re_excl) if (!regexec(&re, ents[c - 1].name, 1, &mc, 0)) { ok = false; break; }
-            }
-            keep[c] = ok ? 1 : 0;
-        }
-        size_t n_filt = 0;
-        for (size_t i = 0; i < nr; i++) {
-            bk_hit &h = hits[i];
-            if (h.nar == BK_NAR_ACCEPTED && h.chrom_id <= n_ent && !keep[h.chrom_id]) { h.nar = 11; h.num_hits = 0; h.low_hit_instances = 0; n_filt++; }
-        }
-        diag("Filtering by chromosome completed - removed %zu  matches", n_filt);
-    }
+// -Z / -z by CAligner::FiltByChroms (chrom_keep_table: inclusion first); accepted reads on the other sequences become eNARChromFilt
+void filter_by_chroms(AlignRun &r)
+{
+    diag("Now filtering matches by chromosome");
+    const std::vector<uint8_t> keep = bk::chrom_keep_table(r.entry_names(), r.o.re_excl, r.o.re_incl);
+    size_t n_filt = 0;
+    for (bk_hit &h : r.rec.hits)
+        if (h.nar == BK_NAR_ACCEPTED && h.chrom_id >= 1 && h.chrom_id <= r.n_ent && !keep[h.chrom_id - 1]) { h.nar = 11; h.num_hits = 0; h.low_hit_instances = 0; n_filt++; }
+    diag("Filtering by chromosome completed - removed %zu  matches", n_filt);
+}
 
-    // CAligner::ReportAlignStats (Aligner.cpp:3493-3822): strand counts, the simulated-reads truth check, NAR histogram
-    uint64_t nar[20] = {0};
-    uint64_t tot_acc = 0, tot_plus = 0;
-    size_t first_acc = nr;                         // the first accepted read, in load order
-    {
-        const int nt = std::max(1, o.nthreads);
-        std::vector<std::array<uint64_t, 24>> part((size_t)nt);
-        std::vector<size_t> first((size_t)nt, nr);
-        for (auto &pt : part) pt.fill(0);
-        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
-            std::array<uint64_t, 24> c{};
-            size_t f = nr;
-            for (size_t i = lo; i < hi; i++) {
-                const bk_hit &h = hits[i];
-                c[h.nar < 20 ? h.nar : 0]++;
-                if (h.nar == BK_NAR_ACCEPTED) { c[20]++; c[21] += h.strand == '+'; if (f == nr) f = i; }
-            }
-            part[(size_t)t] = c; first[(size_t)t] = f;
-        });
-        for (int t = 0; t < nt; t++) {
-            for (int k = 0; k < 20; k++) nar[k] += part[(size_t)t][(size_t)k];
-            tot_acc += part[(size_t)t][20]; tot_plus += part[(size_t)t][21];
-            first_acc = std::min(first_acc, first[(size_t)t]);
-        }
-    }
-    {
-        // Reads named by `biokanga simreads` carry where they came from (lcl|usimreads|id|chrom|start|end|len|strand|..): an accepted
-        // alignment on the named sequence counts as high confidence when one or both of its ends are the named ones, anything
-        // else as misaligned.  Reads are visited in load order; the first accepted read decides whether the set is simulated, and
-        // a later accepted read that does not parse ends the check - and drops the line - exactly as the reference's loop does
-        // (:3560-3650).  The descriptors are parsed with the reference's own sscanf formats.
-        uint64_t n_plus = 0, n_acc = 0, n2 = 0, n1 = 0, n_mis = 0;
-        bool sim = false;
-        n_acc = tot_acc; n_plus = tot_plus;        // (counted above by all threads; the truth check below visits reads only while the set looks simulated)
-        for (size_t i = first_acc; i < nr; i++) {
+// CAligner::ReportAlignStats (Aligner.cpp:3493-3822): strand counts, the simulated-reads truth check, NAR histogram
+struct AcceptedCounts { uint64_t acc = 0, plus = 0; size_t first = 0; };      // accepted records, those on '+', the first one in load order
+
+AcceptedCounts count_nars(AlignRun &r)
+{
+    const std::vector<bk_hit> &hits = r.rec.hits;
+    const size_t nr = hits.size();
+    const int nt = std::max(1, r.o.nthreads);
+    std::vector<std::array<uint64_t, 24>> part((size_t)nt);
+    std::vector<size_t> first((size_t)nt, nr);
+    for (auto &pt : part) pt.fill(0);
+    par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
+        std::array<uint64_t, 24> c{};
+        size_t f = nr;
+        for (size_t i = lo; i < hi; i++) {
             const bk_hit &h = hits[i];
-            if (h.nar != BK_NAR_ACCEPTED) continue;
-            if (!(sim || i == first_acc)) break;
-            char typ[100], xchrom[300], x1c[100], x2c[100], xstrand;
-            int id, xs, xe, xl, xerrs;
-            const char *nm = rs.name(RD(i));
-            if (strlen(nm) > 127) continue;
-            int its = sscanf(nm, "%99[^|]|usimreads|%d|%99[^|]|%d|%d|%d|%c|%d", typ, &id, xchrom, &xs, &xe, &xl, &xstrand, &xerrs);
-            if (its >= 6) sim = true;
-            else {
-                its = sscanf(nm, "%99[^|]|usimreads|%d|%99[^|]|%99[^|]|%99[^|]|%d|%d|%d|%c|%d", typ, &id, xchrom, x1c, x2c, &xs, &xe, &xl, &xstrand, &xerrs);
-                if (its < 8) sim = false;
-                else { strcat(xchrom, "|"); strcat(xchrom, x1c); strcat(xchrom, "|"); strcat(xchrom, x2c); sim = true; }
-            }
-            if (!sim) continue;
-            if (h.chrom_id < 1 || h.chrom_id > n_ent || strcasecmp(ents[h.chrom_id - 1].name, xchrom)) { n_mis++; continue; }
-            const long left = (long)h.match_loci;
-            const long right = has_seg2(i) ? (long)seg2[RD(i)].match_loci + seg2[RD(i)].match_len - 1 : left + h.match_len - 1;
-            if (left == xs || right == xe) (left != xs || right != xe ? n1 : n2)++;
-            else n_mis++;
+            c[h.nar < 20 ? h.nar : 0]++;
+            if (h.nar == BK_NAR_ACCEPTED) { c[20]++; c[21] += h.strand == '+'; if (f == nr) f = i; }
         }
-        diag("From %zu source reads there are %llu accepted alignments, %llu on '+' strand, %llu on '-' strand", rs.size(), (unsigned long long)n_acc,
-             (unsigned long long)n_plus, (unsigned long long)(n_acc - n_plus));
-        if (sim)
-            diag("There are %llu (%llu 2 edge, %llu 1 edge) high confidence aligned simulated reads with %llu misaligned", (unsigned long long)(n2 + n1),
-                 (unsigned long long)n2, (unsigned long long)n1, (unsigned long long)n_mis);
+        part[(size_t)t] = c; first[(size_t)t] = f;
+    });
+    AcceptedCounts tot;
+    tot.first = nr;
+    for (int t = 0; t < nt; t++) {
+        for (int k = 0; k < 20; k++) r.nar[k] += part[(size_t)t][(size_t)k];
+        tot.acc += part[(size_t)t][20]; tot.plus += part[(size_t)t][21];
+        tot.first = std::min(tot.first, first[(size_t)t]);
     }
-    diag("Unable to align %llu source reads of which %llu were not aligned as they contained excessive number of indeterminate 'N' bases",
-         (unsigned long long)(nr - nar[1]), (unsigned long long)nar[2]);
-    diag("Read nonalignment reason summary:");
-    for (int k = 0; k < 20; k++) diag("   %llu (%s) %s", (unsigned long long)nar[k], kNarTag[k], kNarDescr[k]);
-    if (!o.pe_mode && !o.ml_mode && !o.micro_indel && !o.splice_len && !o.min_chim && o.pcr_win < 0 && !o.min_flank && !o.primer_subs && o.re_excl.empty() && o.re_incl.empty()) {
-        // nothing above changed an acceptance: the per-sequence counts the devices kept (summed over them by the exchange step)
-        // must add up to the accepted reads counted here
-        uint64_t tot = 0;
-        for (uint64_t c : A.seq_counts) tot += c;
-        if (tot != nar[1]) { diag("Fatal: the devices counted %llu accepted reads, the result records hold %llu", (unsigned long long)tot, (unsigned long long)nar[1]); destroy_ctxs(); return 1; }
-        if (ndev > 1) diag("Accepted read counts per sequence reduced over %zu devices: %llu reads", ndev, (unsigned long long)tot);
-    }
+    return tot;
+}
 
-    // SortReadHits(eRSMHitMatch): index in load (ReadID) order -> reference order
-    std::vector<uint32_t> order;
-    // -8: CAligner::ProcessSiteProbabilites, called between ReportAlignStats - which leaves the reads sorted - and the writers
-    // (Aligner.cpp:706), when reads were accepted.  The visited reads' Seg[0] as it stands (MatchLoci / MatchLen, not the flank-trimmed
-    // start) goes to the first device, which gathers the eight target bases of every start site; the sequential rest is site_prefs.h.
-    bk::SitePrefs site_prefs;
-    const bool with_site_prefs = !o.site_prefs_path.empty() && nar[1] > 0;
-    if (with_site_prefs) {
-        sorted_order(order);
-        diag("Processing for alignment site probabilities...");
-        HostClock clk;
-        // (by all threads: a stretch of the sorted order each - counted, placed by a prefix sum, then filled)
-        const int nt = std::max(1, o.nthreads);
-        auto visited = [&](uint32_t i) { return hits[i].nar == BK_NAR_ACCEPTED && !has_seg2(i); };
-        std::vector<size_t> first((size_t)nt + 1, 0);
-        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) { size_t c = 0; for (size_t k = lo; k < hi; k++) c += visited(order[k]); first[(size_t)t + 1] = c; });
-        for (int t = 0; t < nt; t++) first[(size_t)t + 1] += first[(size_t)t];
-        bk::RawVec<bk_site_req> reqs(first[(size_t)nt]);
-        bk::RawVec<uint32_t> rec_of(first[(size_t)nt]);
-        par_ranges(nr, nt, [&](size_t lo, size_t hi, int t) {
-            size_t at = first[(size_t)t];
-            for (size_t k = lo; k < hi; k++) {
-                const uint32_t i = order[k];
-                if (!visited(i)) continue;
-                const bk_hit &h = hits[i];
-                reqs[at] = bk_site_req{h.chrom_id, h.match_loci, h.match_len, h.strand, 0};
-                rec_of[at++] = i;
-            }
-        });
-        bk::RawVec<bk_site_res> res(reqs.size());
-        clk.lap("site requests made");
-        const int sprc = bk_site_octamers(ctx, reqs.data(), reqs.size(), o.site_prefs_ofs, res.data());
-        if (sprc) { diag("Fatal: the start-site octamer gather failed: %s", bk_strerror(sprc)); destroy_ctxs(); return 1; }
-        clk.lap("site octamers gathered (device)");
-        bk::site_prefs_pass(reqs.data(), res.data(), rec_of.data(), reqs.size(), nr, site_prefs);
-        bk::site_prefs_scale(site_prefs);
-        clk.lap("site preferences counted and scaled");
-        diag("Completed alignment site probabilities");
+// Reads named by `biokanga simreads` carry where they came from (lcl|usimreads|id|chrom|start|end|len|strand|..): an accepted
+// alignment on the named sequence counts as high confidence when one or both of its ends are the named ones, anything
+// else as misaligned.  Reads are visited in load order; the first accepted read decides whether the set is simulated, and
+// a later accepted read that does not parse ends the check - and drops the line - exactly as the reference's loop does
+// (:3560-3650).  The descriptors are parsed with the reference's own sscanf formats.
+void check_simulated_reads(AlignRun &r, const AcceptedCounts &tot)
+{
+    const bk::RecordSet &rec = r.rec;
+    uint64_t n2 = 0, n1 = 0, n_mis = 0;
+    bool sim = false;
+    // (the accepted reads were counted by all threads; the truth check below visits reads only while the set looks simulated)
+    for (size_t i = tot.first; i < rec.size(); i++) {
+        const bk_hit &h = rec.hits[i];
+        if (h.nar != BK_NAR_ACCEPTED) continue;
+        if (!(sim || i == tot.first)) break;
+        char typ[100], xchrom[300], x1c[100], x2c[100], xstrand;
+        int id, xs, xe, xl, xerrs;
+        const char *nm = r.rs.name(rec.RD(i));
+        if (strlen(nm) > 127) continue;
+        int its = sscanf(nm, "%99[^|]|usimreads|%d|%99[^|]|%d|%d|%d|%c|%d", typ, &id, xchrom, &xs, &xe, &xl, &xstrand, &xerrs);
+        if (its >= 6) sim = true;
+        else {
+            its = sscanf(nm, "%99[^|]|usimreads|%d|%99[^|]|%99[^|]|%99[^|]|%d|%d|%d|%c|%d", typ, &id, xchrom, x1c, x2c, &xs, &xe, &xl, &xstrand, &xerrs);
+            if (its < 8) sim = false;
+            else { strcat(xchrom, "|"); strcat(xchrom, x1c); strcat(xchrom, "|"); strcat(xchrom, x2c); sim = true; }
+        }
+        if (!sim) continue;
+        if (h.chrom_id < 1 || h.chrom_id > r.n_ent || strcasecmp(r.ents[h.chrom_id - 1].name, xchrom)) { n_mis++; continue; }
+        const long left = (long)h.match_loci;
+        const long right = rec.has_seg2(i) ? (long)rec.seg2[rec.RD(i)].match_loci + rec.seg2[rec.RD(i)].match_len - 1 : left + h.match_len - 1;
+        if (left == xs || right == xe) (left != xs || right != xe ? n1 : n2)++;
+        else n_mis++;
     }
+    diag("From %zu source reads there are %llu accepted alignments, %llu on '+' strand, %llu on '-' strand", r.rs.size(), (unsigned long long)tot.acc,
+         (unsigned long long)tot.plus, (unsigned long long)(tot.acc - tot.plus));
+    if (sim)
+        diag("There are %llu (%llu 2 edge, %llu 1 edge) high confidence aligned simulated reads with %llu misaligned", (unsigned long long)(n2 + n1),
+             (unsigned long long)n2, (unsigned long long)n1, (unsigned long long)n_mis);
+}
+
+// nothing behind the alignment changed an acceptance: the per-sequence counts the devices kept (summed over them by the exchange
+// step) must add up to the accepted reads counted here
+int check_seq_counts(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    if (o.pe_mode || o.ml_mode || o.micro_indel || o.splice_len || o.min_chim || o.pcr_win >= 0 || o.min_flank || o.primer_subs || !o.re_excl.empty() || !o.re_incl.empty()) return 0;
+    uint64_t tot = 0;
+    for (uint64_t c : r.A.seq_counts) tot += c;
+    if (tot != r.nar[1]) { diag("Fatal: the devices counted %llu accepted reads, the result records hold %llu", (unsigned long long)tot, (unsigned long long)r.nar[1]); return 1; }
+    if (r.ndev > 1) diag("Accepted read counts per sequence reduced over %zu devices: %llu reads", r.ndev, (unsigned long long)tot);
+    return 0;
+}
+
+int report_align_stats(AlignRun &r)
+{
+    check_simulated_reads(r, count_nars(r));
+    diag("Unable to align %llu source reads of which %llu were not aligned as they contained excessive number of indeterminate 'N' bases",
+         (unsigned long long)(r.rec.size() - r.nar[1]), (unsigned long long)r.nar[2]);
+    diag("Read nonalignment reason summary:");
+    for (int k = 0; k < 20; k++) diag("   %llu (%s) %s", (unsigned long long)r.nar[k], kNarTag[k], kNarDescr[k]);
+    return check_seq_counts(r);
+}
+
+// -8: CAligner::ProcessSiteProbabilites, called between ReportAlignStats - which leaves the reads sorted - and the writers
+// (Aligner.cpp:706), when reads were accepted.  The visited reads' Seg[0] as it stands (MatchLoci / MatchLen, not the flank-trimmed
+// start) goes to the first device, which gathers the eight target bases of every start site; the sequential rest is site_prefs.h.
+int gather_site_prefs(AlignRun &r)
+{
+    const bk::RecordSet &rec = r.rec;
+    const std::vector<uint32_t> &order = r.order;
+    sorted_order(rec, r.o.nthreads, r.order);
+    diag("Processing for alignment site probabilities...");
+    HostClock clk;
+    // (by all threads: a stretch of the sorted order each)
+    bk::RawVec<bk_site_req> reqs;
+    bk::RawVec<uint32_t> rec_of;
+    par_select(order.size(), r.o.nthreads, [&](size_t k) { return rec.hits[order[k]].nar == BK_NAR_ACCEPTED && !rec.has_seg2(order[k]); },
+               [&](size_t at, size_t k) {
+                   const bk_hit &h = rec.hits[order[k]];
+                   reqs[at] = bk_site_req{h.chrom_id, h.match_loci, h.match_len, h.strand, 0};
+                   rec_of[at] = order[k];
+               },
+               [&](size_t n) { reqs.resize(n); rec_of.resize(n); });
+    bk::RawVec<bk_site_res> res(reqs.size());
+    clk.lap("site requests made");
+    const int sprc = bk_site_octamers(r.ctx, reqs.data(), reqs.size(), r.o.site_prefs_ofs, res.data());
+    if (sprc) { diag("Fatal: the start-site octamer gather failed: %s", bk_strerror(sprc)); return 1; }
+    clk.lap("site octamers gathered (device)");
+    bk::site_prefs_pass(reqs.data(), res.data(), rec_of.data(), reqs.size(), rec.size(), r.site_prefs);
+    bk::site_prefs_scale(r.site_prefs);
+    clk.lap("site preferences counted and scaled");
+    diag("Completed alignment site probabilities");
+    return 0;
+}
+
+// the writers, then the files that come behind them: the site preferences of -8, the SNPs of -p.  0, or the failed writer's code.
+int write_reports(AlignRun &r)
+{
+    AlignOpts &o = r.o;
+    const Args &a = r.a;
     diag("Reporting of aligned result set started...");
     diag("Sorting alignments by ascending chrom.loci");
-    if (!with_site_prefs) sorted_order(order);
+    if (!r.with_site_prefs) sorted_order(r.rec, o.nthreads, r.order);
 
-    Report R{a, rs, hits, ents, species, n_ent, src, seg2, trims, multi_dist, order, o.pe_mode, o.ml_mode, o.max_ml, o.fmt, o.nthreads, o.micro_indel, o.splice_len, o.max_rpt_sam_seqs};
-    R.ctx = ctx;
-    R.site_prefs = with_site_prefs ? &site_prefs : nullptr;
-    R.pre = pre.fd >= 0 ? &pre : nullptr;
-    S.done_with_head_start();
-    R.restore_reads = restore_reads;
-    R.sam_prep = sam_prep;
-    R.pk_words = pk_job.pk_words; R.n_pk_words = pk_job.n_pk_words; R.pk_lens16 = pk_job.pk_lens16; R.pk_exc = pk_job.pk_exc; R.n_pk_exc = pk_job.n_pk_exc;
-    sam_prep = nullptr;                            // (the report owns it from here)
-    // ".bam" (more than 5 characters of name, kanga.cpp:848-857): BGZF-compressed BAM with its BAI index; else SAM / CSV / BED text
+    Report R{a, r.rs, r.rec, r.ents, r.species, r.n_ent, r.multi_dist, r.order, o.pe_mode, o.ml_mode, o.max_ml, o.fmt, o.nthreads, o.micro_indel, o.splice_len, o.max_rpt_sam_seqs};
+    R.ctx = r.ctx;
+    R.site_prefs = r.with_site_prefs ? &r.site_prefs : nullptr;
+    R.pre = r.pre.fd >= 0 ? &r.pre : nullptr;
+    r.S.done_with_head_start();
+    R.restore_reads = [&r]() { return restore_reads(r); };
+    R.sam_prep = r.sam_prep;
+    R.pk_words = r.pk_job.pk_words; R.n_pk_words = r.pk_job.n_pk_words; R.pk_lens16 = r.pk_job.pk_lens16; R.pk_exc = r.pk_job.pk_exc; R.n_pk_exc = r.pk_job.n_pk_exc;
+    r.sam_prep = nullptr;                          // (the report owns it from here)
+    // ".bam": BGZF-compressed BAM with its BAI index; else SAM / CSV / BED text
     const std::string opath = a.str("o");
-    int rr = (o.fmt >= 5 && opath.size() > 5 && !strcasecmp(opath.c_str() + opath.size() - 4, ".bam")) ? report_bam(R, opath) : report_text(R);
+    int rr = (o.fmt >= 5 && is_bam_name(opath)) ? report_bam(R, opath) : report_text(R);
     if (R.sam_prep) { bk_sam_prep_free(R.sam_prep); R.sam_prep = nullptr; }        // (the report took another path)
-    if (rr == 0 && with_site_prefs) {               // WriteSitePrefs, behind the writers and the -O statistics (Aligner.cpp:743)
+    if (rr == 0 && r.with_site_prefs) {             // WriteSitePrefs, behind the writers and the -O statistics (Aligner.cpp:743)
         std::string csv;
-        bk::site_prefs_csv(site_prefs, csv);
+        bk::site_prefs_csv(r.site_prefs, csv);
         OutBuf sp_file;
         sp_file.open(o.site_prefs_path.c_str());
         const bool opened = sp_file.fd >= 0;
@@ -1437,18 +1531,56 @@ int cmd_align(int argc, char **argv, int first)
         o.snp.title = a.str("t", "kanga");
         o.snp.sfx_path = a.str("I");
         bool any = false;
-        for (const bk_hit &h : hits) if (h.nar == BK_NAR_ACCEPTED) { any = true; break; }
-        if (any) rr = process_snps(ctx, R, o.snp);
+        for (const bk_hit &h : r.rec.hits) if (h.nar == BK_NAR_ACCEPTED) { any = true; break; }
+        if (any) rr = process_snps(r.ctx, R, o.snp);
         else for (const char *ext : {"", ".disnp.csv", ".trisnp.csv", ".markers"}) { if (ext[1] == 'm' && !o.snp.marker_len) continue; OutBuf e; e.open((o.snp.path + ext).c_str()); e.close(); }
     }
-    if (rr == 0 && nr >= 1000000) {                // (small runs unwind normally: leak checkers and tests see every destructor)
-        pre.finish();
-        end_process(rr);                           // (contexts, page-locked buffers and the address space go with the process)
-    }
-    { HostClock clk; destroy_ctxs(); clk.lap("contexts destroyed"); }
     return rr;
 }
 
+// The run, top to bottom, in the reference's order (CAligner::Align, Aligner.cpp:195-760)
+int cmd_align(int argc, char **argv, int first)
+{
+    AlignRun r;
+    const AlignOpts &o = r.o;
+    if (parse_align_args(argc, argv, first, r.a)) return 1;
+    if (r.a.has("F")) g_logfile = fopen(r.a.str("F").c_str(), "a");
+    diag("Subprocess align Version %s starting", kProgVer);
+    if (read_align_opts(r.a, r.o)) return 1;
+    r.ndev = o.devices.size();
+    if (make_contam_matcher(r)) return 1;
+    if (print_param_lines(o)) return 1;
+
+    diag("Loading suffix array file '%s'", r.a.str("I").c_str());
+    estimate_input(r);
+    start_early_buffers(r);
+    choose_index_image(r);
+    load_reads_behind_index(r);                     // (the loader threads run ..
+    if (pack_reads_and_join_index(r)) return 1;     //  .. until here: no return in between)
+    tune_and_describe_image(r);
+    start_sam_file_late(r);
+    if (make_accept_table(r)) return 1;
+    if (run_alignment(r)) return 1;
+    start_sam_head(r);
+
+    resolve_multi_and_count_pairs(r);
+    if (o.min_chim) keep_chimeric_trims(r.rec);
+    if (o.pcr_win >= 0 && !o.pe_mode) reduce_pcr_artefacts(r);
+    if (o.primer_subs > 0 && correct_primer_artefacts(r)) return 1;
+    if (o.min_flank > 0 && trim_flanks(r)) return 1;
+    remove_orphan_junctions(r);
+    if (!o.re_excl.empty() || !o.re_incl.empty()) filter_by_chroms(r);
+    if (report_align_stats(r)) return 1;
+
+    r.with_site_prefs = !o.site_prefs_path.empty() && r.nar[1] > 0;
+    if (r.with_site_prefs && gather_site_prefs(r)) return 1;
+    const int rr = write_reports(r);
+    if (rr == 0 && r.rec.size() >= 1000000) {       // (small runs unwind normally: leak checkers and tests see every destructor)
+        r.pre.finish();
+        end_process(rr);                            // (contexts, page-locked buffers and the address space go with the process)
+    }
+    return rr;
+}
 
 // CUtility::arg_parsefromfile (libbiokanga/Utility.cpp:793-910; called first thing by every sub-process, kanga.cpp:298): an argument
 // "@file" is replaced by the options found in that file - one or more per line, separated by blanks or tabs except inside quotes

@@ -42,6 +42,24 @@ inline void par_ranges(size_t n, int nthreads, Fn fn)
     for (auto &x : th) x.join();
 }
 
+// The i of [0, n) with pred(i), compacted by all threads: counted per range, placed by a prefix sum, then emit(slot, i) for each of
+// them - slots dense from 0, ascending with i.  sized(count) runs once between the two passes, for the caller to make room.
+// Returns the count.
+template <class Pred, class Emit, class Sized = void (*)(size_t)>
+inline size_t par_select(size_t n, int nthreads, Pred pred, Emit emit, Sized sized = [](size_t) {})
+{
+    const int nt = std::max(1, nthreads);
+    std::vector<size_t> first((size_t)nt + 1, 0);
+    par_ranges(n, nt, [&](size_t lo, size_t hi, int t) { size_t c = 0; for (size_t i = lo; i < hi; i++) c += pred(i) ? 1 : 0; first[(size_t)t + 1] = c; });
+    for (int t = 0; t < nt; t++) first[(size_t)t + 1] += first[(size_t)t];
+    sized(first[(size_t)nt]);
+    par_ranges(n, nt, [&](size_t lo, size_t hi, int t) {
+        size_t at = first[(size_t)t];
+        for (size_t i = lo; i < hi; i++) if (pred(i)) emit(at++, i);
+    });
+    return first[(size_t)nt];
+}
+
 inline const char *kProgVer = "4.4.2";          // cpszProgVer of the release whose formats are kept (biokanga.cpp:33)
 inline std::string g_proc = "biokanga";          // gszProcName = basename(argv[0]) (used for @PG ID:)
 inline FILE *g_logfile = nullptr;
@@ -65,6 +83,23 @@ inline void diag(const char *fmt, ...)
     fflush(stdout);
     if (g_logfile) { fputs(line, g_logfile); fflush(g_logfile); }
 }
+
+// a parameter line as the reference prints them: the text as it is, no time stamp in front
+inline void param_line(const char *fmt, ...)
+{
+    char line[4300];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(line, sizeof(line), fmt, ap);
+    va_end(ap);
+    fputs(line, stdout);
+    if (g_logfile) fputs(line, g_logfile);
+}
+
+// output names the reference tells apart by their ending, whatever its case: ".bam" (more than 5 characters of name,
+// kanga.cpp:848-857) and ".gz" (CAligner::FileReqWriteCompr, Aligner.cpp:4337)
+inline bool is_bam_name(const std::string &p) { return p.size() > 5 && !strcasecmp(p.c_str() + p.size() - 4, ".bam"); }
+inline bool is_gz_name(const std::string &p) { return p.size() > 3 && !strcasecmp(p.c_str() + p.size() - 3, ".gz"); }
 
 // ---------------------------------------------------------------------------------------------
 // tiny option parser: -x val, -xval, --long=val, --long val; repeated options accumulate
@@ -272,12 +307,11 @@ struct OutBuf {
     std::vector<char> b;
     void open(const char *path)
     {
-        size_t n = strlen(path);
         // read-write: the SAM writer maps ranges of the file (a shared mapping needs a readable descriptor); write-only for what cannot
         // be opened that way (a FIFO, /dev/stdout) - those are written with pwrite() / write()
         fd = ::open(path, O_RDWR | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        gz = fd >= 0 && n > 3 && !strcasecmp(path + n - 3, ".gz");
+        gz = fd >= 0 && is_gz_name(path);
         pipe = fd >= 0 && lseek(fd, 0, SEEK_CUR) == (off_t)-1 && errno == ESPIPE;
         b.reserve(8 << 20);
         pos = 0;

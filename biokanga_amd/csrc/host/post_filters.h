@@ -1,11 +1,14 @@
 // Host-side filters the reference applies to the aligned read set after the hot path, restated over the C ABI's records:
 //   * auto_trim_flanks    - CAligner::AutoTrimFlanks (biokanga/Aligner.cpp:1608-1800), `-x` (and forced by `-A`)
 //   * remove_orphan_segs  - CAligner::RemoveOrphanSpliceJuncts / RemoveOrphanMicroInDels (Aligner.cpp:2287-2470)
+//   * chrom_accept_table / chrom_keep_table - the two rules the -Z / -z expressions are read by (AcceptThisChromID, FiltByChroms)
+// and RecordSet, the view of the records every step after the alignment reads them through.
 // Records are indexed like bk_hit[] (one per read, or per reported locus in -r5); reads are looked up through `read_of`.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <regex.h>
 #include <thread>
 #include <vector>
 
@@ -20,6 +23,62 @@ struct FlankTrims {
     size_t removed_plus = 0, removed_minus = 0;
     bool empty() const { return left.empty(); }
 };
+
+// The records of one `align` run as the steps behind the alignment see them: one per read, or - after -r5's expansion - one per
+// reported locus, which `src` maps back to its read.  seg2 is indexed by READ, everything else by record.
+struct RecordSet {
+    std::vector<bk_hit> &hits;
+    const std::vector<bk_seg2> &seg2;              // -a / -A / -c: second segment of each read / chimeric trims (flags 0 = none)
+    std::vector<uint32_t> src;                     // -r5: record -> read it came from (records replace the reads)
+    FlankTrims trims;                              // per record, empty until a step makes them
+    std::vector<bk_loci_trims> rec_trims;          // -c with -r: per record (after -r5's expansion) the trims of the placement it took
+
+    size_t size() const { return hits.size(); }
+    size_t RD(size_t i) const { return src.empty() ? i : (size_t)src[i]; }
+    bool has_seg2(size_t i) const { return !seg2.empty() && (seg2[RD(i)].flags & 5); }       // FlgInDel or FlgSplice
+    bool is_chimeric(size_t i) const                                                          // FlgChimeric: trims come with the hit
+    {
+        if (!rec_trims.empty()) return rec_trims[i].chimeric != 0;
+        return !seg2.empty() && (seg2[RD(i)].flags & 8);
+    }
+    uint32_t TL(size_t i) const { return trims.empty() ? 0u : trims.left[i]; }
+    uint32_t TR(size_t i) const { return trims.empty() ? 0u : trims.right[i]; }
+    uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci
+    uint32_t a_len(const bk_hit &h, size_t i) const { return (uint32_t)h.match_len - TL(i) - TR(i); }                      // AdjHitLen
+    uint32_t a_mm(const bk_hit &h, size_t i) const { return trims.empty() ? h.mismatches : trims.mismatches[i]; }         // TrimMismatches
+    // no trims yet: none at either end, the mismatches those of the records as they stand
+    void ensure_trims()
+    {
+        if (!trims.empty()) return;
+        const size_t nr = hits.size();
+        trims.left.assign(nr, 0); trims.right.assign(nr, 0); trims.mismatches.resize(nr);
+        for (size_t i = 0; i < nr; i++) trims.mismatches[i] = hits[i].mismatches;
+    }
+};
+
+// -Z / -z: which of `names` pass, as a table of 0 / 1 per name.  The reference reads the two lists of expressions by two rules:
+//   chrom_accept_table - CAligner::AcceptThisChromID (Aligner.cpp:2651-2715): exclusion first.  A name passes unless an exclude
+//                        expression matches it, and - with include expressions present - only if one of those does too
+//   chrom_keep_table   - CAligner::FiltByChroms (Aligner.cpp:4019-4120): inclusion first.  A name stays if an include expression
+//                        matches it, or - with no include expressions at all - if no exclude expression does
+inline bool chrom_matches_any(const std::vector<regex_t> &res, const char *name)
+{
+    regmatch_t mc;
+    for (const regex_t &re : res) if (!regexec(&re, name, 1, &mc, 0)) return true;
+    return false;
+}
+inline std::vector<uint8_t> chrom_accept_table(const std::vector<const char *> &names, const std::vector<regex_t> &excl, const std::vector<regex_t> &incl)
+{
+    std::vector<uint8_t> ok(names.size());
+    for (size_t c = 0; c < names.size(); c++) ok[c] = !chrom_matches_any(excl, names[c]) && (incl.empty() || chrom_matches_any(incl, names[c]));
+    return ok;
+}
+inline std::vector<uint8_t> chrom_keep_table(const std::vector<const char *> &names, const std::vector<regex_t> &excl, const std::vector<regex_t> &incl)
+{
+    std::vector<uint8_t> ok(names.size());
+    for (size_t c = 0; c < names.size(); c++) ok[c] = incl.empty() ? !chrom_matches_any(excl, names[c]) : chrom_matches_any(incl, names[c]);
+    return ok;
+}
 
 // From each end of the read walk inwards until min_flank consecutive bases match the target; what lies outside is trimmed.
 // SE: a read that cannot keep half its length (>= 15) between two such runs becomes eNARTrim (6); PE: the walks stop after a

@@ -23,11 +23,11 @@ namespace bkcli {
 void report_read_subset(Report &R, const char *opt, const char *tag, bool (*want)(uint8_t))
 {
     const Args &a = R.a;
-    auto &hits = R.hits;
+    const bk::RecordSet &recs = R.rec;
+    auto &hits = recs.hits;
     auto &rs = R.rs;
-    const size_t nr = R.hits.size();
+    const size_t nr = recs.hits.size();
     const auto &order = R.order;
-    auto RD = [&](size_t i) -> size_t { return R.RD(i); };
     const int ml_mode = R.ml_mode;
     if (!a.has(opt) || ml_mode == 5) return;                         // kanga.cpp:1045-1066
     OutBuf o;
@@ -38,10 +38,10 @@ void report_read_subset(Report &R, const char *opt, const char *tag, bool (*want
     for (size_t k = 0; k < nr; k++) {
         const uint32_t i = order[k];
         if (!want(hits[i].nar)) continue;
-        const uint32_t len = rs.lens[RD(i)];
-        const uint8_t *sq = rs.bases.data() + rs.offs[RD(i)];
+        const uint32_t len = rs.lens[recs.RD(i)];
+        const uint8_t *sq = rs.bases.data() + rs.offs[recs.RD(i)];
         char hd[400];
-        int n = snprintf(hd, sizeof(hd), ">lcl|%s|%u %s %u|1|%u\n", tag, i + 1, rs.name(RD(i)), i + 1, len);
+        int n = snprintf(hd, sizeof(hd), ">lcl|%s|%u %s %u|1|%u\n", tag, i + 1, rs.name(recs.RD(i)), i + 1, len);
         rec.assign(hd, (size_t)n);
         for (uint32_t q = 0; q < len; q++) {
             rec.push_back(up[sq[q] & 7]);
@@ -57,17 +57,13 @@ void report_read_subset(Report &R, const char *opt, const char *tag, bool (*want
 void report_stats(Report &R)
 {
     const Args &a = R.a;
-    auto &hits = R.hits;
+    const bk::RecordSet &recs = R.rec;
+    auto &hits = recs.hits;
     auto &rs = R.rs;
     auto &ents = R.ents;
     const uint32_t n_ent = R.n_ent;
-    const size_t nr = R.hits.size();
+    const size_t nr = recs.hits.size();
     const auto &multi_dist = R.multi_dist;
-    auto RD = [&](size_t i) -> size_t { return R.RD(i); };
-    auto has_seg2 = [&](size_t i) -> bool { return R.has_seg2(i); };
-    auto TL = [&](size_t i) -> uint32_t { return R.TL(i); };
-    auto a_start = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_start(h, i); };
-    auto a_len = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_len(h, i); };
     const int pe_mode = R.pe_mode, ml_mode = R.ml_mode, max_ml = R.max_ml, nthreads = R.nthreads;
     if (!a.has("O")) return;
     FILE *f = fopen(a.str("O").c_str(), "w");
@@ -85,7 +81,7 @@ void report_stats(Report &R)
     }
     size_t n_acc = 0;
     uint32_t max_len = 0;
-    for (size_t i = 0; i < nr; i++) if (hits[i].nar == BK_NAR_ACCEPTED) { n_acc++; max_len = std::max(max_len, rs.lens[RD(i)]); }
+    for (size_t i = 0; i < nr; i++) if (hits[i].nar == BK_NAR_ACCEPTED) { n_acc++; max_len = std::max(max_len, rs.lens[recs.RD(i)]); }
     if (n_acc && max_len) {
         bk::SfxFile sf;
         std::string serr;
@@ -100,11 +96,11 @@ void report_stats(Report &R)
                 auto &Q = qi[(size_t)w], &S = sb[(size_t)w], &M = ms[(size_t)w];
                 for (size_t i = (size_t)w; i < nr; i += (size_t)nthreads) {
                     const bk_hit &h = hits[i];
-                    if (h.nar != BK_NAR_ACCEPTED || h.chrom_id < 1 || h.chrom_id > n_ent || has_seg2(i)) continue;     // FlagSegs reads are sloughed (:6286)
-                    const uint8_t *rd = rs.bases.data() + rs.offs[RD(i)];
-                    const uint32_t len = rs.lens[RD(i)];
-                    const uint8_t *tg = sf.seq + ents[h.chrom_id - 1].start_ofs + a_start(h, i);
-                    const uint32_t alen = a_len(h, i), tl0 = TL(i);
+                    if (h.nar != BK_NAR_ACCEPTED || h.chrom_id < 1 || h.chrom_id > n_ent || recs.has_seg2(i)) continue;     // FlagSegs reads are sloughed (:6286)
+                    const uint8_t *rd = rs.bases.data() + rs.offs[recs.RD(i)];
+                    const uint32_t len = rs.lens[recs.RD(i)];
+                    const uint8_t *tg = sf.seq + ents[h.chrom_id - 1].start_ofs + recs.a_start(h, i);
+                    const uint32_t alen = recs.a_len(h, i), tl0 = recs.TL(i);
                     uint32_t nsub = 0;
                     for (uint32_t k = 0; k < alen && tl0 + k < len; k++) {      // read positions TrimLeft .. ReadLen - TrimRight (:6303-6306)
                         uint8_t t = h.strand == '-' ? tg[alen - 1 - k] & 7 : tg[k] & 7;
@@ -166,17 +162,16 @@ void report_stats(Report &R)
 void report_jct_for_sam(Report &R)
 {
     const Args &a = R.a;
-    auto &hits = R.hits;
+    const bk::RecordSet &recs = R.rec;
+    auto &hits = recs.hits;
     auto &ents = R.ents;
-    const size_t nr = R.hits.size();
+    const size_t nr = recs.hits.size();
     const auto &order = R.order;
-    const auto &seg2 = R.seg2;
-    auto RD = [&](size_t i) -> size_t { return R.RD(i); };
-    auto has_seg2 = [&](size_t i) -> bool { return R.has_seg2(i); };
+    const auto &seg2 = recs.seg2;
     const int fmt = R.fmt, splice_len = R.splice_len;
     if (!splice_len || fmt < 5) return;
     std::string jp = a.str("o");
-    if (jp.size() > 3 && !strcasecmp(jp.c_str() + jp.size() - 3, ".gz")) jp.resize(jp.size() - 3);
+    if (is_gz_name(jp)) jp.resize(jp.size() - 3);
     OutBuf j;
     j.open((jp + ".jct").c_str());
     if (j.fd < 0) { diag("Unable to create '%s.jct'", jp.c_str()); return; }
@@ -186,8 +181,8 @@ void report_jct_for_sam(Report &R)
     for (size_t k = 0; k < nr; k++) {
         const uint32_t i = order[k];
         const bk_hit &h = hits[i];
-        if (h.nar != BK_NAR_ACCEPTED || !has_seg2(i) || !(seg2[RD(i)].flags & 4)) continue;
-        const bk_seg2 &g = seg2[RD(i)];
+        if (h.nar != BK_NAR_ACCEPTED || !recs.has_seg2(i) || !(seg2[recs.RD(i)].flags & 4)) continue;
+        const bk_seg2 &g = seg2[recs.RD(i)];
         const uint32_t end1 = g.match_loci + g.match_len;
         m = snprintf(ln, sizeof(ln), "%s\t%u\t%u\tarj\t0\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1, (char)h.strand,
                      h.match_loci, end1, (unsigned)h.match_len, (unsigned)g.match_len, g.match_loci - h.match_loci);
@@ -214,20 +209,15 @@ static std::vector<uint8_t> seqs_with_hits(const std::vector<bk_hit> &hits, uint
     // ".bam" (more than 5 characters of name, kanga.cpp:848-857): BGZF-compressed BAM with its BAI index
 int report_bam(Report &R, const std::string &opath)
 {
-    auto &hits = R.hits;
+    const bk::RecordSet &recs = R.rec;
+    auto &hits = recs.hits;
     auto &rs = R.rs;
     auto &ents = R.ents;
     const std::string &species = R.species;
     const uint32_t n_ent = R.n_ent;
-    const size_t nr = R.hits.size();
+    const size_t nr = recs.hits.size();
     const auto &order = R.order;
-    const auto &seg2 = R.seg2;
-    auto RD = [&](size_t i) -> size_t { return R.RD(i); };
-    auto has_seg2 = [&](size_t i) -> bool { return R.has_seg2(i); };
-    auto TL = [&](size_t i) -> uint32_t { return R.TL(i); };
-    auto TR = [&](size_t i) -> uint32_t { return R.TR(i); };
-    auto a_start = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_start(h, i); };
-    auto a_len = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_len(h, i); };
+    const auto &seg2 = recs.seg2;
     const int pe_mode = R.pe_mode, fmt = R.fmt, nthreads = R.nthreads, max_rpt_sam_seqs = R.max_rpt_sam_seqs;
     int rc = 0;
     std::vector<uint8_t> has_hit = seqs_with_hits(hits, n_ent, nthreads);
@@ -276,8 +266,8 @@ int report_bam(Report &R, const std::string &opath)
             const bk_hit &h = hits[i];
             const bool acc = h.nar == BK_NAR_ACCEPTED;
             if (!acc && fmt != 6) continue;
-            const uint8_t *sq = rs.bases.data() + rs.offs[RD(i)];
-            const uint32_t len = rs.lens[RD(i)];
+            const uint8_t *sq = rs.bases.data() + rs.offs[recs.RD(i)];
+            const uint32_t len = rs.lens[recs.RD(i)];
             int flag = 0, tlen = 0;
             long pnext = -1;
             if (!pe_mode) flag = acc ? (h.strand == '+' ? 0 : 16) : 4;
@@ -290,23 +280,23 @@ int report_bam(Report &R, const std::string &opath)
                     flag |= m.strand == '+' ? 0 : 0x20;
                     if (acc) {
                         const size_t mi = first_of_pair ? i + 1 : i - 1;
-                        pnext = (long)a_start(m, mi);
-                        long s0 = (long)a_start(h, i), s1 = (long)a_start(m, mi);
-                        tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)a_len(m, mi) : (s0 - s1) + (long)a_len(h, i));
+                        pnext = (long)recs.a_start(m, mi);
+                        long s0 = (long)recs.a_start(h, i), s1 = (long)recs.a_start(m, mi);
+                        tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)recs.a_len(m, mi) : (s0 - s1) + (long)recs.a_len(h, i));
                     }
                 } else
                     flag |= 0x8;
             }
-            const char *qn = rs.name(RD(i));
+            const char *qn = rs.name(recs.RD(i));
             const uint32_t l_qn = (uint32_t)strlen(qn) + 1;
             const char *tag = acc ? nullptr : kNarTag[h.nar < 20 ? h.nar : 0];
             const uint32_t aux = tag ? 3 + (uint32_t)strlen(tag) + 1 : 0;
-            const bool two = acc && has_seg2(i);
+            const bool two = acc && recs.has_seg2(i);
             // soft clips in target order: read orientation for '+', swapped for '-' (Aligner.cpp:5961-5984)
-            const uint32_t clip5 = acc ? (h.strand == '+' ? TL(i) : TR(i)) : 0u, clip3 = acc ? (h.strand == '+' ? TR(i) : TL(i)) : 0u;
+            const uint32_t clip5 = acc ? (h.strand == '+' ? recs.TL(i) : recs.TR(i)) : 0u, clip3 = acc ? (h.strand == '+' ? recs.TR(i) : recs.TL(i)) : 0u;
             const uint32_t n_cig = (two ? 3u : 1u) + (clip5 ? 1u : 0u) + (clip3 ? 1u : 0u);
-            const uint32_t pos0 = acc ? a_start(h, i) : 0u;
-            const uint32_t hit_len = acc ? a_len(h, i) + (two ? seg2[RD(i)].match_len : 0u) : 0u;      // AdjAlignHitLen
+            const uint32_t pos0 = acc ? recs.a_start(h, i) : 0u;
+            const uint32_t hit_len = acc ? recs.a_len(h, i) + (two ? seg2[recs.RD(i)].match_len : 0u) : 0u;      // AdjAlignHitLen
             const uint32_t block = 32 + l_qn + 4 * n_cig + (len + 1) / 2 + len + aux;
             const size_t at = v.size();
             v.resize(at + 4 + block);
@@ -325,10 +315,10 @@ int report_bam(Report &R, const std::string &opath)
             w32((uint32_t)tlen);
             memcpy(q, qn, l_qn); q += l_qn;
             if (clip5) w32(clip5 << 4 | 4u);
-            w32((acc ? a_len(h, i) : len) << 4);
+            w32((acc ? recs.a_len(h, i) : len) << 4);
             if (clip3) w32(clip3 << 4 | 4u);
             if (two) {
-                const bk_seg2 &g = seg2[RD(i)];
+                const bk_seg2 &g = seg2[recs.RD(i)];
                 if (g.flags & 4) w32((uint32_t)((long)g.match_loci - ((long)h.match_loci + h.match_len)) << 4 | 3u);
                 else if (g.flags & 2) w32((uint32_t)((long)len - ((long)h.match_len + g.match_len)) << 4 | 1u);
                 else { long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len); w32((uint32_t)(gap < 0 ? -gap : gap) << 4 | 2u); }
@@ -390,21 +380,15 @@ int report_bam(Report &R, const std::string &opath)
 int report_text(Report &R)
 {
     const Args &a = R.a;
-    auto &hits = R.hits;
+    const bk::RecordSet &recs = R.rec;
+    auto &hits = recs.hits;
     auto &rs = R.rs;
     auto &ents = R.ents;
     const std::string &species = R.species;
     const uint32_t n_ent = R.n_ent;
-    const size_t nr = R.hits.size();
+    const size_t nr = recs.hits.size();
     const auto &order = R.order;
-    const auto &seg2 = R.seg2;
-    auto RD = [&](size_t i) -> size_t { return R.RD(i); };
-    auto has_seg2 = [&](size_t i) -> bool { return R.has_seg2(i); };
-    auto TL = [&](size_t i) -> uint32_t { return R.TL(i); };
-    auto TR = [&](size_t i) -> uint32_t { return R.TR(i); };
-    auto a_start = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_start(h, i); };
-    auto a_len = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_len(h, i); };
-    auto a_mm = [&](const bk_hit &h, size_t i) -> uint32_t { return R.a_mm(h, i); };
+    const auto &seg2 = recs.seg2;
     const int pe_mode = R.pe_mode, ml_mode = R.ml_mode, fmt = R.fmt, nthreads = R.nthreads, micro_indel = R.micro_indel, splice_len = R.splice_len, max_rpt_sam_seqs = R.max_rpt_sam_seqs;
     OutBuf out;
     if (R.pre != nullptr && fmt >= 5) { out.fd = R.pre->fd; out.borrowed = true; out.b.reserve(8 << 20); }
@@ -467,9 +451,9 @@ int report_text(Report &R)
             const bk_hit &h = hits[i];
             bool acc = h.nar == BK_NAR_ACCEPTED;
             if (!acc && fmt != 6) return false;
-            const uint8_t *s = rs.bases.data() + rs.offs[RD(i)];
-            uint32_t len = rs.lens[RD(i)];
-            const char *nm = rs.name(RD(i));
+            const uint8_t *s = rs.bases.data() + rs.offs[recs.RD(i)];
+            uint32_t len = rs.lens[recs.RD(i)];
+            const char *nm = rs.name(recs.RD(i));
             const size_t nml = strlen(nm);
             char *w = st.room(nml + 2 * (size_t)len + 400);
             memcpy(w, nm, nml);
@@ -486,9 +470,9 @@ int report_text(Report &R)
                     flag |= m.strand == '+' ? 0 : 0x20;
                     if (acc) {
                         const size_t mi = first_of_pair ? i + 1 : i - 1;
-                        pnext = (long)a_start(m, mi);
-                        long s0 = (long)a_start(h, i), s1 = (long)a_start(m, mi);
-                        tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)a_len(m, mi) : (s0 - s1) + (long)a_len(h, i));
+                        pnext = (long)recs.a_start(m, mi);
+                        long s0 = (long)recs.a_start(h, i), s1 = (long)recs.a_start(m, mi);
+                        tlen = (int)(s0 <= s1 ? (s1 - s0) + (long)recs.a_len(m, mi) : (s0 - s1) + (long)recs.a_len(h, i));
                     }
                 } else
                     flag |= 0x8;
@@ -499,15 +483,15 @@ int report_text(Report &R)
                 *w++ = '\t';
                 w = put_str(w, ents[h.chrom_id - 1].name);
                 *w++ = '\t';
-                w = put_num(w, (long)a_start(h, i) + 1);
+                w = put_num(w, (long)recs.a_start(h, i) + 1);
                 w = put_str(w, "\t255\t");
-                const uint32_t clip5 = h.strand == '+' ? TL(i) : TR(i), clip3 = h.strand == '+' ? TR(i) : TL(i);
+                const uint32_t clip5 = h.strand == '+' ? recs.TL(i) : recs.TR(i), clip3 = h.strand == '+' ? recs.TR(i) : recs.TL(i);
                 if (clip5) { w = put_num(w, clip5); *w++ = 'S'; }
-                w = put_num(w, a_len(h, i));
+                w = put_num(w, recs.a_len(h, i));
                 *w++ = 'M';
                 if (clip3) { w = put_num(w, clip3); *w++ = 'S'; }
-                if (has_seg2(i)) {                                       // CAligner::ReportBAMread, Aligner.cpp:5986-6033
-                    const bk_seg2 &g = seg2[RD(i)];
+                if (recs.has_seg2(i)) {                                       // CAligner::ReportBAMread, Aligner.cpp:5986-6033
+                    const bk_seg2 &g = seg2[recs.RD(i)];
                     if (g.flags & 4) { w = put_num(w, (long)g.match_loci - ((long)h.match_loci + h.match_len)); *w++ = 'N'; }
                     else if (g.flags & 2) { w = put_num(w, (long)len - ((long)h.match_len + g.match_len)); *w++ = 'I'; }
                     else { long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len); w = put_num(w, gap < 0 ? -gap : gap); *w++ = 'D'; }
@@ -613,10 +597,10 @@ int report_text(Report &R)
             job.hits = hits.data(); job.n_reads = nr; job.order = order.data(); job.n_order = nr;
             // (index spaces: src, the trims, hits and order go by record; seg2 and everything of the read store by read)
             const size_t n_rd = rs.lens.size();
-            bool job_ok = R.src.empty() ? n_rd == nr : R.src.size() == nr;
-            if (!R.src.empty()) { job.src = R.src.data(); job.n_src_reads = n_rd; }
-            if (!R.seg2.empty()) { job.seg2 = R.seg2.data(); job_ok = job_ok && R.seg2.size() == n_rd; }
-            if (!R.trims.empty()) { job.trim_left = R.trims.left.data(); job.trim_right = R.trims.right.data(); job_ok = job_ok && R.trims.left.size() == nr && R.trims.right.size() == nr; }
+            bool job_ok = recs.src.empty() ? n_rd == nr : recs.src.size() == nr;
+            if (!recs.src.empty()) { job.src = recs.src.data(); job.n_src_reads = n_rd; }
+            if (!recs.seg2.empty()) { job.seg2 = recs.seg2.data(); job_ok = job_ok && recs.seg2.size() == n_rd; }
+            if (!recs.trims.empty()) { job.trim_left = recs.trims.left.data(); job.trim_right = recs.trims.right.data(); job_ok = job_ok && recs.trims.left.size() == nr && recs.trims.right.size() == nr; }
             job.report_unaligned = fmt == 6 ? 1 : 0; job.pe_mode = pe_mode;
             job.pk_words = R.pk_words; job.n_pk_words = R.n_pk_words; job.pk_lens16 = R.pk_lens16; job.pk_exc = R.pk_exc; job.n_pk_exc = R.n_pk_exc;
             job.prep = R.sam_prep;
@@ -665,7 +649,7 @@ int report_text(Report &R)
             out.flush();
             const bool with_qual = a.num("g", 3) != 3;                                 // QUAL is '*' unless FASTQ scores were loaded (-g0..2)
             uint64_t est = (uint64_t)out.pos + rs.name_bytes() + 64ULL * nr + (pe_mode ? 24ULL * nr : 0);
-            for (size_t k = 0; k < nr; k++) est += (with_qual ? 2ULL : 1ULL) * rs.lens[RD(k)];
+            for (size_t k = 0; k < nr; k++) est += (with_qual ? 2ULL : 1ULL) * rs.lens[recs.RD(k)];
             const int pfd = out.fd;
             prealloc = std::thread([pfd, est, &prealloc_size]() {
                 const off_t step = 256LL << 20;
@@ -688,13 +672,13 @@ int report_text(Report &R)
                     if (k + 16 < hi) {
                         const uint32_t j = order[k + 16];
                         __builtin_prefetch(&hits[j]);
-                        const size_t r = RD(j);
+                        const size_t r = recs.RD(j);
                         __builtin_prefetch(&rs.offs[r]);
                         __builtin_prefetch(&rs.lens[r]);
                         __builtin_prefetch(&rs.name_ofs[r]);
                     }
                     if (k + 8 < hi) {
-                        const size_t r = RD(order[k + 8]);
+                        const size_t r = recs.RD(order[k + 8]);
                         const uint8_t *b = rs.bases.data() + rs.offs[r];
                         __builtin_prefetch(b);
                         __builtin_prefetch(b + 64);
@@ -827,17 +811,17 @@ int report_text(Report &R)
                     uint32_t i = order[k];
                     const bk_hit &h = hits[i];
                     if (h.nar != BK_NAR_ACCEPTED) continue;
-                    const bool two = has_seg2(i);
+                    const bool two = recs.has_seg2(i);
                     if (fmt == 4) {
                         if (two) {
-                            const bk_seg2 &g = seg2[RD(i)];
+                            const bk_seg2 &g = seg2[recs.RD(i)];
                             const bool sj = (g.flags & 4) != 0;
                             const uint32_t end1 = g.match_loci + g.match_len;          // AdjAlignEndLoci + 1
                             int m = snprintf(line, sizeof(line), "%s\t%u\t%u\t%s\t%d\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1,
                                              sj ? "arj" : "ari", R.score(h, i), (char)h.strand, h.match_loci, end1, (unsigned)h.match_len, (unsigned)g.match_len, g.match_loci - h.match_loci);
                             (sj ? M.jct : M.ind).append(line, (size_t)m);
                         } else {
-                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\tar\t%d\t%c\n", ents[h.chrom_id - 1].name, a_start(h, i), a_start(h, i) + a_len(h, i),
+                            int m = snprintf(line, sizeof(line), "%s\t%u\t%u\tar\t%d\t%c\n", ents[h.chrom_id - 1].name, recs.a_start(h, i), recs.a_start(h, i) + recs.a_len(h, i),
                                              R.score(h, i), (char)h.strand);
                             M.out.append(line, (size_t)m);
                         }
@@ -845,16 +829,16 @@ int report_text(Report &R)
                         continue;
                     }
                     // one line per segment (WriteReadHits, Aligner.cpp:6566-6627)
-                    const uint32_t len = rs.lens[RD(i)];
+                    const uint32_t len = rs.lens[recs.RD(i)];
                     for (int sg = 0; sg < (two ? 2 : 1); sg++) {
-                        const uint32_t s_loci = sg ? seg2[RD(i)].match_loci : a_start(h, i), s_len = sg ? seg2[RD(i)].match_len : a_len(h, i);
-                        const uint32_t s_mm = sg ? seg2[RD(i)].mismatches : a_mm(h, i), s_rofs = sg ? seg2[RD(i)].read_ofs : TL(i);       // ReadOfs + TrimLeft
+                        const uint32_t s_loci = sg ? seg2[recs.RD(i)].match_loci : recs.a_start(h, i), s_len = sg ? seg2[recs.RD(i)].match_len : recs.a_len(h, i);
+                        const uint32_t s_mm = sg ? seg2[recs.RD(i)].mismatches : recs.a_mm(h, i), s_rofs = sg ? seg2[recs.RD(i)].read_ofs : recs.TL(i);       // ReadOfs + TrimLeft
                         int m = snprintf(line, sizeof(line), "%u,\"%s\",\"%s\",\"%s\",%u,%u,%u,\"%c\",%d,0,1,%u,\"N/A\",\"%s\"", i + 1,
-                                         two ? ((seg2[RD(i)].flags & 4) ? "arj" : "ari") : "ar", species.c_str(),
-                                         ents[h.chrom_id - 1].name, s_loci, s_loci + s_len - 1, (unsigned)s_len, (char)h.strand, R.score(h, i), (unsigned)s_mm, rs.name(RD(i)));
+                                         two ? ((seg2[recs.RD(i)].flags & 4) ? "arj" : "ari") : "ar", species.c_str(),
+                                         ents[h.chrom_id - 1].name, s_loci, s_loci + s_len - 1, (unsigned)s_len, (char)h.strand, R.score(h, i), (unsigned)s_mm, rs.name(recs.RD(i)));
                         rec.assign(line, (size_t)m);
                         if (fmt >= 2) {                                          // the read as loaded, from the segment's read offset
-                            const uint8_t *sq = rs.bases.data() + rs.offs[RD(i)];
+                            const uint8_t *sq = rs.bases.data() + rs.offs[recs.RD(i)];
                             rec += ",\"";
                             for (uint32_t q = 0; q < s_len && s_rofs + q < len; q++) rec.push_back(up[sq[s_rofs + q] & 7]);
                             rec.push_back('"');

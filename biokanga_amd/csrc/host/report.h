@@ -10,17 +10,14 @@
 namespace bkcli {
 
 // ---------------------------------------------------------------------------------------------
-// Everything the reporting functions need about one `align` run (references into cmd_align's state)
+// Everything the reporting functions need about one `align` run (references into its AlignRun; the records and their accessors: rec)
 struct Report {
     const Args &a;
     ReadStore &rs;
-    std::vector<bk_hit> &hits;                    // one per record (a read, or a reported locus in -r5)
+    const bk::RecordSet &rec;                     // one record per read, or per reported locus in -r5 (post_filters.h)
     const std::vector<bk_entry_info> &ents;
     const std::string &species;
     uint32_t n_ent;
-    const std::vector<uint32_t> &src;             // -r5: record -> read
-    const std::vector<bk_seg2> &seg2;             // per read: second segment / chimeric trims
-    const bk::FlankTrims &trims;                  // per record
     const std::vector<int> &multi_dist;
     const std::vector<uint32_t> &order;           // records in the reference's output order
     int pe_mode, ml_mode, max_ml, fmt, nthreads, micro_indel, splice_len, max_rpt_sam_seqs;
@@ -39,14 +36,7 @@ struct Report {
     const bk_nbase *pk_exc = nullptr;
     uint64_t n_pk_exc = 0;
 
-    size_t RD(size_t i) const { return src.empty() ? i : (size_t)src[i]; }
-    bool has_seg2(size_t i) const { return !seg2.empty() && (seg2[RD(i)].flags & 5); }       // FlgInDel or FlgSplice
-    uint32_t TL(size_t i) const { return trims.empty() ? 0u : trims.left[i]; }
-    uint32_t TR(size_t i) const { return trims.empty() ? 0u : trims.right[i]; }
-    uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci
-    uint32_t a_len(const bk_hit &h, size_t i) const { return (uint32_t)h.match_len - TL(i) - TR(i); }                      // AdjHitLen
     int score(const bk_hit &h, size_t i) const { return site_prefs ? site_prefs->score(h.strand, i) : 0; }                // Aligner.cpp:6447
-    uint32_t a_mm(const bk_hit &h, size_t i) const { return trims.empty() ? h.mismatches : trims.mismatches[i]; }         // TrimMismatches
 };
 
 void report_read_subset(Report &R, const char *opt, const char *tag, bool (*want)(uint8_t));

@@ -82,7 +82,7 @@ inline const char *kCentroidCase = "ACGT";     // CSeqTrans::MapSeq2Ascii
 inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
 {
     using namespace snp_detail;
-    const size_t nrec = R.hits.size();
+    const size_t nrec = R.rec.hits.size();
     OutBuf snp_out, di_out, tri_out;
     snp_out.open(o.path.c_str());
     if (snp_out.fd < 0) { diag("Fatal: Unable to create/truncate SNP file '%s'", o.path.c_str()); return 1; }
@@ -143,7 +143,7 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
     }
 
     // the reads ProcessSNPs piles up: accepted, neither microInDel nor spliced (:7739-7744)
-    auto piled = [&](size_t i) { return R.hits[i].nar == BK_NAR_ACCEPTED && !R.has_seg2(i); };
+    auto piled = [&](size_t i) { return R.rec.hits[i].nar == BK_NAR_ACCEPTED && !R.rec.has_seg2(i); };
     int rc = bk_snp_reset(ctx);
     if (rc) { diag("Fatal: SNP pile-up could not be set up: %s", bk_strerror(rc)); return 1; }
     struct ChromAcc { uint64_t tot_len = 0, n_reads = 0; size_t first = (size_t)-1, last = 0; };
@@ -152,12 +152,12 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
     for (size_t k = 0; k < R.order.size(); k++) {          // sequences in the order the sorted reads reach them
         const size_t i = R.order[k];
         if (!piled(i)) continue;
-        const bk_hit &h = R.hits[i];
+        const bk_hit &h = R.rec.hits[i];
         ChromAcc &c = acc[h.chrom_id];
         if (c.first == (size_t)-1) { c.first = k; chrom_order.push_back(h.chrom_id); }
         c.last = k;
-        uint32_t len = R.a_len(h, i);
-        const uint32_t clen = (uint32_t)R.ents[h.chrom_id - 1].seq_len, st = R.a_start(h, i);
+        uint32_t len = R.rec.a_len(h, i);
+        const uint32_t clen = (uint32_t)R.ents[h.chrom_id - 1].seq_len, st = R.rec.a_start(h, i);
         if (st + len > clen) { if ((int)clen - (int)st < 10) continue; len = clen - st; }
         c.tot_len += len; c.n_reads++;
     }
@@ -169,14 +169,14 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
             alns.clear();
             for (size_t i = r0; i < r1; i++) {
                 if (!piled(i)) continue;
-                const bk_hit &h = R.hits[i];
+                const bk_hit &h = R.rec.hits[i];
                 bk_snp_aln a{};
-                a.read_idx = (uint32_t)(R.RD(i) - R.RD(r0)); a.chrom_id = h.chrom_id; a.loci = R.a_start(h, i); a.len = (uint16_t)R.a_len(h, i);
-                a.read_ofs = (uint16_t)R.TL(i); a.strand = h.strand;
+                a.read_idx = (uint32_t)(R.rec.RD(i) - R.rec.RD(r0)); a.chrom_id = h.chrom_id; a.loci = R.rec.a_start(h, i); a.len = (uint16_t)R.rec.a_len(h, i);
+                a.read_ofs = (uint16_t)R.rec.TL(i); a.strand = h.strand;
                 alns.push_back(a);
             }
             if (alns.empty()) continue;
-            const size_t rd0 = R.RD(r0), rd1 = R.RD(r1 - 1) + 1;
+            const size_t rd0 = R.rec.RD(r0), rd1 = R.rec.RD(r1 - 1) + 1;
             rc = bk_snp_pileup(ctx, R.rs.bases.data(), R.rs.offs.data() + rd0, R.rs.lens.data() + rd0, (uint32_t)(rd1 - rd0), alns.data(), alns.size());
             if (rc) { diag("Fatal: SNP pile-up failed: %s", bk_strerror(rc)); return 1; }
         }
@@ -298,9 +298,9 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
                 if (nxt == kNone) return kNone;
                 const size_t i = R.order[nxt];
                 if (piled(i)) {
-                    const bk_hit &h = R.hits[i];
+                    const bk_hit &h = R.rec.hits[i];
                     if (h.chrom_id != chrom) return kNone;
-                    const int cs = (int)R.a_start(h, i), ce = (int)(R.a_start(h, i) + R.a_len(h, i) - 1);
+                    const int cs = (int)R.rec.a_start(h, i), ce = (int)(R.rec.a_start(h, i) + R.rec.a_len(h, i) - 1);
                     if (cs <= start_loci && ce >= end_loci) {
                         a.prev_iter = nxt;
                         if (fresh) a.first_iter = nxt;
@@ -314,10 +314,10 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
         };
         auto snp_base = [&](size_t k, uint32_t loci) -> uint32_t {     // CAligner::AdjAlignSNPBase (:1475-1518)
             const size_t i = R.order[k];
-            const bk_hit &h = R.hits[i];
-            const uint32_t as = R.a_start(h, i), ae = as + R.a_len(h, i) - 1;
+            const bk_hit &h = R.rec.hits[i];
+            const uint32_t as = R.rec.a_start(h, i), ae = as + R.rec.a_len(h, i) - 1;
             if (as > loci || ae < loci) return 7;
-            const uint8_t *b = R.rs.bases.data() + R.rs.offs[R.RD(i)];
+            const uint8_t *b = R.rs.bases.data() + R.rs.offs[R.rec.RD(i)];
             if (h.strand == '+') return b[loci - h.match_loci] & 7u;
             uint32_t v = b[h.match_loci + h.match_len - loci - 1] & 7u;
             return v < 4 ? 3 - v : v;
@@ -365,7 +365,7 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
                     if (cb > 3) continue;
                     bc[1][pb]++; bc[0][cb]++;
                     n_over++;
-                    if (R.hits[R.order[rd]].strand == '-') n_anti++;
+                    if (R.rec.hits[R.order[rd]].strand == '-') n_anti++;
                     cnts[((pb & 3) << 2) | (cb & 3)]++;
                 }
                 if (n_over >= o.min_reads) {
@@ -400,7 +400,7 @@ inline int process_snps(bk_ctx *ctx, Report &R, const SnpOpts &o)
                     if (cb > 3) continue;
                     bc[2][fb]++; bc[1][pb]++; bc[0][cb]++;
                     n_over++;
-                    if (R.hits[R.order[rd]].strand == '-') n_anti++;
+                    if (R.rec.hits[R.order[rd]].strand == '-') n_anti++;
                     cnts[((fb & 3) << 4) | ((pb & 3) << 2) | (cb & 3)]++;
                 }
                 if (n_over >= o.min_reads) {

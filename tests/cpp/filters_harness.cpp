@@ -2,10 +2,14 @@
 //   filters_harness <min_flank> <paired 0|1> <splice 0|1> <indel 0|1> hits.bin seg2.bin bases.bin offs.bin seq.bin ent_start.bin out_hits.bin out_trims.bin
 // seq.bin: the index's concatenated target (1 byte/base), ent_start.bin: uint64 start offset per entry (EntryID - 1)
 // out_trims.bin: per record uint16 left, uint16 right, uint16 trimmed mismatches
+//   filters_harness pcr <win_len> hits.bin out_hits.bin
+//   filters_harness chroms <names> <exclude expressions> <include expressions>     (comma separated, "-" for none)
+//   filters_harness select <n> <threads> third|none|all out.bin                    (host/cli_common.h's par_select)
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
+#include "../../biokanga_amd/csrc/host/cli_common.h"
 #include "../../biokanga_amd/csrc/host/mtqsort.h"
 #include "../../biokanga_amd/csrc/host/post_filters.h"
 
@@ -23,8 +27,63 @@ static std::vector<T> slurp(const char *path)
     return v;
 }
 
+static std::vector<std::string> split(const char *list)
+{
+    std::vector<std::string> v;
+    const std::string s = list;
+    if (s == "-") return v;
+    for (size_t at = 0; at <= s.size();) {
+        size_t end = s.find(',', at);
+        if (end == std::string::npos) end = s.size();
+        v.push_back(s.substr(at, end - at));
+        at = end + 1;
+    }
+    return v;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 5 && std::string(argv[1]) == "chroms") {
+        // the two tables of -Z / -z over the names given, with the expressions compiled the way read_align_opts compiles them:
+        // prints "accept <names that pass>" and "keep <names that pass>"
+        const std::vector<std::string> names = split(argv[2]);
+        std::vector<const char *> np;
+        for (const std::string &n : names) np.push_back(n.c_str());
+        std::vector<regex_t> re[2];
+        for (int k = 0; k < 2; k++)
+            for (const std::string &pat : split(argv[3 + k])) {
+                regex_t x;
+                if (regcomp(&x, pat.c_str(), REG_EXTENDED | REG_ICASE)) return 3;
+                re[k].push_back(x);
+            }
+        const std::vector<uint8_t> acc = bk::chrom_accept_table(np, re[0], re[1]), keep = bk::chrom_keep_table(np, re[0], re[1]);
+        for (const auto *t : {&acc, &keep}) {
+            printf(t == &acc ? "accept" : "keep");
+            for (size_t c = 0; c < names.size(); c++) if ((*t)[c]) printf(" %s", names[c].c_str());
+            printf("\n");
+        }
+        for (auto &v : re) for (regex_t &x : v) regfree(&x);
+        return 0;
+    }
+    if (argc == 6 && std::string(argv[1]) == "select") {
+        // out.bin: the selected i by slot (uint32); prints "count <returned> written <slots written> dense <0|1>" - dense when every
+        // slot below the count was written exactly once and none beyond
+        const size_t n = (size_t)atol(argv[2]);
+        const std::string what = argv[4];
+        std::vector<uint32_t> out(n, 0xffffffffu), times(n, 0);
+        size_t sized_to = (size_t)-1;
+        const size_t cnt = bkcli::par_select(n, atoi(argv[3]), [&](size_t i) { return what == "all" || (what == "third" && i % 3 == 0); },
+                                             [&](size_t slot, size_t i) { if (slot < n) { out[slot] = (uint32_t)i; times[slot]++; } },
+                                             [&](size_t c) { sized_to = c; });
+        size_t written = 0;
+        bool dense = sized_to == cnt && cnt <= n;
+        for (size_t k = 0; k < n; k++) { written += times[k]; dense = dense && times[k] == (k < cnt ? 1u : 0u); }
+        printf("count %zu written %zu dense %d\n", cnt, written, dense ? 1 : 0);
+        FILE *f = fopen(argv[5], "wb");
+        if (cnt) fwrite(out.data(), 4, std::min(cnt, n), f);
+        fclose(f);
+        return 0;
+    }
     if (argc == 5 && std::string(argv[1]) == "pcr") {
         // filters_harness pcr <win_len> hits.bin out_hits.bin : CAligner::ReducePCRduplicates over the reference's sorted order
         const int win = atoi(argv[2]);

@@ -44,7 +44,8 @@ int main(int argc, char **argv)
     ReadStore rs;
     std::vector<bk_hit> hits(nr);
     std::vector<bk_seg2> seg2(nr);
-    bk::FlankTrims trims;
+    bk::RecordSet rec{hits, seg2, {}, {}, {}};
+    bk::FlankTrims &trims = rec.trims;
     const bool with_trims = (seed & 1) != 0;
     for (size_t i = 0; i < nr; i++) {
         const uint32_t len = 30 + rnd() % 170;
@@ -82,12 +83,12 @@ int main(int argc, char **argv)
             trims.mismatches.push_back((uint8_t)(rnd() % 3));
         }
     }
-    std::vector<uint32_t> order(nr), src;
+    std::vector<uint32_t> order(nr);
     for (size_t i = 0; i < nr; i++) order[i] = (uint32_t)i;
     for (size_t i = nr; i > 1; i--) std::swap(order[i - 1], order[rnd() % i]);
     std::vector<int> multi_dist;
     const std::string species = "synthetic";
-    Report R{a, rs, hits, ents, species, n_ent, src, seg2, trims, multi_dist, order, 0, 0, 1, fmt, nthreads, 5, 2000, 10000};
+    Report R{a, rs, rec, ents, species, n_ent, multi_dist, order, 0, 0, 1, fmt, nthreads, 5, 2000, 10000};
     const std::string op = argv[5];
     const int rc = (op.size() > 4 && op.substr(op.size() - 4) == ".bam") ? report_bam(R, op) : report_text(R);     // (as cmd_align picks)
     printf("rc %d\n", rc);

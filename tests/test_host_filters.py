@@ -1,6 +1,7 @@
 """Host filters on CPU (host/post_filters.h): the flank trimmer (-x, forced by -A) and the orphan junction filters, fed with the
 oracle's records, against what the real reference wrote: POS and CIGAR (soft clips, I/D/N) of every aligned read and the NAR tag
-of every other read of the -M6 SAM files of tests/golden/{basic,indel,splice}."""
+of every other read of the -M6 SAM files of tests/golden/{basic,indel,splice}.  Beside them the two tables the -Z / -z expressions
+are read by, and the front end's parallel compaction (host/cli_common.h, par_select)."""
 import os
 import struct
 import subprocess
@@ -113,3 +114,41 @@ def test_pcr_artefact_reduction_matches_reference(golden_tmp, filters_harness, t
     bad = [(nm, helpers.NAR_TAGS[got["nar"][i]], tags[nm]) for i, nm in enumerate(names) if helpers.NAR_TAGS[got["nar"][i]] != tags[nm]]
     assert not bad, (len(bad), bad[:5])
     assert np.count_nonzero(got["nar"] == 9) > 15000
+
+
+NAMES = ["chr1", "chr2", "chrM", "scaf_1"]
+# (exclude, include) -> names the accept-table (AcceptThisChromID: exclusion first) and the keep-table (FiltByChroms: inclusion first,
+# exclusion only when there is no include expression) let pass: worked out from the two rules as host/post_filters.h quotes them
+CHROM_CASES = [(["chrM", "chr2"], ["chr"], ["chr1"], ["chr1", "chr2", "chrM"]),
+               (["chrM"], [], ["chr1", "chr2", "scaf_1"], ["chr1", "chr2", "scaf_1"]),
+               ([], ["^scaf"], ["scaf_1"], ["scaf_1"]),
+               ([], [], NAMES, NAMES)]
+
+
+def chrom_tables(harness, names, excl, incl):
+    out = subprocess.check_output([harness, "chroms", ",".join(names), ",".join(excl) or "-", ",".join(incl) or "-"], text=True).splitlines()
+    assert [l.split()[0] for l in out] == ["accept", "keep"]
+    return out[0].split()[1:], out[1].split()[1:]
+
+
+@pytest.mark.parametrize("excl,incl,accept,keep", CHROM_CASES)
+def test_chrom_tables_follow_their_two_rules(filters_harness, excl, incl, accept, keep):
+    assert chrom_tables(filters_harness, NAMES, excl, incl) == (accept, keep)
+
+
+def test_chrom_expressions_ignore_case(filters_harness):
+    """REG_ICASE: a lower-case expression against an upper-case name, in either list"""
+    assert chrom_tables(filters_harness, ["CHRM", "CHR1"], ["chrm"], []) == (["CHR1"], ["CHR1"])
+    assert chrom_tables(filters_harness, ["CHRM", "CHR1"], [], ["chrm"]) == (["CHRM"], ["CHRM"])
+
+
+# (300001: the first size in the list at which more than one thread takes a range - a thread gets at least 65536 elements)
+@pytest.mark.parametrize("n", [0, 1, 7, 100000, 300001])
+@pytest.mark.parametrize("threads", [1, 3, 8])
+@pytest.mark.parametrize("what", ["third", "none", "all"])
+def test_par_select_is_the_serial_filter(filters_harness, tmp_path, n, threads, what):
+    op = str(tmp_path / "sel.bin")
+    line = subprocess.check_output([filters_harness, "select", str(n), str(threads), what, op], text=True).split()
+    exp = {"third": np.arange(0, n, 3), "none": np.arange(0), "all": np.arange(n)}[what].astype(np.uint32)
+    assert line == ["count", str(len(exp)), "written", str(len(exp)), "dense", "1"]
+    assert np.array_equal(np.fromfile(op, dtype=np.uint32), exp)
