@@ -112,6 +112,7 @@ struct bk_ctx {
     bool ktab_is2 = false;
     int use_iv32 = 1;        // phase 0 leaves the interval of a read's first k + 16 bases for the offset-0 cores of the later phases
     uint32_t wave_waves = 256u * 8u * 4u;   // resident waves the wave kernel is launched with
+    int wave_len_spec = 1;   // 1: a batch whose reads all have the same number of 16-base dwords gets the wave kernel's form compiled for it; 0: the generic form always
     int use_isa = 1;         // 0: no inverse suffix array - the wave kernel dedupes with its hash set (as it does for 5-byte indexes)
     int use_swin = 1;         // 0: none; 1: the part of the suffix array the wave kernel's long walks visit; 2: the same, whatever the batch's read lengths; 3: every suffix
     uint64_t swin_budget = 0; // most bytes the partial array may take (0: by the free memory)
@@ -201,15 +202,16 @@ struct DevReads {
 };
 // batch driver entry points of bk_engine.cpp used by the stream pipeline (all blocking on `s`: the phase loop reads the
 // active counts back between phases)
-int engine_align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known = 0);
+// maxlen_known / minlen_known: the longest and the shortest read where the caller has looked (0: not; the shortest only counts beside the longest)
+int engine_align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known = 0, uint32_t minlen_known = 0);
 void release_swin(bk_ctx *c);
 void drop_swin(bk_ctx *c);
 int engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_hit *d_hits, uint32_t maxlen, const bk_pe_params *pe, hipStream_t s,
                        bk_seg2 *seg2_host = nullptr, bk_seg2 *seg2_dev = nullptr);
 // packed batches: lens16 -> d_lens32, word offsets of the reads -> d_offs (scan), the batch checked (word count, read lengths,
-// exception list); *maxlen = longest read.  Blocking on `s`.
+// exception list); *maxlen = longest read, *minlen = shortest.  Blocking on `s`.
 int engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nreads, uint64_t n_words, const bk_nbase *d_exc, uint64_t n_exc,
-                          uint32_t *d_lens32, uint64_t *d_offs, uint32_t *maxlen, hipStream_t s);
+                          uint32_t *d_lens32, uint64_t *d_offs, uint32_t *maxlen, uint32_t *minlen, hipStream_t s);
 }  // namespace bk
 
 namespace bk {

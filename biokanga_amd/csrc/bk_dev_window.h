@@ -308,7 +308,9 @@ __device__ __forceinline__ bool window_flagged_t(const DevIndex &ix, uint64_t t,
     return (((ix.nflag[g0 >> 3] >> (g0 & 7)) | (ix.nflag[g1 >> 3] >> (g1 & 7))) & 1) != 0;
 }
 
-template <int NW, bool WIDE>
+// ND: the number of 16-base dwords of the read, (len + 15) >> 4, when the caller knows it at compile time (k_wave's length-specialised
+// forms: every read of the launch has it); 0: any length.  Which compare words exist is then a constant, and only the last one is cut
+template <int NW, bool WIDE, int ND = 0>
 __device__ __forceinline__ void eval_window2i(const uint64_t (&r2w)[NW / 2], const uint64_t (&rni)[NW / 4], int len,
                                               const uint64_t *__restrict__ tgt2, const uint64_t *__restrict__ tgt2s, uint64_t t,
                                               IWindow<NW> &w)
@@ -344,14 +346,14 @@ __device__ __forceinline__ void eval_window2i(const uint64_t (&r2w)[NW / 2], con
 #pragma unroll
     for (int k = 0; k < NW / 2; k++) {
         uint64_t y = 0;
-        if (32 * k < len) {
+        if (ND ? 2 * k < ND : 32 * k < len) {
             uint64_t a = odd ? r[k + 1] : r[k];
             uint64_t b = odd ? r[k + 2] : r[k + 1];
             uint64_t win = (a << s) | ((b >> 1) >> (63 - s));
             uint64_t x = r2w[k] ^ win;
             y = (x | (x >> 1)) & 0x5555555555555555ULL;                  // base j of the word: bit 62 - 2j
             const int rem = len - 32 * k;
-            if (rem < 32) y &= ~0ULL << (64 - 2 * rem);
+            if ((ND == 0 || 2 * k + 2 >= ND) && rem < 32) y &= ~0ULL << (64 - 2 * rem);
         }
         if (k & 1) {
             // only even bits are set in y: the shift does not carry between the halves
@@ -400,10 +402,19 @@ __device__ __forceinline__ void swin2i_compare(const uint64_t (&r2w)[NW / 2], co
 // The same compare in 16-base dwords for a window start that is the same in every lane: window dword w is one funnel shift
 // (v_alignbit_b32) of entry dwords D2 + w and D2 + w + 1, whose registers are known at compile time once the scalar unit has branched
 // on D2; five vector instructions per 16 bases and six per 64-base map word instead of the 64-bit shifts, selects and splits above.
-template <int NW, int D2, int E>
-__device__ __forceinline__ void swin2i_compare32(const uint64_t (&r2w)[NW / 2], const uint64_t (&rni)[NW / 4], int len, const uint32_t (&S)[4 * E + 1], unsigned sh,
-                                                 IWindow<NW> &w)
+// ND (see eval_window2i): dword wd exists when wd < ND - a constant, where `16 * wd < len` was a 64-bit lane mask the compiler hoisted
+// and, in k_wave, spilled and read back per dword -, and only dword ND - 1 is cut to the read's length, by lmask (swin2i_last_mask:
+// one scalar per read); every other dword takes the literal.  ND = 0 ignores lmask.
+__device__ __forceinline__ uint32_t swin2i_last_mask(int len, int nd)
 {
+    const int rem = len - 16 * (nd - 1);                                // 1 .. 16 bases in the last dword
+    return rem < 16 ? (~0u << (32 - 2 * rem)) & 0x55555555u : 0x55555555u;
+}
+template <int NW, int D2, int E, int ND = 0>
+__device__ __forceinline__ void swin2i_compare32(const uint64_t (&r2w)[NW / 2], const uint64_t (&rni)[NW / 4], int len, const uint32_t (&S)[4 * E + 1], unsigned sh,
+                                                 IWindow<NW> &w, uint32_t lmask = 0)
+{
+    static_assert(ND >= 0 && ND <= NW, "the read's dwords fit the window");
     static_assert(D2 >= -1 && D2 <= SwGeo<E>::pre / 16, "the window starts inside the entry's lead");
     int mm = 0;
 #pragma unroll
@@ -414,15 +425,19 @@ __device__ __forceinline__ void swin2i_compare32(const uint64_t (&r2w)[NW / 2], 
             const int wd = 4 * i + d;
             y[d] = 0;
             // (dwords the entry does not hold are never asked for: the caller only comes here with the whole window inside the entry)
-            if (D2 + wd + 1 <= 4 * E && 16 * wd < len) {
+            if (D2 + wd + 1 <= 4 * E && (ND ? wd < ND : 16 * wd < len)) {
                 const uint32_t hi = D2 + wd >= 0 ? S[D2 + wd >= 0 ? D2 + wd : 0] : 0u;
                 const uint32_t lo = S[D2 + wd + 1 <= 4 * E ? D2 + wd + 1 : 4 * E];
                 const uint32_t win = __builtin_amdgcn_alignbit(hi, lo, sh);
                 const uint32_t rw = (wd & 1) ? (uint32_t)r2w[wd >> 1] : (uint32_t)(r2w[wd >> 1] >> 32);
                 const uint32_t x = rw ^ win;
-                uint32_t yy = (x | (x >> 1)) & 0x55555555u;                 // base j of the dword: bit 30 - 2j
-                const int rem = len - 16 * wd;
-                if (rem < 16) yy &= ~0u << (32 - 2 * rem);
+                uint32_t yy;                                                // base j of the dword: bit 30 - 2j
+                if (ND) yy = (x | (x >> 1)) & (wd == ND - 1 ? lmask : 0x55555555u);
+                else {
+                    yy = (x | (x >> 1)) & 0x55555555u;
+                    const int rem = len - 16 * wd;
+                    if (rem < 16) yy &= ~0u << (32 - 2 * rem);
+                }
                 y[d] = yy;
             }
         }
@@ -438,22 +453,24 @@ __device__ __forceinline__ void swin2i_compare32(const uint64_t (&r2w)[NW / 2], 
 
 // UNIFORM: bofs is the same for every lane of the wave (one core per round) - the choice of the starting word is then a branch the scalar
 // unit takes instead of ten selects per lane.  E: 16-byte words of an entry (SwGeo); the per-lane form exists for E = 3 only
-template <int NW, int E, int D2, int LAST>
+template <int NW, int E, int D2, int LAST, int ND = 0>
 __device__ __forceinline__ void swin2i_case(const uint64_t (&r2w)[NW / 2], const uint64_t (&rni)[NW / 4], int len, const uint32_t (&S)[4 * E + 1], unsigned sh, int d2,
-                                            IWindow<NW> &w)
+                                            IWindow<NW> &w, uint32_t lmask = 0)
 {
     // (a chain of scalar branches over the starting dwords D2 .. LAST)
     if constexpr (D2 > LAST) return;
     else {
-        if (d2 == D2 || D2 == LAST) swin2i_compare32<NW, D2, E>(r2w, rni, len, S, sh, w);
-        else swin2i_case<NW, E, D2 + 1, LAST>(r2w, rni, len, S, sh, d2, w);
+        if (d2 == D2 || D2 == LAST) swin2i_compare32<NW, D2, E, ND>(r2w, rni, len, S, sh, w, lmask);
+        else swin2i_case<NW, E, D2 + 1, LAST, ND>(r2w, rni, len, S, sh, d2, w, lmask);
     }
 }
 
-template <int NW, bool UNIFORM, int E = 3>
+// ND, lmask: as swin2i_compare32 (the UNIFORM form only)
+template <int NW, bool UNIFORM, int E = 3, int ND = 0>
 __device__ __forceinline__ void eval_swin2i(const uint64_t (&r2w)[NW / 2], const uint64_t (&rni)[NW / 4], int len, const uint4 (&e)[E],
-                                            int bofs, IWindow<NW> &w)
+                                            int bofs, IWindow<NW> &w, uint32_t lmask = 0)
 {
+    static_assert(ND == 0 || UNIFORM, "the length-specialised compare is the one-core-per-round form");
     if (UNIFORM) {
         // the entry as 4 E + 1 16-base dwords in base order (the 64-bit words hold their first base in the top bits)
         uint32_t S[4 * E + 1];
@@ -466,18 +483,18 @@ __device__ __forceinline__ void eval_swin2i(const uint64_t (&r2w)[NW / 2], const
         const int d2 = (ub >> 4) - (rb ? 0 : 1);                  // -1 .. pre / 16 (bofs <= pre)
         if constexpr (E == 3) {
             switch (d2) {
-            case -1: swin2i_compare32<NW, -1, 3>(r2w, rni, len, S, sh, w); break;
-            case 0: swin2i_compare32<NW, 0, 3>(r2w, rni, len, S, sh, w); break;
-            case 1: swin2i_compare32<NW, 1, 3>(r2w, rni, len, S, sh, w); break;
-            case 2: swin2i_compare32<NW, 2, 3>(r2w, rni, len, S, sh, w); break;
-            case 3: swin2i_compare32<NW, 3, 3>(r2w, rni, len, S, sh, w); break;
-            case 4: swin2i_compare32<NW, 4, 3>(r2w, rni, len, S, sh, w); break;
-            default: swin2i_compare32<NW, 5, 3>(r2w, rni, len, S, sh, w); break;
+            case -1: swin2i_compare32<NW, -1, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            case 0: swin2i_compare32<NW, 0, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            case 1: swin2i_compare32<NW, 1, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            case 2: swin2i_compare32<NW, 2, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            case 3: swin2i_compare32<NW, 3, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            case 4: swin2i_compare32<NW, 4, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
+            default: swin2i_compare32<NW, 5, 3, ND>(r2w, rni, len, S, sh, w, lmask); break;
             }
         } else if (d2 < 4)
-            swin2i_case<NW, E, -1, 3>(r2w, rni, len, S, sh, d2, w);
+            swin2i_case<NW, E, -1, 3, ND>(r2w, rni, len, S, sh, d2, w, lmask);
         else
-            swin2i_case<NW, E, 4, SwGeo<E>::pre / 16>(r2w, rni, len, S, sh, d2, w);
+            swin2i_case<NW, E, 4, SwGeo<E>::pre / 16, ND>(r2w, rni, len, S, sh, d2, w, lmask);
         return;
     }
     if constexpr (E == 3) {

@@ -7,6 +7,7 @@
 // here; a chunk's temporaries are local DevBufs, so an early return frees them.  Nothing here frees device memory by hand.
 #include "bk_engine_int.h"
 #include "bk_plan_table.h"
+#include "bk_wave_form.h"
 
 namespace bk {
 int size_heavy_scratch(bk_ctx *c)
@@ -376,7 +377,9 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
     return lc.finish();
 }
 
-int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
+// minlen: the shortest read of the call when somebody has looked (0: not known) - with maxlen it tells whether every read has the same
+// number of 16-base dwords, which the wave kernel's length-specialised forms rely on
+int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, uint32_t minlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
 {
     uint32_t *sm = c->fixed.small.get(), *hm = c->h_small;
     HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
@@ -569,7 +572,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                 n_sort = 0;
             if (!no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe
             launch_wave(c->ix, c->cfg, b, c->hs, d_wave, wsorted, n_sort, ctl_p + 3, n_wave, phase, ctl_p + 5, d_act[cur ^ 1], ctl_n + 0, ctl_n + 1,
-                        nw16, c->wave_waves, s);
+                        nw16, c->wave_waves, c->wave_len_spec ? uniform_dwords(minlen, maxlen) : 0, s);
             HIP_TRY(hipGetLastError());
             tm.end(Span::Heavy, e3, s);
         }
@@ -689,7 +692,7 @@ int take_phase_history(bk_ctx *c, bool wait)
 // enqueue_only: everything is launched on `s` and the call returns without waiting for any of it (bk_align_batch_device_async): the
 // caller has named the longest read, the scratch is in place (bk_ctx_reserve) and the configuration is one whose phase loop reads
 // nothing back - else BK_ERR_PARAMS, before anything is launched.
-int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known, bool enqueue_only)
+int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known, bool enqueue_only, uint32_t minlen_known)
 {
     grow_tick(c, nreads);                      // (BK_CTX_GROW_IMAGE: the long-run tables are started, or taken in, between batches)
     const uint32_t *d_lens = in.lens;
@@ -711,13 +714,16 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     c->loci_trims.clear();
     c->seg2.clear();
     // longest read of the call -> row width of the packed reads and the kernel family used (the pipeline knows it already)
-    uint32_t maxlen = maxlen_known;
+    // .. and the shortest beside it, where the caller has looked or this call looks anyway: 0, not known, for a call that only enqueues
+    uint32_t maxlen = maxlen_known, minlen = maxlen_known ? minlen_known : 0;
     if (!maxlen) {
         HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
         launch_max_len(d_lens, nreads, c->fixed.small.get() + 5, s);
+        launch_min_len(d_lens, nreads, c->fixed.small.get() + 6, s);
         HIP_TRY(hipMemcpyAsync(c->h_small, c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         maxlen = c->h_small[5];
+        minlen = min_len_of(c->h_small[6]);
     }
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
     c->last_maxlen = maxlen;
@@ -747,7 +753,7 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     }
     for (uint32_t done = 0; done < nreads;) {
         uint32_t n = std::min(chunk, nreads - done);
-        int rc = align_chunk(c, in, done, n, maxlen, d_out + done, s, tm);
+        int rc = align_chunk(c, in, done, n, maxlen, minlen, d_out + done, s, tm);
         if (rc) return rc;
         done += n;
     }
@@ -780,9 +786,9 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
 
 using namespace bk;
 
-int bk::engine_align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known)
+int bk::engine_align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, hipStream_t s, uint32_t maxlen_known, uint32_t minlen_known)
 {
-    return align_device(c, in, nreads, d_out, s, maxlen_known);
+    return align_device(c, in, nreads, d_out, s, maxlen_known, false, minlen_known);
 }
 
 namespace {
@@ -792,7 +798,7 @@ struct CastU64 {
 }
 
 int bk::engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nreads, uint64_t n_words, const bk_nbase *d_exc, uint64_t n_exc,
-                              uint32_t *d_lens32, uint64_t *d_offs, uint32_t *maxlen, hipStream_t s)
+                              uint32_t *d_lens32, uint64_t *d_offs, uint32_t *maxlen, uint32_t *minlen, hipStream_t s)
 {
     // words per read -> exclusive scan in place = first word of every read
     launch_widen_lens(d_lens16, nreads, d_lens32, (unsigned long long *)d_offs, s);
@@ -805,16 +811,18 @@ int bk::engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nrea
     }
     size_t tb = c->buf.scan_tmp.cap();
     HIP_TRY(bk::prim::exclusive_sum(c->buf.scan_tmp.get(), tb, (unsigned long long *)d_offs, (unsigned long long *)d_offs, (size_t)nreads, s));
-    // [0] max over reads of (first word + words) = the batch's word count, [1] longest read; exceptions in range and ascending
+    // [0] max over reads of (first word + words) = the batch's word count, [1] longest read; exceptions in range and ascending; [3] shortest read (launch_min_len's word)
     HIP_TRY(hipMemsetAsync(c->fixed.ctr_aux.get(), 0, 32, s));
     launch_packed_extent(d_offs, d_lens32, nreads, c->fixed.ctr_aux.get(), s);
     launch_check_exc(d_exc, n_exc, d_lens32, nreads, reinterpret_cast<uint32_t *>(c->fixed.ctr_aux.get() + 2), s);
+    launch_min_len(d_lens32, nreads, reinterpret_cast<uint32_t *>(c->fixed.ctr_aux.get() + 3), s);
     HIP_TRY(hipGetLastError());
-    unsigned long long h[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, c->fixed.ctr_aux.get(), 24, hipMemcpyDeviceToHost, s));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, c->fixed.ctr_aux.get(), 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (h[0] != n_words || h[1] > (unsigned long long)kMaxReadLenAbs || (uint32_t)h[2] != 0) return BK_ERR_PARAMS;
     *maxlen = (uint32_t)h[1];
+    *minlen = min_len_of((uint32_t)h[3]);
     return BK_OK;
 }
 
@@ -1076,8 +1084,8 @@ int bk_align_batch_packed(bk_ctx *c, const uint32_t *words, uint64_t n_words, co
     if (n_words) HIP_TRY(hipMemcpyAsync(m.in_words.get(), words, n_words * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(m.in_lens16.get(), lens, (size_t)nreads * 2, hipMemcpyHostToDevice, s));
     if (n_exc) HIP_TRY(hipMemcpyAsync(m.in_exc.get(), exc, n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s));
-    uint32_t maxlen = 0;
-    rc = engine_prepare_packed(c, m.in_lens16.get(), nreads, n_words, m.in_exc.get(), n_exc, m.in_lens.get(), m.in_offs.get(), &maxlen, s);
+    uint32_t maxlen = 0, minlen = 0;
+    rc = engine_prepare_packed(c, m.in_lens16.get(), nreads, n_words, m.in_exc.get(), n_exc, m.in_lens.get(), m.in_offs.get(), &maxlen, &minlen, s);
     if (rc) return rc;
     DevReads in;
     in.offs = m.in_offs.get(); in.lens = m.in_lens.get(); in.words = m.in_words.get(); in.exc = m.in_exc.get(); in.n_exc = n_exc;

@@ -629,6 +629,31 @@ void launch_max_len(const uint32_t *lens, uint32_t n, uint32_t *out, hipStream_t
     if (n) hipLaunchKernelGGL(k_max_len, dim3(blocks), dim3(256), 0, s, lens, n, out);
 }
 
+// the shortest read, kept as the maximum of the lengths' complements: *out = ~min once every block has added its part to a word the caller
+// zeroed (a zeroed word stands for "no read seen"; no length is 2^32 - 1).  One pass over the lengths, as k_max_len.
+__global__ void __launch_bounds__(256) k_min_len(const uint32_t *__restrict__ lens, uint32_t n, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_max;
+    if (threadIdx.x == 0) s_max = 0;
+    __syncthreads();
+    uint32_t v = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t w = ~lens[i];
+        v = w > v ? w : v;
+    }
+    for (int off = 32; off > 0; off >>= 1) { uint32_t w = __shfl_down(v, off); v = w > v ? w : v; }
+    if ((threadIdx.x & 63) == 0 && v) atomicMax(&s_max, v);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max) atomicMax(out, s_max);
+}
+
+void launch_min_len(const uint32_t *lens, uint32_t n, uint32_t *out, hipStream_t s)
+{
+    uint32_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (n) hipLaunchKernelGGL(k_min_len, dim3(blocks), dim3(256), 0, s, lens, n, out);
+}
+
 // the stripes of up to three lists -> their dense forms (appended behind total[i] entries; the counts and the maximum follow)
 void launch_compact(const StripeSet &set, uint32_t *const *dense, uint32_t *const *total, int n, uint32_t *max_out, hipStream_t s)
 {

@@ -24,6 +24,7 @@
 #include <thread>
 
 #include "bk_ctx_int.h"
+#include "bk_wave_form.h"
 #include "bk_wait.h"
 #include "bk_env.h"
 
@@ -34,25 +35,32 @@ struct CastU64 {
 };
 
 // max over reads of offs[i] + lens[i] (reads must lie inside the uploaded bases) and of lens[i].  Checked per element without a
-// sum that can wrap: a read that starts beyond `nbases` or runs past it reports an end of ~0.
+// sum that can wrap: a read that starts beyond `nbases` or runs past it reports an end of ~0.  out[2]: the shortest read, as the
+// maximum of the 32-bit complements of the lengths (bk::min_len_of) - the same pass, no trip of its own.
 __global__ void __launch_bounds__(256) k_extent(const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens, uint32_t n,
                                                 unsigned long long nbases, unsigned long long *__restrict__ out)
 {
     unsigned long long e = 0, l = 0;
+    uint32_t c = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long len = lens[i], o = offs[i];
         const unsigned long long end = (o > nbases || len > nbases - o) ? ~0ULL : o + len;
         e = end > e ? end : e;
         l = len > l ? len : l;
+        const uint32_t nl = ~(uint32_t)len;
+        c = nl > c ? nl : c;
     }
     for (int off = 32; off > 0; off >>= 1) {
         unsigned long long e2 = __shfl_down(e, off), l2 = __shfl_down(l, off);
+        const uint32_t c2 = __shfl_down(c, off);
         e = e2 > e ? e2 : e;
         l = l2 > l ? l2 : l;
+        c = c2 > c ? c2 : c;
     }
     if ((threadIdx.x & 63) == 0) {
         if (e) atomicMax(out + 0, e);
         if (l) atomicMax(out + 1, l);
+        if (c) atomicMax(out + 2, (unsigned long long)c);
     }
 }
 
@@ -120,7 +128,7 @@ struct bk_stream {
     hipStream_t s_up = nullptr, s_al = nullptr, s_dn = nullptr;
     void *d_scan_tmp = nullptr;
     size_t scan_tmp_bytes = 0;
-    unsigned long long *d_ext = nullptr, *h_ext = nullptr;     // [0] max read end [1] max read length
+    unsigned long long *d_ext = nullptr, *h_ext = nullptr;     // [0] max read end [1] max read length [2] ~(min read length), 32 bits
     std::thread t_up, t_al, t_dn;
     hipEvent_t ev_w_al = nullptr, ev_w_dn = nullptr;       // what the aligner and the download thread sleep on (bk_wait.h)
     std::mutex mu;
@@ -223,13 +231,13 @@ struct bk_stream {
             }
             if (j->rc == BK_OK && j->n && j->lens16) {
                 hipError_t e = hipStreamWaitEvent(s_al, sl.ev_up, 0);
-                uint32_t maxlen = 0;
-                int rc = e == hipSuccess ? bk::engine_prepare_packed(ctx, sl.d_lens16, j->n, j->n_words, sl.d_exc, j->n_exc, sl.d_lens, sl.d_offs, &maxlen, s_al)
+                uint32_t maxlen = 0, minlen = 0;
+                int rc = e == hipSuccess ? bk::engine_prepare_packed(ctx, sl.d_lens16, j->n, j->n_words, sl.d_exc, j->n_exc, sl.d_lens, sl.d_offs, &maxlen, &minlen, s_al)
                                          : rc_of(e);
                 t_prep = now_s();
                 bk::DevReads in;
                 in.offs = sl.d_offs; in.lens = sl.d_lens; in.words = reinterpret_cast<const uint32_t *>(sl.d_bases); in.exc = sl.d_exc; in.n_exc = j->n_exc;
-                if (rc == BK_OK) rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen);
+                if (rc == BK_OK) rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen, minlen);
                 if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out, maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
                 if (rc) fail(j, rc);
                 else if (list_modes) {
@@ -249,22 +257,22 @@ struct bk_stream {
                     rocprim::transform_iterator<const uint32_t *, CastU64, unsigned long long> in(sl.d_lens, CastU64());
                     e = bk::prim::exclusive_sum(d_scan_tmp, tb, in, (unsigned long long *)sl.d_offs, (size_t)j->n, s_al);
                 }
-                if (e == hipSuccess) e = hipMemsetAsync(d_ext, 0, 16, s_al);
+                if (e == hipSuccess) e = hipMemsetAsync(d_ext, 0, 24, s_al);
                 if (e == hipSuccess) {
                     unsigned blocks = (j->n + 255) / 256;
                     if (blocks > 2048) blocks = 2048;
                     hipLaunchKernelGGL(k_extent, dim3(blocks), dim3(256), 0, s_al, sl.d_offs, sl.d_lens, j->n, (unsigned long long)j->nbases, d_ext);
                     e = hipGetLastError();
                 }
-                if (e == hipSuccess) e = hipMemcpyAsync(h_ext, d_ext, 16, hipMemcpyDeviceToHost, s_al);
+                if (e == hipSuccess) e = hipMemcpyAsync(h_ext, d_ext, 24, hipMemcpyDeviceToHost, s_al);
                 if (e == hipSuccess) e = bk::wait_stream(s_al, ev_w_al);
                 if (e != hipSuccess) fail(j, rc_of(e));
                 else if (h_ext[0] > j->nbases || h_ext[1] > (unsigned long long)bk::kMaxReadLenAbs) fail(j, BK_ERR_PARAMS);
-                const uint32_t maxlen = (uint32_t)h_ext[1];
+                const uint32_t maxlen = (uint32_t)h_ext[1], minlen = bk::min_len_of((uint32_t)h_ext[2]);
                 if (j->rc == BK_OK) {
                     bk::DevReads in;
                     in.bases = sl.d_bases; in.offs = sl.d_offs; in.lens = sl.d_lens;
-                    int rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen);
+                    int rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen, minlen);
                     if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out, maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
                     if (rc) fail(j, rc);
                     else if (list_modes) {
@@ -456,8 +464,8 @@ static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads,
         e = bk::prim::exclusive_sum(nullptr, s->scan_tmp_bytes, in, (unsigned long long *)nullptr, (size_t)max_batch_reads, s->s_al);
     }
     if (e == hipSuccess) e = bk::dev_malloc(&s->d_scan_tmp, s->scan_tmp_bytes ? s->scan_tmp_bytes : 16);
-    if (e == hipSuccess) e = bk::dev_malloc(&s->d_ext, 16);
-    if (e == hipSuccess) e = hipHostMalloc(&s->h_ext, 16, hipHostMallocDefault);
+    if (e == hipSuccess) e = bk::dev_malloc(&s->d_ext, 24);
+    if (e == hipSuccess) e = hipHostMalloc(&s->h_ext, 24, hipHostMallocDefault);
     if (e != hipSuccess) {
         fprintf(stderr, "biokanga_amd: bk_stream_create: %s\n", hipGetErrorString(e));
         s->next_ticket = 1;

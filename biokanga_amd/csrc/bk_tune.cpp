@@ -148,6 +148,11 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->wave_waves = (uint32_t)value;
         return old;
     }
+    if (n == "wave_len_spec") {            // host only: which form of the wave kernel is launched, never what it computes
+        int64_t old = c->wave_len_spec;
+        c->wave_len_spec = value ? 1 : 0;
+        return old;
+    }
     if (n == "async_phases") {             // 0: the phase loop reads its counts back between launches (exact launch sizes), as every other configuration does
         int64_t old = c->async_phases;
         c->async_phases = value ? 1 : 0;

@@ -1,6 +1,7 @@
 // bk_wave.hip - LocateCoreMultiples for repeat reads (gfx950): one wave per call, 64 candidates of a core interval per round.
 #include "bk_dev_window.h"
 #include "bk_dev_sets.h"
+#include "bk_wave_form.h"
 
 namespace bk {
 
@@ -72,7 +73,8 @@ static __device__ unsigned long long g_wprof[64 * 8];
 #elif defined(BK_PROF) && BK_PROF == 4
 // where a ROUND's cycles go (lane 0 of every wave, every mark behind a wait for what is in flight): 0 the suffix array elements in hand,
 // 1 windows fetched and compared, 2 the look-up in the set of seen keys, 3 the keys' insertion, 4 the round's bookkeeping; 5 = rounds,
-// 6 = rounds of a strand pass that lives in the HBM table, 7 = cycles outside the rounds
+// 6 = rounds of a strand pass that lives in the HBM table (hash-set forms) or rounds that took the lean path (the other forms),
+// 7 = cycles outside the rounds
 static __device__ unsigned long long g_wprof[64 * 8];
 #define WPROF_DECL long long wp_last = clock64(); unsigned long long wp[8] = {0, 0, 0, 0, 0, 0, 0, 0}
 #define WPROF(k) do { const long long now_ = clock64(); wp[7] += (unsigned long long)(now_ - wp_last); wp_last = now_; } while (0)
@@ -98,9 +100,18 @@ struct WaveArgs {
     int phase;
     uint32_t *cursor, *next_act, *next_cnt, *cmax_next;
 };
-template <int NW, bool WIDE, bool HASH, bool SW, bool GROUP>
+// BK_WAVE_LEAN: a round of a long walk that accepts nothing and is away from every iteration rule skips the per-lane bookkeeping (see the
+// branch behind `newmask`); 0 builds the kernel without it (tools/build_variant.sh, for the A/B)
+#ifndef BK_WAVE_LEAN
+#define BK_WAVE_LEAN 1
+#endif
+// ND: every read of the launch has this many 16-base dwords, (len + 15) >> 4 == ND - the host launches such a form only for a batch whose
+// shortest and longest read agree in it (wave_len_nd, bk_wave_form.h); 0: any lengths.  The window array compare then knows at compile
+// time which dwords exist and which one is cut to the read's length (swin2i_compare32).
+template <int NW, bool WIDE, bool HASH, bool SW, bool GROUP, int ND = 0>
 __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_BLOCKS) : ((NW == 16 && !HASH) ? BK_WAVE16_BLOCKS : ((NW == 16 && SW) ? 4 : 2))) k_wave(WaveArgs wa)
 {
+    static_assert(ND == 0 || (SW && !HASH && !GROUP), "length-specialised forms: one core per round, windows from the array, no hash set");
     const DevIndex &ix = wa.ix;
     const DevAlignCfg &cfg = wa.cfg;
     const DevBatch &b = wa.b;
@@ -214,6 +225,7 @@ __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_B
         grab_at++;
         const int len = (int)(meta & kReadLenMask);
         const bool has_n = (meta & kReadHasN) != 0;
+        const uint32_t nd_mask = ND ? swin2i_last_mask(len, ND) : 0u;       // ND: the one dword of the compare that is cut to the read's length
         // the plan of the read's length, the core offsets and the cores' masks only change with the length: a batch of equal-length reads
         // computes them once per wave (they live in registers and in the wave's LDS words), not once per read
         if (len != geo_len) {
@@ -330,7 +342,7 @@ __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_B
                     uint64_t nm = 0;
 #pragma unroll
                     for (int k = 0; k < 4; k++)
-                        if (16 * (4 * q + k) < len) nm |= (uint64_t)flags_to_bits16((uniform64(rp[4 * q + k]) >> 2) & 0x1111111111111111ULL) << (16 * k);
+                        if (ND ? 4 * q + k < ND : 16 * (4 * q + k) < len) nm |= (uint64_t)flags_to_bits16((uniform64(rp[4 * q + k]) >> 2) & 0x1111111111111111ULL) << (16 * k);
                     rni[q] = nm ? uniform64(bits_to_imap(nm)) : 0ULL;
                 }
             }
@@ -477,10 +489,10 @@ __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_B
                             if (SW && sw_now) {
                                 if constexpr (SW) {
                                     if (GROUP && grouped) eval_swin2i<NW, false, E>(r2w, rni, len, ev, SwGeo<E>::pre - lofs, w);
-                                    else eval_swin2i<NW, true, E>(r2w, rni, len, ev, SwGeo<E>::pre - lofs, w);
+                                    else eval_swin2i<NW, true, E, ND>(r2w, rni, len, ev, SwGeo<E>::pre - lofs, w, nd_mask);
                                 }
                             } else
-                                eval_window2i<NW, WIDE>(r2w, rni, len, ix.tgt2, ix.tgt2s, t, w);
+                                eval_window2i<NW, WIDE, ND>(r2w, rni, len, ix.tgt2, ix.tgt2s, t, w);
                             if (flg) {
                                 Window<NW> w4;
                                 eval_window_rare<NW>(row4, len, ix.tgt4, t, w4);
@@ -520,7 +532,34 @@ __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_B
                     if (HASH && spilled) RPROF_N(6);
                     if (kDiag) { n_fetch += __popcll(__ballot(active && loci >= (uint64_t)ofs)); n_dup += __popcll(__ballot(dup)); }
                     const uint64_t newmask = __ballot(isnew);
-                    const uint32_t pre = (uint32_t)__popcll(newmask & lt_mask);
+#if BK_WAVE_LEAN && !defined(BK_CAND_HIST)
+                    // The lean round.  Most rounds belong to long walks (intervals of hundreds to thousands of suffixes) in which nothing is
+                    // within the phase's mismatch budget and every iteration rule is far away; the bookkeeping below then works out, per
+                    // lane, that nothing happens.  With nnew new candidates in the round, a lane's iter_before = iter + (new lanes before
+                    // it) lies in iter .. iter + nnew (the upper end in a lane behind the last new one), nodes_before likewise.  So:
+                    //   iter + nnew < MaxIter and nodes + nnew < kNodeCap    =>  no lane has `stop`: cutoff stays n;
+                    //   copies_checked, or iter + nnew < 100                 =>  no lane has iter_before == 100: the copy check does not
+                    //     fire (strictly below: a lane that is not new, behind the hundredth new one, still sees 100) and cutoff stays n;
+                    //   cutoff == n                                          =>  proc == isnew in every lane;
+                    //   no new lane with w.mm <= mm && w.mm < nxt            =>  cm == 127 and acc false everywhere: zmask == 0, so
+                    //     keep == ~0 and no early exit; procmask == newmask; accmask == 0, so low_mm, low_inst, nxt and the hit stay.
+                    // What is left of the round is nproc == nnew added to the three counts.  cutoff == n < j0 + 64 only in the interval's
+                    // last round, where the full path sets walked = n - the value it already holds - and leaves a loop that ends here too.
+                    // (Shared rounds and the hash-set forms, whose keys are inserted behind this point, take the full path.)
+                    if (!HASH && !(GROUP && grouped)) {
+                        const uint32_t nnew = (uint32_t)__popcll(newmask);
+                        if (__ballot(isnew && w.mm <= mm && w.mm < nxt) == 0 && (!cfg.max_iter || iter + nnew < (uint32_t)cfg.max_iter) && nodes + nnew < kNodeCap &&
+                            (copies_checked || iter + nnew < 100u)) {
+                            iter += nnew;
+                            nodes += nnew;
+                            n_cand += nnew;
+                            RPROF(4);
+                            if (!HASH) RPROF_N(6);
+                            continue;
+                        }
+                    }
+#endif
+                    const uint32_t pre =(uint32_t)__popcll(newmask & lt_mask);
                     const uint32_t iter_before = iter + pre;
                     const uint32_t nodes_before = nodes + pre;
                     bool stop = active && !(GROUP && grouped) && ((cfg.max_iter && iter_before >= (uint32_t)cfg.max_iter) || nodes_before >= kNodeCap);
@@ -709,10 +748,12 @@ void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, cons
 }
 
 // list: the reads k_flat handed on (*p_n_list of them, at most n_bound); sorted / n_sorted: the sorted copy of the first n_sorted (or null)
+// len_dwords: (len + 15) >> 4 of EVERY read of the batch when they all agree in it, else 0 (uniform_dwords, bk_wave_form.h) - the
+// 8-word window-array form is then launched in its length-specialised form
 void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const uint32_t *list, const uint32_t *sorted,
                  uint32_t n_sorted, const uint32_t *p_n_list, uint32_t n_bound,
                  int phase, uint32_t *cursor, uint32_t *next_act, uint32_t *next_cnt, uint32_t *cmax_next, int nw, uint32_t max_waves,
-                 hipStream_t s)
+                 int len_dwords, hipStream_t s)
 {
     if (!n_bound) return;
     const bool wide = ix.sa_hi != nullptr, hash = ix.isa == nullptr;
@@ -732,7 +773,21 @@ void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, 
 #ifdef BK_WAVE8_GROUP
         else if (sw) BK_WAVE(8, false, false, true, true);
 #else
-        else if (sw) BK_WAVE(8, false, false, true, false);
+        else if (sw) {
+#define BK_WAVE_ND(D) hipLaunchKernelGGL((k_wave<8, false, false, true, false, D>), dim3(blocks), dim3(256), 0, s, wa)
+            switch (wave_form_nd(len_dwords, nw, wide, hash, sw)) {
+            case 1: BK_WAVE_ND(1); break;
+            case 2: BK_WAVE_ND(2); break;
+            case 3: BK_WAVE_ND(3); break;
+            case 4: BK_WAVE_ND(4); break;
+            case 5: BK_WAVE_ND(5); break;
+            case 6: BK_WAVE_ND(6); break;
+            case 7: BK_WAVE_ND(7); break;
+            case 8: BK_WAVE_ND(8); break;
+            default: BK_WAVE_ND(0); break;
+            }
+#undef BK_WAVE_ND
+        }
 #endif
         else BK_WAVE(8, false, false, false, false);
     } else if (nw <= 16) {

@@ -205,6 +205,8 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "use_iv32" (phase 0 hands the interval of a read's first k + 16 bases to the later phases)   "lazy_search" (small buckets handed on unverified)
  *   "iv_poison" (test hook, 0: the interval records a phase can use are filled with ones in front of its search - nothing clears them
  *   otherwise, the search stores the slot of every core a read has -, so that a slot read without having been written in that phase shows)
+ *   "wave_len_spec" (1, the default: a batch whose reads all have the same number of 16-base dwords gets the wave kernel's form compiled
+ *   for that count; 0: the generic form always.  Host only: which kernel is launched, no kernel argument)
  *   "use_ktab2" (k-mer table entries of two words, 17 GB more at k = 16: 1, the default - a bucket of one suffix carries its second-level key and is
  *   settled by the line that names it; 2 - it carries the suffix array element and the search hands the suffix on for the extension to check:
  *   no trip to the suffix array for it, but every bucket whose key the search would have turned down is a candidate - slower, round 6)

@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B of library variants on the GPU box (tools/build_variant.sh makes them): the kernel-only C2 steps of bench.py, once per variant, device
 # milliseconds per kernel family side by side.   tools/ab_variants.sh <out dir> <variant> [<variant> ..]     ("main" = the regular library)
+# The wave kernel's two parts: `tools/build_variant.sh nolean "-DBK_WAVE_LEAN=0" bk_wave.hip`, then "main" against "nolean" for the lean round;
+# "main" with AB_ARGS="--tune wave_len_spec=0" against "main" for the length-specialised forms.
 set -u
 O=$1; shift
 mkdir -p $O
