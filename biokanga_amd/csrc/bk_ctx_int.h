@@ -97,6 +97,8 @@ struct bk_ctx {
     int sort_lists = 7;      // bit 0: search work list grouped by index position; bit 1: wave list sorted, by index position or (bit 2) longest read first
     bool sort_lists_set = false;   // .. as the caller's knob left it; else bit 0 follows the index: off where it has third-level keys (tables_end)
     int sort_shift = 0;      // keys = suffix array index >> sort_shift (fits 32 bits)
+    int search_split = 1;    // pass B in two launches: the key levels, then - dense - the items they do not settle (k_search_deep)
+    bool search_split_set = false; // .. as the caller's knob left it; else on where the work list is not grouped (bit 0 of sort_lists clear), off where it is
     int use_k2 = 1;
     int use_k3 = bk::kMoreKeys;  // key arrays behind the second-level keys (DevIndex::kx): at most this many, where the HBM has the room
     // BK_CTX_GROW_IMAGE: the tables that only pay over long runs (key arrays behind the second-level keys, k-mer table entries with their

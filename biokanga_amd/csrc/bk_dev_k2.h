@@ -86,7 +86,9 @@ __device__ __forceinline__ uint32_t k2_make(const uint64_t *__restrict__ tgt4, u
 // aligned lines are loaded - four 16-byte requests, no dependent trips inside a line - and the second line of a range that straddles
 // two is only fetched when the first did not end both counts.
 #ifdef BK_DIAG_B
-#define BK_K2_LINE(ctr) (ctr)++
+// (a line for the lane; above bit 20, once per wave and load - by the first of the lanes that load -, the wave's count of such loads:
+// what bk_search.hip's lane-use figures are made of)
+#define BK_K2_LINE(ctr) do { const unsigned long long m_ = __ballot(1); (ctr) += 1 + ((int)(threadIdx.x & 63) == __ffsll((long long)m_) - 1 ? 1ULL << 20 : 0ULL); } while (0)
 #else
 #define BK_K2_LINE(ctr) (void)0
 #endif

@@ -173,7 +173,8 @@ struct PhaseCtl {
     uint32_t n_wave;            // reads k_flat handed to the wave kernel
     uint32_t n_heavy;           // .. and to the general kernel
     uint32_t wave_cursor, heavy_cursor;
-    uint32_t pad[9];
+    uint32_t n_deep;            // work items pass B handed to k_search_deep ("search_split")
+    uint32_t pad[8];
 };
 constexpr int kMaxPhases = 72;          // AlignReads runs at most MaxTotMM + 2 <= 65 LocateCoreMultiples calls (cMaxTotAllowedSubs 63)
 

@@ -418,7 +418,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     // sizes their launches exactly.
     PhaseCtl *ctl = c->fixed.ctl.get();
     HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PhaseCtl) * (kMaxPhases + 2), s));
-    auto P = [&](int ph) { return reinterpret_cast<uint32_t *>(ctl + ph); };      // words of ctl[ph]: [0] n_act [1] cmax [2] n_slist [3] n_wave [4] n_heavy [5] wave cursor [6] heavy cursor
+    auto P = [&](int ph) { return reinterpret_cast<uint32_t *>(ctl + ph); };      // words of ctl[ph]: [0] n_act [1] cmax [2] n_slist [3] n_wave [4] n_heavy [5] wave cursor [6] heavy cursor [7] n_deep
     // bounds of a read of up to maxlen bases: phases, cores per strand in each
     int max_phases = 0, cmax_bound[kMaxPhases + 1] = {0};
     bool cores_fit = true;
@@ -517,7 +517,12 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                     n_sort = 0;
                 if (n_slist_bound) {
                     hipEvent_t eb = tm.begin(s);
-                    launch_search_b(c->ix, c->cfg, b, phase, lazy, d_slist, sorted, n_sort, ctl_p + 2, n_slist_bound, s);
+                    // "search_split": the items the key levels do not settle are finished by a second, dense launch.  Their list takes
+                    // pass A's place - the work list and its stripes are free once k_search_b has read them - and its length a spare
+                    // word of the phase's line, zero since the chunk began; both launches are pass B's time
+                    const bool split = bk::search_split_on(c);
+                    launch_search_b(c->ix, c->cfg, b, phase, lazy, d_slist, sorted, n_sort, ctl_p + 2, n_slist_bound, split ? d_slist : nullptr,
+                                    split ? ctl_p + 7 : nullptr, m.slist_stage.get(), d_stripe_cnt, s);
                     tm.end(Span::SearchB, eb, s);
                 }
             } else

@@ -75,7 +75,8 @@ void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
                      int phase, int cmax, int nstr, int lazy, uint32_t *list, uint32_t *list_cnt, uint32_t *stage, uint32_t *stripe_cnt,
                      hipStream_t s);
 void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int phase, int lazy, const uint32_t *list, const uint32_t *sorted,
-                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, hipStream_t s);
+                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, uint32_t *deep_list, uint32_t *deep_cnt, uint32_t *stage,
+                     uint32_t *stripe_cnt, hipStream_t s);
 void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s);
 void launch_pe(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int pe_mode, int min_len, int max_len, int pair_strand,
                bk_hit *hits, uint32_t n_pairs, uint32_t *orphans, uint32_t *counters, uint32_t *h_count, bk_seg2 *seg2, int min_chim,
@@ -135,6 +136,10 @@ inline uint32_t iv_cores_for(const bk_ctx *c, uint32_t maxlen)
     const uint32_t ms = std::max(1u, ((uint32_t)c->cfg.slides_per100 * maxlen + 99) / 100);
     return std::min<uint32_t>(ms, kMaxCoresFast);
 }
+
+// whether pass B runs as two launches ("search_split"): the knob when somebody set it, else wherever pass B's work list is not grouped - on
+// a grouped list a repeat family's items lie side by side already
+inline bool search_split_on(const bk_ctx *c) { return c->search_split_set ? c->search_split != 0 : !(c->sort_lists & 1); }
 
 // 64-bit words of a read's 2 bit/base row in the register-window kernel family that takes reads of up to maxlen bases
 inline uint32_t rd2w_for(uint32_t maxlen)

@@ -2,6 +2,7 @@
 //   k_search          one pass over suffix array + target (indexes without second-level keys)
 //   k_search_a_ilp    pass A: k-mer table + small buckets out of the second-level keys
 //   k_search_b        pass B: bisection of the big buckets, work list grouped by bucket
+//   k_search_deep     pass B's tails in a launch of their own ("search_split"): suffix array + target behind the key levels, full searches
 #include <algorithm>
 
 #include "bk_dev_k2.h"
@@ -281,10 +282,31 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
 #endif
 }
 
-template <bool WIDE>
+// -DBK_DIAG_B builds also count how full pass B's waves are where they load: at every load site the lanes that issue the load add one
+// each to `used`, and one of them adds 64 for the wave to `offered` (a line's worth of lanes was there to be used).  Summed per phase in
+// g_diag_b (phases 0 .. 7: word 2p used, word 2p + 1 offered), read with bk_debug_prof() by tools/search_b_diag.py.
+#ifdef BK_DIAG_B
+static __device__ unsigned long long g_diag_b[64 * 16];
+#define BK_B_TRIP() do { const unsigned long long m_ = __ballot(1); d_used += 1; if ((int)(threadIdx.x & 63) == __ffsll((long long)m_) - 1) d_off += 64; } while (0)
+// (k2_count_range's line counter carries the wave's share above bit 20: bk_dev_k2.h, BK_K2_LINE)
+#define BK_B_LINES(l) do { d_used += (l) & 0xFFFFFULL; d_off += 64 * ((l) >> 20); (l) &= 0xFFFFFULL; } while (0)
+#define BK_B_FLUSH(phase) do { if ((phase) < 8) { if (d_used) atomicAdd(&g_diag_b[(blockIdx.x & 63) * 16 + 2 * (phase)], d_used); \
+                                                   if (d_off) atomicAdd(&g_diag_b[(blockIdx.x & 63) * 16 + 2 * (phase) + 1], d_off); } } while (0)
+#else
+#define BK_B_TRIP() (void)0
+#define BK_B_LINES(l) (void)0
+#define BK_B_FLUSH(phase) (void)0
+#endif
+
+// Pass B.  SPLIT = false: a lane carries its work item from the second-level keys to the final record.  SPLIT = true ("search_split"): the
+// lane runs the key levels only; an item they do not settle - and every kKindFull item - is left in its slot as a continuation (the
+// narrowed interval with kind kKindDeep; the kKindFull record as it is) and the slot is appended to the striped list `deep`, which
+// k_search_deep finishes in a launch of its own, dense in lanes that all have the same kind of work: the bisection over suffix array and
+// target is ten times the dependent trips of an item that ends behind the second-level keys, and one such item keeps its whole wave.
+template <bool WIDE, bool SPLIT>
 __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, DevBatch b, int phase, int lazy,
                                                   const uint32_t *__restrict__ list, const uint32_t *__restrict__ sorted, uint32_t n_sorted,
-                                                  const uint32_t *__restrict__ p_n_list, SlotGeo sg)
+                                                  const uint32_t *__restrict__ p_n_list, SlotGeo sg, StripeSet deep)
 {
     // the work list's length lives in device memory; its first min(length, n_sorted) items are taken from `sorted` (the grouped copy:
     // the launch had to size the sort before the length was known), the others from the list as pass A left it - the order of the
@@ -296,19 +318,28 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
     __syncthreads();
     const uint32_t n_list = *p_n_list;
     const uint32_t n_grouped = sorted != nullptr ? (n_list < n_sorted ? n_list : n_sorted) : 0u;
+#ifdef BK_DIAG_B
+    unsigned long long d_used = 0, d_off = 0;
+#endif
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += gridDim.x * blockDim.x) {
+    uint32_t slot32 = 0;
+    // the item's key levels; true: the item is not settled and goes on the deep list (SPLIT only)
+    const bool push = [&]() -> bool {
 #ifdef BK_DIAG_B
     // counted per item kind, low word items, high word 64-byte lines: counter 5 = the bisections over the second- and the third-level
     // keys (items of both added up), counter 6 = what is left for suffix array + target after them
     unsigned long long d_k2 = 0, d_deep = 0, d_sa = 0;
     struct Fin { unsigned long long &a, &b, &c; DevBatch &bb; __device__ ~Fin() { if (a + b) atomicAdd(&bb.ctr[ctr_stripe() + 5], a + b); if (c) atomicAdd(&bb.ctr[ctr_stripe() + 6], c); } } fin{d_k2, d_deep, d_sa, b};
 #endif
-    const uint32_t slot32 = i < n_grouped ? sorted[i] : list[i];
+    BK_B_TRIP();
+    slot32 = i < n_grouped ? sorted[i] : list[i];
     const uint64_t slot = slot32;
     uint32_t a;
     int strand, c;
     slot_decode(slot32, sg, a, strand, c);                  // (reciprocals of iv_stride and iv_cores from the launch)
+    BK_B_TRIP();
     const uint32_t r = b.act[a];
+    BK_B_TRIP();
     const uint32_t meta = b.rmeta[r];
     const int len = (int)(meta & kReadLenMask);
     const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
@@ -322,17 +353,21 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
     uint64_t cnt = raw & ((1u << kKindShift) - 1);
     const int k = ix.k;
     if (kind == kKindFull) {
+        if (SPLIT) return true;                             // (the record stays as pass A left it)
+        BK_B_TRIP();
         search_core<WIDE>(ix, rdw, my_ofs, cl, ~0ULL >> 1, first, cnt);
         iv_put(b, slot, first, cnt > 0x7FFFFFFFULL ? 0x7FFFFFFFu : (uint32_t)cnt);
-        continue;
+        return false;
     }
     if (kind == kKindK2) {
         const uint32_t m = k2_mask(cl - k);
+        BK_B_TRIP();
         const uint32_t q2 = squeeze2(rdw.nib16(my_ofs + k)) & m;
         // lower and upper bound through the sampled levels: a line per level and bound (bk_dev_k2.h)
         uint64_t l1, l2;
         unsigned long long k2_lines = 0;                    // (counted by -DBK_DIAG_B builds only)
         k2_bounds(ix.k2, s_lv, first, cnt, m, q2, l1, l2, k2_lines);
+        BK_B_LINES(k2_lines);
 #ifdef BK_DIAG_B
         d_k2 += 1 + (k2_lines << 32);                       // (low word: items of this kind; high word: their lines)
 #endif
@@ -340,6 +375,7 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
         {
             const int upto = cl < k + kK2Bases ? cl : k + kK2Bases;
             while (l2 > l1) {
+                BK_B_TRIP();
                 const uint32_t kv = ix.k2[l2 - 1];
                 if (!k2_nkind(kv) || cmp_core_from(rdw, my_ofs, upto, k, ix.tgt4, sa_get<WIDE>(ix, l2 - 1)) == 0) break;
                 l2--;
@@ -351,13 +387,13 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
             b.iv32[(uint32_t)strand * b.n_reads + r] = make_uint2((uint32_t)first, (uint32_t)cnt);
         if (cnt == 0 || cl <= k + kK2Bases) {
             iv_put(b, slot, first, cnt > 0x7FFFFFFFULL ? 0x7FFFFFFFu : (uint32_t)cnt);
-            continue;
+            return false;
         }
     }
     // [first, first+cnt) agrees with the core on its first k+15 bases
     if (lazy && cnt <= kLazyBucket) {
         iv_put(b, slot, first, (uint32_t)cnt | kLazyFlag);
-        continue;
+        return false;
     }
     int start = k + kK2Bases;
     // the next 15 bases from the third-level keys and the 15 after those from the fourth-level keys, the way the second-level keys gave
@@ -365,6 +401,7 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
     bool settled = false;
     for (int lv = 0; lv < kMoreKeys && ix.kx[lv] != nullptr; lv++) {
         const uint32_t *__restrict__ kx = ix.kx[lv];
+        BK_B_TRIP();
         const uint64_t p3 = rdw.nib16(my_ofs + start);
         if (p3 & 0x4444444444444444ULL & top_mask(cl - start < kK2Bases ? cl - start : kK2Bases)) break;
         const uint32_t m3 = k2_mask(cl - start);
@@ -372,12 +409,14 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
         uint64_t l1, l2;
         unsigned long long k3_lines = 0;
         k2_bounds(kx, s_lv, first, cnt, m3, q3, l1, l2, k3_lines);
+        BK_B_LINES(k3_lines);
 #ifdef BK_DIAG_B
         d_deep += 1 + (k3_lines << 32);                     // (low word: items that consult the third-level keys; high word: their lines)
 #endif
         {
             const int upto = cl < start + kK2Bases ? cl : start + kK2Bases;
             while (l2 > l1) {
+                BK_B_TRIP();
                 const uint32_t kv = kx[l2 - 1];
                 if (!k2_nkind(kv) || cmp_core_from(rdw, my_ofs, upto, start, ix.tgt4, sa_get<WIDE>(ix, l2 - 1)) == 0) break;
                 l2--;
@@ -397,7 +436,13 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
             break;
         }
     }
-    if (settled) continue;
+    if (settled) return false;
+    if (SPLIT) {
+        // the continuation: what the key levels left of the interval (never wider than the item's own: below 2^kKindShift).  How many
+        // bases they covered is not stored - k_search_deep works it out from the read as the loop above did
+        iv_put(b, slot, first, (uint32_t)cnt | (kKindDeep << kKindShift));
+        return true;
+    }
     {
         uint64_t l1 = first, h1 = first + cnt, l2 = first, h2 = first + cnt;
         while (l1 < h1 || l2 < h2) {
@@ -406,7 +451,9 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
 #ifdef BK_DIAG_B
             d_sa += (2ULL << 32) * (a1 + (a2 && m1 != m2));            // (an element of the suffix array and a window of the target per probe)
 #endif
+            BK_B_TRIP();
             const uint64_t s1 = a1 ? sa_get<WIDE>(ix, m1) : 0, s2 = a2 ? sa_get<WIDE>(ix, m2) : 0;
+            BK_B_TRIP();
             const int c1 = a1 ? cmp_core_from(rdw, my_ofs, cl, start, ix.tgt4, s1) : 0;
             const int c2 = a2 ? cmp_core_from(rdw, my_ofs, cl, start, ix.tgt4, s2) : 0;
             if (a1) { if (c1 > 0) l1 = m1 + 1; else h1 = m1; }
@@ -419,7 +466,122 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
         cnt = l2 - l1;
     }
     iv_put(b, slot, first, cnt > 0x7FFFFFFFULL ? 0x7FFFFFFFu : (uint32_t)cnt);
+    return false;
+    }();
+    if (SPLIT && push) {
+        // the lanes of the wave that hand their item on take places in the tile's stripe together: one atomic a wave, on one of
+        // kListStripes lines (tile = the 256 items this block has in hand; a tile appends at most 256 slots: stripe_cap)
+        const uint64_t m = __ballot(1);
+        const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
+        const uint64_t tile = i >> 8;
+        uint32_t w = 0;
+        if (lane == leader) w = stripe_reserve_tile(deep, 0, (uint32_t)__popcll(m), tile);
+        w = __shfl(w, leader);
+        stripe_put_tile(deep, 0, w + (uint32_t)__popcll(m & ((1ULL << lane) - 1)), slot32, tile);
+    }
   }
+    BK_B_FLUSH(phase);
+}
+
+// cmp_core_from with the core's first kTailWords 16-base words behind `start` held in registers (masked to the core's length): the tail's
+// bisection compares the same bases of the read a dozen times or two, and in a launch where every lane does so the rows of the resident
+// waves no longer fit the caches - every step fetched them again
+constexpr int kTailWords = 4;
+template <typename Row>
+__device__ __forceinline__ int cmp_tail(const uint64_t (&pw)[kTailWords], const Row &rdw, int ofs, int cl, int start,
+                                        const uint64_t *__restrict__ tgt, uint64_t pos)
+{
+#pragma unroll
+    for (int j = 0; j < kTailWords; j++) {
+        const int i = start + 16 * j;
+        if (i >= cl) return 0;
+        const uint64_t t = nib16(tgt, pos + i) & top_mask(cl - i);
+        if (pw[j] != t) return pw[j] < t ? -1 : 1;
+    }
+    return cmp_core_from(rdw, ofs, cl, start + 16 * kTailWords, tgt, pos);
+}
+
+// The tails of pass B's items ("search_split"), a lane per slot of the deep list: the bisection over suffix array and target from the first
+// base no key level covered (kKindDeep, the interval k_search_b narrowed), the full search (kKindFull).  It stores the slot's final
+// record, as the unsplit pass B does.  How many bases the key levels covered comes from the read alone: k + 15, and 15 more for every key
+// array the index has, up to the first whose 15 bases hold an N in the read - the rule of k_search_b's loop, which hands an item on only
+// where the core is longer than that.
+template <bool WIDE>
+__global__ void __launch_bounds__(256) k_search_deep(DevIndex ix, DevBatch b, int phase, const uint32_t *__restrict__ list,
+                                                     const uint32_t *__restrict__ p_n_list, SlotGeo sg)
+{
+    extern __shared__ uint2 s_plan[];
+    plan_stage(s_plan, b, phase, threadIdx.x, 256);
+    __syncthreads();
+    const uint32_t n_list = *p_n_list;
+#ifdef BK_DIAG_B
+    unsigned long long d_used = 0, d_off = 0;
+#endif
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += gridDim.x * blockDim.x) {
+#ifdef BK_DIAG_B
+    unsigned long long d_sa = 0;                            // counter 6, as in k_search_b
+    struct Fin { unsigned long long &c; DevBatch &bb; __device__ ~Fin() { if (c) atomicAdd(&bb.ctr[ctr_stripe() + 6], c); } } fin{d_sa, b};
+#endif
+    BK_B_TRIP();
+    const uint32_t slot32 = list[i];
+    const uint64_t slot = slot32;
+    uint32_t a;
+    int strand, c;
+    slot_decode(slot32, sg, a, strand, c);
+    BK_B_TRIP();
+    const uint32_t r = b.act[a];
+    BK_B_TRIP();
+    const uint32_t meta = b.rmeta[r];
+    const int len = (int)(meta & kReadLenMask);
+    const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
+    const int cl = g.cl, cd = g.cd;
+    const int my_ofs = c * cd < len - cl ? c * cd : len - cl;
+    const RdRow rdw = read_row(b, r, strand, (meta & kReadHasN) != 0);
+    uint64_t first;
+    uint32_t raw;
+    iv_get(b, slot, first, raw);
+    uint64_t cnt = raw & ((1u << kKindShift) - 1);
+    if ((raw >> kKindShift) == kKindFull) {
+        BK_B_TRIP();
+        search_core<WIDE>(ix, rdw, my_ofs, cl, ~0ULL >> 1, first, cnt);
+        iv_put(b, slot, first, cnt > 0x7FFFFFFFULL ? 0x7FFFFFFFu : (uint32_t)cnt);
+        continue;
+    }
+    int start = ix.k + kK2Bases;
+    for (int lv = 0; lv < kMoreKeys && ix.kx[lv] != nullptr && cl > start; lv++) {
+        BK_B_TRIP();
+        const uint64_t p3 = rdw.nib16(my_ofs + start);
+        if (p3 & 0x4444444444444444ULL & top_mask(cl - start < kK2Bases ? cl - start : kK2Bases)) break;
+        start += kK2Bases;
+    }
+    uint64_t pw[kTailWords];
+#pragma unroll
+    for (int j = 0; j < kTailWords; j++) {
+        const int at = start + 16 * j;
+        pw[j] = at < cl ? rdw.nib16(my_ofs + at) & top_mask(cl - at) : 0;
+    }
+    uint64_t l1 = first, h1 = first + cnt, l2 = first, h2 = first + cnt;
+    while (l1 < h1 || l2 < h2) {
+        const bool a1 = l1 < h1, a2 = l2 < h2;
+        const uint64_t m1 = l1 + ((h1 - l1) >> 1), m2 = l2 + ((h2 - l2) >> 1);
+#ifdef BK_DIAG_B
+        d_sa += (2ULL << 32) * (a1 + (a2 && m1 != m2));
+#endif
+        BK_B_TRIP();
+        const uint64_t s1 = a1 ? sa_get<WIDE>(ix, m1) : 0, s2 = a2 ? sa_get<WIDE>(ix, m2) : 0;
+        BK_B_TRIP();
+        const int c1 = a1 ? cmp_tail(pw, rdw, my_ofs, cl, start, ix.tgt4, s1) : 0;
+        const int c2 = a2 ? cmp_tail(pw, rdw, my_ofs, cl, start, ix.tgt4, s2) : 0;
+        if (a1) { if (c1 > 0) l1 = m1 + 1; else h1 = m1; }
+        if (a2) { if (c2 >= 0) l2 = m2 + 1; else h2 = m2; }
+    }
+#ifdef BK_DIAG_B
+    d_sa += 1;
+#endif
+    cnt = l2 - l1;
+    iv_put(b, slot, l1, cnt > 0x7FFFFFFFULL ? 0x7FFFFFFFu : (uint32_t)cnt);
+  }
+    BK_B_FLUSH(phase);
 }
 
 void launch_search(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
@@ -475,15 +637,35 @@ void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
 }
 
 // list: the work items as pass A left them (*p_n_list of them, at most n_bound); sorted / n_sorted: the grouped copy of the first n_sorted (or null)
+// deep_cnt null: a lane carries its item to the end.  Else ("search_split") the items the key levels do not settle are finished by a second
+// launch: their slots go through the stripes of `stage` (at least n_bound + (kListStripes + 2) * 1024 entries; stripe_cnt as for pass A)
+// into `deep_list` (at least n_bound entries; it may be `list` itself, which nobody reads once k_search_b has ended) and their number is
+// added to *deep_cnt, zero before the call.  k_search_deep is sized by n_bound as well: blocks beyond the count leave at once, none at all
+// does nothing.
 void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int phase, int lazy, const uint32_t *list, const uint32_t *sorted,
-                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, hipStream_t s)
+                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, uint32_t *deep_list, uint32_t *deep_cnt, uint32_t *stage,
+                     uint32_t *stripe_cnt, hipStream_t s)
 {
     if (!n_bound) return;
-    unsigned blocks = (unsigned)std::min<uint64_t>((n_bound + 255) / 256, 32768);
+    const uint64_t tiles = (n_bound + 255) / 256;
+    unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 32768);
     const SlotGeo sg = slot_geo_make(b.iv_stride, b.iv_cores);
     const size_t lds = (size_t)b.plan_n * sizeof(uint2);
-    if (ix.sa_hi) hipLaunchKernelGGL(k_search_b<true>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg);
-    else hipLaunchKernelGGL(k_search_b<false>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg);
+    StripeSet deep;
+    deep.cnt = stripe_cnt;
+    deep.stage[0] = deep.stage[1] = deep.stage[2] = stage;
+    deep.cap = stripe_cap((unsigned)tiles, 256);                      // (stripes go by tile number)
+    if (deep_cnt == nullptr) {
+        if (ix.sa_hi) hipLaunchKernelGGL((k_search_b<true, false>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
+        else hipLaunchKernelGGL((k_search_b<false, false>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
+        return;
+    }
+    if (ix.sa_hi) hipLaunchKernelGGL((k_search_b<true, true>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
+    else hipLaunchKernelGGL((k_search_b<false, true>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
+    launch_compact(deep, &deep_list, &deep_cnt, 1, nullptr, s);
+    blocks = (unsigned)std::min<uint64_t>(tiles, 8192);
+    if (ix.sa_hi) hipLaunchKernelGGL(k_search_deep<true>, dim3(blocks), dim3(256), lds, s, ix, b, phase, deep_list, deep_cnt, sg);
+    else hipLaunchKernelGGL(k_search_deep<false>, dim3(blocks), dim3(256), lds, s, ix, b, phase, deep_list, deep_cnt, sg);
 }
 
 // the interval records of the slots a phase can use - [strand][core][position in the active list] for every core below cmax - set
@@ -513,12 +695,18 @@ void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_
 
 }  // namespace bk
 
-// in-kernel section timers (bk_dev_prof.h): BK_PROF == 1 reads k_flat's, 2 pass A's
+// in-kernel section timers (bk_dev_prof.h): BK_PROF == 1 reads k_flat's, 2 pass A's; a -DBK_DIAG_B build reads pass B's lane use
 namespace bk { int prof_read_flat(unsigned long long *out16); }
 extern "C" int bk_debug_prof(unsigned long long *out16)
 {
 #if defined(BK_PROF) && BK_PROF == 2
     return bk::prof_read(out16);
+#elif defined(BK_DIAG_B)
+    // lane use of pass B since the library was loaded: phase p's lane-trips used in word 2p, offered in word 2p + 1 (p < 8)
+    unsigned long long h[64 * 16];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(bk::g_diag_b), sizeof(h)) != hipSuccess) return 1;
+    for (int k = 0; k < 16; k++) { out16[k] = 0; for (int s0 = 0; s0 < 64; s0++) out16[k] += h[s0 * 16 + k]; }
+    return 0;
 #elif defined(BK_PROF)
     return bk::prof_read_flat(out16);
 #else

@@ -136,6 +136,12 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->sort_lists_set = true;
         return old;
     }
+    if (n == "search_split") {             // host only: pass B as one launch (0) or as key levels + a dense launch of the tails (1); the same records either way
+        int64_t old = search_split_on(c) ? 1 : 0;
+        c->search_split = value ? 1 : 0;
+        c->search_split_set = true;
+        return old;
+    }
     if (n == "use_tgt2") {
         int64_t old = c->use_tgt2;
         c->use_tgt2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
