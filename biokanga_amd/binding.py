@@ -14,7 +14,7 @@ EXPORTED_SYMBOLS = [
     "bk_version", "bk_strerror", "bk_device_count", "bk_ctx_create", "bk_ctx_create_from_device",
     "bk_ctx_clone", "bk_ctx_destroy", "bk_ctx_set_params", "bk_ctx_tune", "bk_num_entries", "bk_get_entry",
     "bk_dataset_name", "bk_concat_len", "bk_sfx_el_size", "bk_min_core_len", "bk_align_batch",
-    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_site_octamers", "bk_site_octamers_device", "bk_primer_correct", "bk_primer_correct_device", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
+    "bk_align_batch_device", "bk_pair_batch", "bk_pair_batch_device", "bk_pair_batch_seg2", "bk_pair_batch_seg2_device", "bk_batch_loci", "bk_batch_seg2", "bk_snp_reset", "bk_snp_pileup", "bk_snp_pileup_device", "bk_snp_sites", "bk_snp_counts", "bk_snp_centroid_insts", "bk_site_octamers", "bk_site_octamers_device", "bk_primer_correct", "bk_primer_correct_device", "bk_constraints_create", "bk_constraints_destroy", "bk_constraints_check", "bk_get_counters", "bk_get_timing", "bk_seq_counts", "bk_seq_counts_allreduce", "bk_build_sa_device",
     "bk_host_alloc", "bk_host_free", "bk_stream_create", "bk_stream_submit", "bk_stream_wait", "bk_stream_batch_loci",
     "bk_stream_batch_seg2", "bk_stream_release", "bk_stream_drain", "bk_stream_get_stats", "bk_stream_destroy",
     "bk_packed_words", "bk_pack_reads", "bk_align_batch_packed", "bk_stream_submit_packed", "bk_sam_format", "bk_batch_loci_trims", "bk_stream_batch_loci_trims", "bk_stream_submit_device", "bk_sam_prepare", "bk_sam_prep_free",
@@ -77,6 +77,12 @@ PRIMER_REQ_DTYPE = np.dtype([("codes", "<u8"), ("chrom_id", "<u4"), ("match_loci
                              ("max_mms", "u1"), ("_r", "u1", (3,))])
 PRIMER_RES_DTYPE = np.dtype([("codes", "<u8"), ("mask", "<u2"), ("status", "u1"), ("mismatches", "u1"), ("n_corrected", "u1"), ("_r", "u1", (3,))])
 assert PRIMER_REQ_DTYPE.itemsize == 24 and PRIMER_RES_DTYPE.itemsize == 16
+MAX_CONSTRAINED_SEQS, MAX_CONSTRAINTS, CONSTRAINT_R = 64, 6400, 0x10
+CONSTRAINT_UNTOUCHED, CONSTRAINT_TOUCHED, CONSTRAINT_VIOLATED, CONSTRAINT_BAD = 0, 1, 2, 0x80
+CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("mask", "u1"), ("_r", "u1", (3,))])
+CONSTRAINT_SEG_DTYPE = np.dtype([("start", "<u4"), ("len", "<u2"), ("read_idx", "<u2")])
+CONSTRAINT_REQ_DTYPE = np.dtype([("read_ofs", "<u8"), ("chrom_id", "<u4"), ("read_len", "<u2"), ("strand", "u1"), ("n_segs", "u1"), ("seg", CONSTRAINT_SEG_DTYPE, (2,))])
+assert CONSTRAINT_DTYPE.itemsize == 16 and CONSTRAINT_SEG_DTYPE.itemsize == 8 and CONSTRAINT_REQ_DTYPE.itemsize == 32
 
 ENTRY_DTYPE = np.dtype([("entry_id", "<u4"), ("seq_len", "<u4"), ("start_ofs", "<u8"), ("end_ofs", "<u8"),
                         ("name", "S81"), ("_pad", "S7")])
@@ -241,6 +247,12 @@ def load_library():
     lib.bk_primer_correct.restype = i32
     lib.bk_primer_correct_device.argtypes = [vp, vp, u64, vp, i32]
     lib.bk_primer_correct_device.restype = i32
+    lib.bk_constraints_create.argtypes = [vp, vp, u32, ctypes.POINTER(vp)]
+    lib.bk_constraints_create.restype = i32
+    lib.bk_constraints_destroy.argtypes = [vp]
+    lib.bk_constraints_destroy.restype = None
+    lib.bk_constraints_check.argtypes = [vp, vp, u64, vp, u64, vp, vp]
+    lib.bk_constraints_check.restype = i32
     lib.bk_seq_counts.argtypes = [vp, vp, u32, i32]
     lib.bk_seq_counts.restype = i32
     lib.bk_seq_counts_allreduce.argtypes = [ctypes.POINTER(vp), i32, vp, u32, i32]
@@ -413,6 +425,42 @@ def build_sa_device(d_seq_ptr, concat_len, d_sa_ptr, el_size=4, device=0):
     rc = load_library().bk_build_sa_device(d_seq_ptr, concat_len, d_sa_ptr, el_size, device)
     if rc:
         raise BkError(rc, "bk_build_sa_device")
+
+
+class Constraints:
+    """bk_constraints_*: a validated, sorted set of loci base constraints resident on an Aligner's GPU; close it before its Aligner"""
+
+    def __init__(self, aligner, table):
+        table = np.ascontiguousarray(table, dtype=CONSTRAINT_DTYPE)
+        self.lib, self.h = aligner.lib, None
+        h = ctypes.c_void_p()
+        rc = self.lib.bk_constraints_create(aligner.h, table.ctypes.data, len(table), ctypes.byref(h))
+        if rc:
+            raise BkError(rc, "bk_constraints_create")
+        self.h = h
+
+    def check(self, reqs, bases):
+        """CONSTRAINT_REQ_DTYPE requests against the set, their reads taken from `bases` (a byte per base) -> (a status byte per request,
+        [untouched, touched and accepted, violated, bad])"""
+        reqs = np.ascontiguousarray(reqs, dtype=CONSTRAINT_REQ_DTYPE)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        status = np.full(len(reqs), 0xA5, dtype=np.uint8)
+        counts = np.zeros(4, dtype=np.uint64)
+        rc = self.lib.bk_constraints_check(self.h, reqs.ctypes.data, len(reqs), bases.ctypes.data, bases.size, status.ctypes.data, counts.ctypes.data)
+        if rc:
+            raise BkError(rc, "bk_constraints_check")
+        return status, [int(x) for x in counts]
+
+    def close(self):
+        if self.h is not None:
+            self.lib.bk_constraints_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class Aligner:
@@ -652,6 +700,10 @@ class Aligner:
         rc = self.lib.bk_primer_correct_device(self.h, d_reqs_ptr, n, d_out_ptr, 1 if sync else 0)
         if rc:
             raise BkError(rc, "bk_primer_correct_device")
+
+    def constraints(self, table):
+        """the loci base constraints of `align -5` (CONSTRAINT_DTYPE records) on this context's GPU: a Constraints to check alignments against"""
+        return Constraints(self, table)
 
     def pair(self, bases, offs, lens, hits, pe, seg2=None):
         """PE association in place on `hits` (PE1/PE2 interleaved; the output of align() for the same reads).  seg2 = batch_seg2() of that

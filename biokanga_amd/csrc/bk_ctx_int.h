@@ -174,6 +174,7 @@ struct bk_ctx {
     uint32_t chunk_reads = 64u << 20;
     uint64_t site_chunk = 8u << 20;       // bk_site_octamers stages this many requests at a time ("site_chunk")
     uint64_t primer_chunk = 8u << 20;     // .. and bk_primer_correct this many ("primer_chunk")
+    uint64_t constraint_chunk = 4u << 20; // .. and bk_constraints_check this many ("constraint_chunk")
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)

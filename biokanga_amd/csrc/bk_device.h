@@ -121,6 +121,25 @@ struct DevIndex {
     int k;                      // k-mer table order (0 = none)
 };
 
+// -5: the loci base constraints of a run as the kernels of bk_constraints.hip read them (bk_constraints_create makes them)
+struct DevConstraint {          // sorted by (sequence, start, end); 16 bytes, read as one
+    uint32_t start, end;        // first and last constrained locus
+    uint32_t max_end;           // the largest `end` from the sequence's first constraint up to this one: never decreases inside a slice
+    uint32_t mask;              // 1 A | 2 C | 4 G | 8 T | 0x10 R
+};
+struct DevConstraintSlice {     // one per constrained sequence, sorted by chrom_id: its constraints are tab[first .. first + count)
+    uint32_t chrom_id, first, count, reserved;
+};
+struct DevConstraints {
+    const DevConstraint *tab;
+    const DevConstraintSlice *dir;
+    uint32_t n_tab, n_dir;      // <= BK_MAX_CONSTRAINTS, <= BK_MAX_CONSTRAINED_SEQS
+};
+struct ConstraintHit {          // a request that overlaps a constraint: per segment the constraints tab[lo .. hi) that may cover a locus of it (lo == hi: none)
+    uint32_t req;
+    uint16_t lo[2], hi[2];
+};
+
 struct DevAlignCfg {            // derived once per context (CAligner::LocateCoredApprox, Align)
     int max_subs, mm_delta, align_strand, max_ns, max_hits;
     int min_core_len, slides_per100, max_iter;

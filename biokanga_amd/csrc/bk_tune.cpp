@@ -89,6 +89,12 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->primer_chunk = (uint64_t)value;
         return old;
     }
+    if (n == "constraint_chunk") {         // requests bk_constraints_check stages at a time
+        int64_t old = (int64_t)c->constraint_chunk;
+        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
+        c->constraint_chunk = (uint64_t)value;
+        return old;
+    }
     if (n == "primer_buf_bytes")           // (read only) what bk_primer_correct's staging holds now: 0 until its first call
         return (int64_t)(c->buf.primer_reqs.cap() * sizeof(bk_primer_req) + c->buf.primer_res.cap() * sizeof(bk_primer_res));
     if (n == "kmer_bits" || n == "use_ktab") {

@@ -8,7 +8,7 @@
 //   biokanga index -i genome.fa[.gz] [-i more.fa] -o genome.sfx -r name [-l minseqlen] [-d descr] [-t title] [-T threads] [--device n]
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
-//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-T host threads] [-F logfile] [--device n | --devices 0-7]
+//                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-5 lociconstraints.csv] [-T host threads] [-F logfile] [--device n | --devices 0-7]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -50,6 +50,7 @@
 #include "snp.h"
 #include "site_prefs.h"
 #include "primer_correct.h"
+#include "loci_constraints.h"
 #include "read_loader.h"
 #include "contaminants.h"
 #include "report.h"
@@ -217,6 +218,7 @@ struct AlignOpts {
     SnpOpts snp;
     std::string site_prefs_path;           // -8: start-site octamer preferences into this file (empty: none)
     int site_prefs_ofs = -4;               // -9, cDfltRelSiteStartOfs
+    std::string constraints_path;          // -5: loci base constraints from this CSV file (empty: none)
     int primer_subs = 0;                   // -6: align at min(-s + this, 15), then correct 5' primer artefacts back under -s (0: off)
     int user_subs = 10;                    // -s as given (m_MaxSubs); P.max_subs is the rate the reads are aligned at (m_InitalAlignSubs)
     std::vector<regex_t> re_excl, re_incl;
@@ -374,6 +376,7 @@ int read_align_opts(Args &a, AlignOpts &o)
         while (!o.site_prefs_path.empty() && (o.site_prefs_path.front() == '"' || o.site_prefs_path.front() == '\'')) o.site_prefs_path.erase(0, 1);      // CUtility::TrimQuotes
         while (!o.site_prefs_path.empty() && (o.site_prefs_path.back() == '"' || o.site_prefs_path.back() == '\'')) o.site_prefs_path.pop_back();
     }
+    if (a.has("5")) o.constraints_path = a.str("5");        // (kanga.cpp:998-1004: the name as given)
     o.min_len = a.num("l", 50), o.max_len = a.num("L", 500);
     o.trim5 = a.num("y", 0), o.trim3 = a.num("Y", 0);
     o.max_rpt_sam_seqs = a.num("4", 10000);
@@ -900,6 +903,9 @@ struct AlignRun {
     std::vector<int> ctx_rc;
     std::vector<std::thread> loaders;
     int load_rc = 0;                               // what the read loader returned while they ran
+    // -5: the constraints on the first device (declared behind the contexts: goes before them)
+    struct ConstraintSet { bk_constraints *p = nullptr; ~ConstraintSet() { bk_constraints_destroy(p); } } constraints;
+    std::vector<uint8_t> constrained;              // by chrom_id: the sequence carries a constraint
     // the index's entries
     std::string species;
     uint32_t n_ent = 0;
@@ -939,8 +945,8 @@ int parse_align_args(int argc, char **argv, int first, Args &a)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H896", "EXN", a, err)) {
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
@@ -979,6 +985,7 @@ int print_param_lines(const AlignOpts &o)
         sp_file.close();
     }
     if (o.primer_subs > 0) param_line("correcting PCR 5' artefacts : %d\n", o.primer_subs);      // (kanga.cpp:1146-1147)
+    if (!o.constraints_path.empty()) param_line("Loci base constraints file: '%s'\n", o.constraints_path.c_str());      // (kanga.cpp:1264)
     return 0;
 }
 
@@ -1083,6 +1090,27 @@ int pack_reads_and_join_index(AlignRun &r)
     return 0;
 }
 
+// -5: the constraints are read as soon as the index's sequences are known (CAligner::Align, Aligner.cpp:328-337) and travel to the
+// first device, which checks the records against them behind the alignment (apply_loci_constraints)
+int load_constraints(AlignRun &r)
+{
+    const std::string &path = r.o.constraints_path;
+    diag("Loading loci base constraints from CSV file '%s' ...", path.c_str());
+    std::vector<bk_constraint> cons;
+    size_t n_chroms = 0;
+    std::string err;
+    if (bk::load_loci_constraints(path, r.ents, cons, n_chroms, err)) {
+        diag("%s", err.c_str());
+        diag("Unable to load loci constraints");
+        return 1;
+    }
+    const int rc = bk_constraints_create(r.ctx, cons.data(), (uint32_t)cons.size(), &r.constraints.p);
+    if (rc) { diag("Fatal: unable to set up the loci base constraints on device %d: %s", r.o.devices[0], bk_strerror(rc)); return 1; }
+    r.constrained = bk::constrained_chroms(cons);
+    diag("Completed loading %d loci base constraints for %d target sequences from CSV file '%s'", (int)cons.size(), (int)n_chroms, path.c_str());
+    return 0;
+}
+
 void tune_and_describe_image(AlignRun &r)
 {
     // (the other devices' contexts, copies of the first's image, make their window arrays when their first batch arrives)
@@ -1147,6 +1175,7 @@ void start_sam_head(AlignRun &r)
     const size_t nr = rs.size();
     // (-6 overwrites bases of the read store further down: no head start then - the formatter uploads the byte form, corrected, when
     // the records are written, and the bases are never dropped: may_drop_bases needs the head start)
+    // (-5 changes NARs, not bases: the head start goes ahead, as it does with -k)
     if (r.pre.fd >= 0 && r.rec.size() == rs.lens.size() && o.primer_subs == 0) {
         bk_sam_job hj{};
         hj.bases = rs.bases.data(); hj.n_bases = rs.bases.size(); hj.offs = rs.offs.data(); hj.lens = rs.lens.data();
@@ -1171,8 +1200,8 @@ void start_sam_head(AlignRun &r)
         if (a.has(opt))
             for (const std::string &fn : a.v.at(opt)) { struct stat ist; inputs_regular = inputs_regular && stat(fn.c_str(), &ist) == 0 && S_ISREG(ist.st_mode); }
     // (.. and not in the modes whose later steps read the bases on the host: the flank trimmer of -x / -A, the .jct / .ind files of -A / -a,
-    // -c's and -r5's records - there the read store stays whole)
-    const bool host_reads_bases = o.ml_mode == 5 || o.micro_indel || o.splice_len || o.min_chim || o.min_flank;
+    // -c's and -r5's records, the constraint pass of -5, which gathers the bases of the reads over a constraint - there the read store stays whole)
+    const bool host_reads_bases = o.ml_mode == 5 || o.micro_indel || o.splice_len || o.min_chim || o.min_flank || !o.constraints_path.empty();
     const bool may_drop_bases = inputs_regular && !host_reads_bases && r.pk_job.pk_words != nullptr && r.sam_prep != nullptr && !a.has("j") && !a.has("J") && !a.has("O") && o.snp.min_reads <= 0;
     if (nr)
         S.release_packed_in_background(r.pk_job.pk_words != nullptr ? r.sam_prep : nullptr,
@@ -1225,6 +1254,46 @@ void keep_chimeric_trims(bk::RecordSet &rec)
             n_ch++;
         }
     diag("Of the accepted aligned reads, %zu were chimeric", n_ch);
+}
+
+// -5: CAligner::IdentifyConstraintViolations, behind the paired-end association and the multi-loci assignment, before -k, -6 and -x
+// (Aligner.cpp:594).  Every accepted record on a constrained sequence goes to the first device with its adjusted loci (both segments
+// of a two-segment read; -c's trims are in place by now, as they are in the reference's records from the alignment on); the device
+// looks at the bases of those that lie over a constraint.  A violated record becomes eNARLociConstrained, with -U its mate too
+int apply_loci_constraints(AlignRun &r)
+{
+    const AlignOpts &o = r.o;
+    const ReadStore &rs = r.rs;
+    bk::RecordSet &rec = r.rec;
+    std::vector<bk_hit> &hits = rec.hits;
+    const char *kind = o.pe_mode ? "PE" : "SE";
+    diag("Identifying %s loci base constraint violations ...", kind);
+    HostClock clk;
+    bk::RawVec<bk_constraint_req> reqs;
+    bk::RawVec<uint32_t> rec_of;
+    par_select(rec.size(), o.nthreads, [&](size_t i) { return bk::constraint_selects(hits[i], r.constrained); },
+               [&](size_t at, size_t i) {
+                   const size_t rd = rec.RD(i);
+                   reqs[at] = bk::constraint_request(hits[i], rec.a_start(hits[i], i), rec.a_len(hits[i], i), rec.TL(i), rec.has_seg2(i) ? &rec.seg2[rd] : nullptr, rs.offs[rd], rs.lens[rd]);
+                   rec_of[at] = (uint32_t)i;
+               },
+               [&](size_t n) { reqs.resize(n); rec_of.resize(n); });
+    bk::RawVec<uint8_t> status(reqs.size());
+    clk.lap("constraint requests made");
+    uint64_t counts[4];
+    const int rc = bk_constraints_check(r.constraints.p, reqs.data(), reqs.size(), rs.bases.data(), rs.bases.size(), status.data(), counts);
+    if (rc) { diag("Fatal: the loci base constraint check failed: %s", bk_strerror(rc)); return 1; }
+    clk.lap("constraints checked (device)");
+    size_t n_marked = 0;
+    for (size_t k = 0; k < reqs.size(); k++) {
+        const int m = bk::constraint_apply(status[k], hits[rec_of[k]]);
+        if (m < 0) { diag("Fatal: the loci base constraint check turned a request down"); return 1; }
+        n_marked += (size_t)m;
+    }
+    if (o.pe_mode) n_marked += bk::constraint_mark_mates(hits);
+    clk.lap("constraint violations marked");
+    diag("Identified %d %s loci base constraint violations", (int)n_marked, kind);
+    return 0;
 }
 
 // CAligner::SortHitMatch (Aligner.cpp:10069-10114), ties left to the replica of the reference's sort.  The comparator's fields are
@@ -1442,7 +1511,7 @@ void check_simulated_reads(AlignRun &r, const AcceptedCounts &tot)
 int check_seq_counts(AlignRun &r)
 {
     const AlignOpts &o = r.o;
-    if (o.pe_mode || o.ml_mode || o.micro_indel || o.splice_len || o.min_chim || o.pcr_win >= 0 || o.min_flank || o.primer_subs || !o.re_excl.empty() || !o.re_incl.empty()) return 0;
+    if (o.pe_mode || o.ml_mode || o.micro_indel || o.splice_len || o.min_chim || o.pcr_win >= 0 || o.min_flank || o.primer_subs || !o.constraints_path.empty() || !o.re_excl.empty() || !o.re_incl.empty()) return 0;
     uint64_t tot = 0;
     for (uint64_t c : r.A.seq_counts) tot += c;
     if (tot != r.nar[1]) { diag("Fatal: the devices counted %llu accepted reads, the result records hold %llu", (unsigned long long)tot, (unsigned long long)r.nar[1]); return 1; }
@@ -1557,6 +1626,7 @@ int cmd_align(int argc, char **argv, int first)
     choose_index_image(r);
     load_reads_behind_index(r);                     // (the loader threads run ..
     if (pack_reads_and_join_index(r)) return 1;     //  .. until here: no return in between)
+    if (!o.constraints_path.empty() && load_constraints(r)) return 1;
     tune_and_describe_image(r);
     start_sam_file_late(r);
     if (make_accept_table(r)) return 1;
@@ -1565,6 +1635,7 @@ int cmd_align(int argc, char **argv, int first)
 
     resolve_multi_and_count_pairs(r);
     if (o.min_chim) keep_chimeric_trims(r.rec);
+    if (!o.constraints_path.empty() && apply_loci_constraints(r)) return 1;
     if (o.pcr_win >= 0 && !o.pe_mode) reduce_pcr_artefacts(r);
     if (o.primer_subs > 0 && correct_primer_artefacts(r)) return 1;
     if (o.min_flank > 0 && trim_flanks(r)) return 1;

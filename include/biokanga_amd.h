@@ -238,6 +238,7 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "debug_stop_phase" (test hook, see bk_debug_intervals)
  *   "chunk_reads" (reads per pass over the phases)   "max_read_len"   "site_chunk" (requests bk_site_octamers stages at a time)
  *   "primer_chunk" (requests bk_primer_correct stages at a time; "primer_buf_bytes": what its staging holds now, read only)
+ *   "constraint_chunk" (requests bk_constraints_check stages at a time)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -564,6 +565,54 @@ int  bk_primer_correct(bk_ctx *ctx, const bk_primer_req *reqs, uint64_t n, bk_pr
 /* the same HBM to HBM on the context's GPU (d_reqs 8-byte, d_out 16-byte aligned); asynchronous on the context's stream unless `sync`.
  * The caller guarantees the requests (a bad one comes back BK_PRIMER_BAD, nothing fetched) */
 int  bk_primer_correct_device(bk_ctx *ctx, const void *d_reqs, uint64_t n, void *d_out, int sync);
+
+/* ---- loci base constraints (-5) -------------------------------------------------------------------- */
+/* CAligner::IdentifyConstraintViolations' per-record half (AcceptLociConstraints / AcceptBaseConstraint, biokanga/Aligner.cpp:2480-2595)
+ * on the GPU: "reads aligned over lcA:100 are only accepted if they carry C or T there".  A constraint names a sequence, an inclusive
+ * range of loci and the bases allowed there: bits 0..3 = A C G T, bit 4 = R, "the read's base equals the target's".  A record is
+ * walked base by base over its one or two aligned segments, the read `& 7` and reverse-complemented as a whole for '-'; it violates
+ * when ANY constraint that covers a walked locus allows neither the base's bit nor (with R) equality with the target's base.  A read N
+ * has no bit; it equals a target N under R.  The limits are the reference's (Aligner.h:74-75).  Which records are asked about and what
+ * becomes of the answers is host policy above this boundary (biokanga_amd/csrc/host/loci_constraints.h). */
+#define BK_MAX_CONSTRAINED_SEQS 64
+#define BK_MAX_CONSTRAINTS      6400
+#define BK_CONSTRAINT_R         0x10
+typedef struct bk_constraint {
+    uint32_t chrom_id;           /* EntryID of the constrained sequence                                     */
+    uint32_t start, end;         /* first and last constrained locus, 0-based, start <= end < the sequence's length */
+    uint8_t  mask;               /* 1 A | 2 C | 4 G | 8 T | BK_CONSTRAINT_R; not 0                           */
+    uint8_t  reserved[3];
+} bk_constraint;                 /* 16 bytes */
+typedef struct bk_constraint_seg {
+    uint32_t start;              /* AdjStartLoci of the segment                                             */
+    uint16_t len;                /* its loci (AdjEndLoci - AdjStartLoci + 1); 0: nothing walked             */
+    uint16_t read_idx;           /* ReadOfs + TrimLeft: index of the first locus' base in the read as aligned */
+} bk_constraint_seg;             /* 8 bytes */
+typedef struct bk_constraint_req {
+    uint64_t read_ofs;           /* the read's first base in `bases` (a byte per base, code in the low three bits) */
+    uint32_t chrom_id;           /* Seg[0].ChromID - both segments are walked on it                         */
+    uint16_t read_len;           /* ReadLen                                                                 */
+    uint8_t  strand;             /* '+' | '-'                                                               */
+    uint8_t  n_segs;             /* 1, or 2 with FlagSegs                                                   */
+    bk_constraint_seg seg[2];
+} bk_constraint_req;             /* 32 bytes */
+/* one status byte per request; BAD: nothing was read for it - no such sequence, a strand other than '+' / '-', n_segs not 1 | 2, a
+ * segment that leaves its sequence or its read, a read outside `bases` */
+enum { BK_CONSTRAINT_UNTOUCHED = 0, BK_CONSTRAINT_TOUCHED = 1, BK_CONSTRAINT_VIOLATED = 2, BK_CONSTRAINT_BAD = 0x80 };
+typedef struct bk_constraints bk_constraints;
+/* The constraints of a run on the context's GPU: sorted by (sequence, start, end) with a slice per sequence and the running maximum of
+ * `end` inside each, about 100 KB at most.  BK_ERR_PARAMS: n > BK_MAX_CONSTRAINTS, more than BK_MAX_CONSTRAINED_SEQS sequences, a
+ * chrom_id that is no sequence of the index, start > end, end outside the sequence, a mask of 0 or with bits above BK_CONSTRAINT_R.
+ * n == 0 is a set that touches nothing.  The set must be destroyed before its context. */
+int  bk_constraints_create(bk_ctx *ctx, const bk_constraint *constraints, uint32_t n, bk_constraints **out);
+void bk_constraints_destroy(bk_constraints *set);
+/* host arrays, blocking, in chunks of "constraint_chunk" requests: the requests travel to the device, k_constraint_touch (one lane
+ * per request, geometry only) answers UNTOUCHED / BAD and lists the requests whose segments overlap a constraint, the host gathers the
+ * bases of those reads alone into page-locked staging, k_constraint_check (one wave per listed request) walks them.  The staging is
+ * made by the first call that has requests.  counts[4]: requests UNTOUCHED, TOUCHED (and accepted), VIOLATED, BAD - may be NULL.
+ * n_bases: the bytes of `bases`. */
+int  bk_constraints_check(bk_constraints *set, const bk_constraint_req *reqs, uint64_t n, const uint8_t *bases, uint64_t n_bases,
+                          uint8_t *status_out, uint64_t counts[4]);
 
 /* ---- SAM records formatted on the device -------------------------------------------------------------------------
  * CAligner::ReportBAMread (biokanga/Aligner.cpp:5768-6126; CSAMfile::AddAlignment, SAMfile.cpp:2100-2283) prints one text line per
