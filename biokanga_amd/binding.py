@@ -20,6 +20,7 @@ EXPORTED_SYMBOLS = [
     "bk_packed_words", "bk_pack_reads", "bk_align_batch_packed", "bk_stream_submit_packed", "bk_sam_format", "bk_batch_loci_trims", "bk_stream_batch_loci_trims", "bk_stream_submit_device", "bk_sam_prepare", "bk_sam_prep_free",
     "bk_host_register", "bk_host_unregister", "bk_ctx_reserve", "bk_stream_create_packed", "bk_align_batch_device_async", "bk_ctx_create_ex", "bk_ctx_set_chrom_filter", "bk_sam_prep_wait", "bk_debug_intervals", "bk_image_policy",
     "bk_contam_create", "bk_contam_destroy", "bk_contam_match",
+    "bk_samtags", "bk_sam_format_tags",
 ]
 
 
@@ -77,6 +78,11 @@ PRIMER_REQ_DTYPE = np.dtype([("codes", "<u8"), ("chrom_id", "<u4"), ("match_loci
                              ("max_mms", "u1"), ("_r", "u1", (3,))])
 PRIMER_RES_DTYPE = np.dtype([("codes", "<u8"), ("mask", "<u2"), ("status", "u1"), ("mismatches", "u1"), ("n_corrected", "u1"), ("_r", "u1", (3,))])
 assert PRIMER_REQ_DTYPE.itemsize == 24 and PRIMER_RES_DTYPE.itemsize == 16
+# bk_samtag_req: the line of one SAM record for its NM:i / MD:Z - [c5 S] m M [c3 S] [gap gop m2 M] from `pos` (0-based) of sequence chrom_id
+SAMTAG_REQ_DTYPE = np.dtype([("read_ofs", "<u8"), ("chrom_id", "<u4"), ("pos", "<u4"), ("read_len", "<u2"), ("strand", "u1"), ("gop", "u1"),
+                             ("c5", "<u2"), ("m", "<u2"), ("c3", "<u2"), ("m2", "<u2"), ("gap", "<i4")])
+assert SAMTAG_REQ_DTYPE.itemsize == 32
+SAMTAG_NM, SAMTAG_MD, SAMTAG_NONE = 1, 2, 0xFFFF
 MAX_CONSTRAINED_SEQS, MAX_CONSTRAINTS, CONSTRAINT_R = 64, 6400, 0x10
 CONSTRAINT_UNTOUCHED, CONSTRAINT_TOUCHED, CONSTRAINT_VIOLATED, CONSTRAINT_BAD = 0, 1, 2, 0x80
 CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("mask", "u1"), ("_r", "u1", (3,))])
@@ -295,6 +301,10 @@ def load_library():
     lib.bk_stream_destroy.restype = None
     lib.bk_sam_format.argtypes = [vp, ctypes.POINTER(_SamJob), _SAM_SINK, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.bk_sam_format.restype = i32
+    lib.bk_sam_format_tags.argtypes = [vp, ctypes.POINTER(_SamJob), u32, _SAM_SINK, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.bk_sam_format_tags.restype = i32
+    lib.bk_samtags.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    lib.bk_samtags.restype = i32
     lib.bk_contam_create.argtypes = [ctypes.POINTER(vp), i32, vp, u32]
     lib.bk_contam_create.restype = i32
     lib.bk_contam_destroy.argtypes = [vp]
@@ -727,10 +737,44 @@ class Aligner:
             raise BkError(rc, "bk_pair_batch_seg2")
         return hits, seg2
 
+    def samtags(self, reqs, bases, md=True, md_cap=None):
+        """bk_samtags: NM:i / MD:Z of SAMTAG_REQ_DTYPE requests, their reads taken from `bases` (a byte per base) -> (NM per request as
+        uint16, SAMTAG_NONE = no tags; a list of MD texts as bytes, None without tags).  md=False: NM alone, (nm, None).  md_cap: the
+        size of the text buffer handed over (default: asked for first); too small raises BkError with .needed = the bytes wanted and
+        .untouched = True when nothing of the outputs was written."""
+        reqs = np.ascontiguousarray(reqs, dtype=SAMTAG_REQ_DTYPE)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        n = len(reqs)
+        nm = np.full(max(n, 1), 0xABCD, dtype=np.uint16)
+        needed = ctypes.c_uint64()
+        if not md:
+            rc = self.lib.bk_samtags(self.h, reqs.ctypes.data, n, bases.ctypes.data, len(bases), nm.ctypes.data, None, None, 0, ctypes.byref(needed))
+            if rc:
+                raise BkError(rc, "bk_samtags")
+            return nm[:n], None
+        ofs = np.full(n + 1, 0xABCDABCD, dtype=np.uint64)
+        if md_cap is None:
+            probe = np.zeros(1, dtype=np.uint8)
+            rc = self.lib.bk_samtags(self.h, reqs.ctypes.data, n, bases.ctypes.data, len(bases), nm.ctypes.data, ofs.ctypes.data, probe.ctypes.data, 0, ctypes.byref(needed))
+            if rc and rc != -95:
+                raise BkError(rc, "bk_samtags")
+            md_cap = int(needed.value)
+        text = np.full(max(md_cap, 1), 0x7E, dtype=np.uint8)
+        rc = self.lib.bk_samtags(self.h, reqs.ctypes.data, n, bases.ctypes.data, len(bases), nm.ctypes.data, ofs.ctypes.data, text.ctypes.data, md_cap, ctypes.byref(needed))
+        if rc:
+            err = BkError(rc, "bk_samtags")
+            err.needed = int(needed.value)
+            err.untouched = bool((text == 0x7E).all() and (nm == 0xABCD).all() and (ofs == 0xABCDABCD).all())
+            raise err
+        raw = text.tobytes()
+        return nm[:n], [None if nm[i] == SAMTAG_NONE else raw[int(ofs[i]):int(ofs[i + 1])] for i in range(n)]
+
     def sam_format(self, bases, offs, lens, names, hits, order, report_unaligned=True, pe_mode=0, *, src=None, seg2=None,
-                   trim_left=None, trim_right=None):
+                   trim_left=None, trim_right=None, tags=None, packed=False):
         """bk_sam_format: the SAM body of `hits` in the order given, as bytes.  `names`: a list of bytes, one per read.  Without `src`
-        hits go by read; with it (record -> read) hits, order and the trims go by record, the read store and seg2 by read."""
+        hits go by read; with it (record -> read) hits, order and the trims go by record, the read store and seg2 by read.
+        tags: None, or the mask of bk_sam_format_tags (SAMTAG_NM | SAMTAG_MD; 0 is allowed).  packed: the reads travel in the packed
+        form of pack_reads (they must lie back to back in `bases`, in read order)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
@@ -756,13 +800,22 @@ class Aligner:
             job.n_src_reads = len(lens)
         else:
             assert len(hits) == len(lens)
+        if packed:
+            words, lens16, exc = pack_reads(bases, offs, lens)
+            keep += [words, lens16, exc]
+            job.bases, job.n_bases, job.offs, job.lens = None, 0, None, None
+            job.pk_words, job.n_pk_words, job.pk_lens16 = words.ctypes.data, len(words), lens16.ctypes.data
+            job.pk_exc, job.n_pk_exc = (exc.ctypes.data if len(exc) else None), len(exc)
         parts = {}
 
         def sink(user, text, n, ofs):
             parts[ofs] = ctypes.string_at(text, n)
             return 0
         n_rep, n_bytes = ctypes.c_uint64(), ctypes.c_uint64()
-        rc = self.lib.bk_sam_format(self.h, ctypes.byref(job), _SAM_SINK(sink), None, ctypes.byref(n_rep), ctypes.byref(n_bytes))
+        if tags is None:
+            rc = self.lib.bk_sam_format(self.h, ctypes.byref(job), _SAM_SINK(sink), None, ctypes.byref(n_rep), ctypes.byref(n_bytes))
+        else:
+            rc = self.lib.bk_sam_format_tags(self.h, ctypes.byref(job), int(tags), _SAM_SINK(sink), None, ctypes.byref(n_rep), ctypes.byref(n_bytes))
         if rc:
             raise BkError(rc, "bk_sam_format")
         text = b"".join(parts[k] for k in sorted(parts))

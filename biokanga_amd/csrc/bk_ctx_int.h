@@ -52,6 +52,12 @@ struct BatchBufs {
     DevBuf<bk_site_res> site_res;
     DevBuf<bk_primer_req> primer_reqs;    // bk_primer_correct: one chunk of requests and its results (made by its first call)
     DevBuf<bk_primer_res> primer_res;
+    DevBuf<bk_samtag_req> samtag_reqs;    // bk_samtags: one chunk of requests, its reads' bases and where each starts in them, the answers
+    DevBuf<uint8_t> samtag_bases, samtag_tmp;     //   (made by its first call; samtag_tmp: the offset scan's temporary)
+    DevBuf<uint64_t> samtag_gofs;
+    DevBuf<uint16_t> samtag_nm;
+    DevBuf<unsigned long long> samtag_len, samtag_at;
+    DevBuf<char> samtag_text;
     DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
@@ -175,6 +181,7 @@ struct bk_ctx {
     uint64_t site_chunk = 8u << 20;       // bk_site_octamers stages this many requests at a time ("site_chunk")
     uint64_t primer_chunk = 8u << 20;     // .. and bk_primer_correct this many ("primer_chunk")
     uint64_t constraint_chunk = 4u << 20; // .. and bk_constraints_check this many ("constraint_chunk")
+    uint64_t samtag_chunk = 2u << 20;     // .. and bk_samtags this many ("samtag_chunk")
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)

@@ -15,6 +15,7 @@
 
 #include "bk_ctx_int.h"
 #include "bk_env.h"
+#include "bk_samtags.h"
 
 namespace {
 
@@ -43,6 +44,13 @@ struct SamDev {
     const bk_seg2 *seg2;
     const uint16_t *trim_l, *trim_r;
     int ext;                         // any of the four is there: the kernels ask this first, so plain jobs never look at a record for them
+    // bk_sam_format_tags (tags = 0: none of this is looked at): the mask, the indexed target with its entry table, and per record of the
+    // slice the NM the measuring pass found (bk::kTagNone: the record gets no tags), which the writing pass places the MD text by
+    int tags;
+    const uint64_t *tgt4, *ent_start, *ent_end;
+    const uint32_t *id2idx;
+    uint32_t max_id, n_ix_ent;
+    uint16_t *tag_nm;
 };
 constexpr uint32_t kNoExc = 0xFFFFFFFFu;
 
@@ -175,6 +183,19 @@ __device__ __forceinline__ SamRec sam_rec(const SamDev &d, uint64_t k)
     return r;
 }
 
+// the walk of an accepted record's line for its NM / MD (bk_samtags.h): the numbers put_cigar writes, against the record's sequence
+__device__ __forceinline__ void sam_tag_walk(const SamDev &d, const SamRec &r, bk::TagWalk &w)
+{
+    const bk_hit h = d.hits[r.i];
+    const uint32_t e = h.chrom_id <= d.max_id ? d.id2idx[h.chrom_id] : 0xffffffffu;
+    if (e >= d.n_ix_ent || (h.strand != '+' && h.strand != '-')) return;
+    const uint64_t g0 = d.ent_start[e];
+    if (!bk::tag_walk_set(w, r.len, r.clip5, r.mlen, r.clip3, (uint32_t)(uint8_t)r.gop, r.gap, r.len2, h.strand != '+', r.pos, d.ent_end[e] - g0 + 1)) return;
+    w.g0 = g0 + r.pos;
+    if (d.bases) w.rd_at = d.offs[r.rd];
+    else { w.rd_at = d.pk_wofs[r.rd]; w.rd = r.rd; w.efirst = d.pk_efirst[r.rd]; }
+}
+
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 {
     return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src);
@@ -217,6 +238,8 @@ __global__ void __launch_bounds__(256) k_sam_any_qual(const uint8_t *__restrict_
     if (__ballot(acc != 0) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
+// TAGS: the job carries a tag mask (bk_sam_format_tags); without, the kernel is the one it was before there were tags
+template <bool TAGS>
 __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint32_t n, unsigned long long *__restrict__ bytes, uint32_t *__restrict__ n_rep)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -225,8 +248,8 @@ __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint
     r.reported = false; r.len = 0; r.i = 0; r.rd = 0;
     if (j < n) r = sam_rec(d, k0 + j);
     r.has_qual = wave_has_qual(d, (r.reported && d.bases) ? d.offs[r.rd] : 0, (r.reported && d.bases) ? r.len : 0);
+    unsigned long long b = 0;
     if (j < n) {
-        unsigned long long b = 0;
         if (r.reported) {
             rep = 1;
             const bk_hit h = d.hits[r.i];
@@ -243,8 +266,20 @@ __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint
                 // \t*\t0\t255\t <len>M\t*\t0\t0\t SEQ \t QUAL \t\tYU:Z:xx \n
                 b += 9 + n_digits(r.len) + 8 + r.len + 1 + qual + 7 + 2 + 1;
         }
-        bytes[j] = b;
     }
+    if (TAGS) {
+        // \tNM:i:<n> \tMD:Z:<s> behind QUAL of an accepted record whose line is a well-formed walk
+        bk::TagWalk tw{};
+        if (r.reported && r.acc) sam_tag_walk(d, r, tw);
+        const bk::TagReads rs{d.bases, d.pk_words, d.pk_exc, d.n_pk_exc};
+        uint32_t nm, md_len;
+        bk::wave_tags<false>(d.tgt4, rs, tw, nullptr, nm, md_len);
+        if (j < n) {
+            d.tag_nm[j] = (uint16_t)nm;
+            if (nm != bk::kTagNone) b += ((d.tags & BK_SAMTAG_NM) ? 6 + n_digits(nm) : 0) + ((d.tags & BK_SAMTAG_MD) ? 6 + md_len : 0);
+        }
+    }
+    if (j < n) bytes[j] = b;
     const uint64_t m = __ballot(rep != 0);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_rep, (uint32_t)__popcll(m));
 }
@@ -279,6 +314,7 @@ __device__ __forceinline__ void wave_copy(const uint8_t *src, char *dst, uint32_
     }
 }
 
+template <bool TAGS>
 __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32_t n, const unsigned long long *__restrict__ at, char *__restrict__ out)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -289,7 +325,7 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
     const uint8_t *s = !r.reported ? nullptr : (packed ? reinterpret_cast<const uint8_t *>(d.pk_words + d.pk_wofs[r.rd]) : d.bases + d.offs[r.rd]);
     r.has_qual = wave_has_qual(d, (r.reported && !packed) ? d.offs[r.rd] : 0, (r.reported && !packed) ? r.len : 0);
     // the lane writes its record's small fields and notes where the three bulk pieces go
-    char *w_name = nullptr, *w_seq = nullptr, *w_qual = nullptr;
+    char *w_name = nullptr, *w_seq = nullptr, *w_qual = nullptr, *w_md = nullptr;
     int seq_mode = 1, qual_mode = 3;
     if (r.reported) {
         const bk_hit h = d.hits[r.i];
@@ -319,7 +355,14 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
             *w++ = '\t';
             if (!r.has_qual) *w++ = '*';
             else { w_qual = w; qual_mode = h.strand == '+' ? 3 : 4; w += r.len; }
-            *w++ = '\n';
+            uint32_t nm = bk::kTagNone;
+            if (TAGS) nm = d.tag_nm[j];
+            if (nm != bk::kTagNone) {
+                if (d.tags & BK_SAMTAG_NM) { w = put_str(w, "\tNM:i:"); w = put_num(w, (long)nm); }
+                if (d.tags & BK_SAMTAG_MD) { w = put_str(w, "\tMD:Z:"); w_md = w; }       // (the text itself: the wave, below)
+                out[at[j + 1] - 1] = '\n';
+            } else
+                *w++ = '\n';
         } else {
             w = put_str(w, "\t*\t0\t255\t");
             w = put_num(w, r.len);
@@ -337,6 +380,13 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
     wave_copy(r.reported ? reinterpret_cast<const uint8_t *>(d.names + d.name_ofs[r.rd]) : nullptr, w_name, r.reported ? r.nml : 0, 0);
     wave_copy(s, w_seq, r.reported ? r.len : 0, packed ? seq_mode + 4 : seq_mode);
     wave_copy(s, w_qual, w_qual ? r.len : 0, qual_mode);
+    if (TAGS && (d.tags & BK_SAMTAG_MD)) {
+        bk::TagWalk tw{};
+        if (w_md) sam_tag_walk(d, r, tw);
+        const bk::TagReads rs{d.bases, d.pk_words, d.pk_exc, d.n_pk_exc};
+        uint32_t nm, md_len;
+        bk::wave_tags<true>(d.tgt4, rs, tw, w_md, nm, md_len);
+    }
     if (packed && r.reported) {
         // the record's bases that are not a,c,g,t: every code prints as N (the few there are: the lane walks its own runs)
         uint32_t e = d.pk_efirst[r.rd];
@@ -502,9 +552,14 @@ extern "C" int bk_sam_prep_wait(bk_sam_prep *prep)
 
 extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink, void *user, uint64_t *n_reported, uint64_t *n_bytes)
 {
+    return bk_sam_format_tags(c, job, 0, sink, user, n_reported, n_bytes);
+}
+
+extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tags, bk_sam_sink sink, void *user, uint64_t *n_reported, uint64_t *n_bytes)
+{
     if (!job) return BK_ERR_PARAMS;
     std::unique_ptr<bk_sam_prep> prep(job->prep);          // consumed whatever happens
-    if (!c || !sink || !n_reported || !n_bytes) return BK_ERR_PARAMS;
+    if (!c || !sink || !n_reported || !n_bytes || (tags & ~(uint32_t)(BK_SAMTAG_NM | BK_SAMTAG_MD)) || (tags && !c->ix.tgt4)) return BK_ERR_PARAMS;
     *n_reported = 0;
     *n_bytes = 0;
     if (!job->n_order) return BK_OK;
@@ -524,7 +579,7 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     auto lap = [&](const char *what) { const double t = now(); if (timing) fprintf(stderr, "bk timing: bk_sam_format %-28s %7.1f ms\n", what, 1e3 * (t - t_mark)); t_mark = t; };
     // the read store, names, records and order travel to the device once (pageable memory: staged by a few threads)
     SamReads own;
-    DevBuf d_hits, d_order, d_ent, d_bytes, d_at, d_tmp, d_cnt;
+    DevBuf d_hits, d_order, d_ent, d_bytes, d_at, d_tmp, d_cnt, d_tagnm;
 #define SAM_TRY(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return BK_ERR_MEM; } } while (0)
     // the read-side arrays: already on the device when bk_sam_prepare() was given these reads, else they travel now
     if (prep) {
@@ -545,6 +600,7 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     SAM_TRY(d_bytes.alloc(((size_t)slice + 1) * 8));
     SAM_TRY(d_at.alloc(((size_t)slice + 1) * 8));
     SAM_TRY(d_cnt.alloc(16));
+    if (tags) SAM_TRY(d_tagnm.alloc((size_t)slice * 2));
     size_t tb = 0;
     SAM_TRY(bk::prim::exclusive_sum(nullptr, tb, d_bytes.as<unsigned long long>(), d_at.as<unsigned long long>(), (size_t)slice + 1, s));
     SAM_TRY(d_tmp.alloc(tb + 256));
@@ -580,6 +636,11 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
     d.src = job->src ? d_src.as<uint32_t>() : nullptr; d.seg2 = job->seg2 ? d_seg2.as<bk_seg2>() : nullptr;
     d.trim_l = job->trim_left ? d_tl.as<uint16_t>() : nullptr; d.trim_r = job->trim_left ? d_tr.as<uint16_t>() : nullptr;
     d.ext = (d.src || d.seg2 || d.trim_l) ? 1 : 0;
+    d.tags = (int)tags;
+    if (tags) {
+        d.tgt4 = c->ix.tgt4; d.ent_start = c->ix.ent_start; d.ent_end = c->ix.ent_end; d.id2idx = c->ix.id2idx; d.max_id = c->ix.max_id; d.n_ix_ent = c->ix.n_ent;
+        d.tag_nm = d_tagnm.as<uint16_t>();
+    }
     // does any base carry a score at all?  (one streaming pass; without scores - FASTA input, or -g3 - no record is scanned for them)
     DevBuf d_anyq;
     SAM_TRY(d_anyq.alloc(16));
@@ -663,7 +724,8 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
         double t0 = now();
         hipError_t e = hipMemsetAsync(d_cnt.p, 0, 16, s);
         if (e == hipSuccess) e = hipMemsetAsync((char *)d_bytes.p + (size_t)n * 8, 0, 8, s);
-        hipLaunchKernelGGL(k_sam_measure, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.as<unsigned long long>(), d_cnt.as<uint32_t>());
+        if (tags) hipLaunchKernelGGL(k_sam_measure<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.as<unsigned long long>(), d_cnt.as<uint32_t>());
+        else hipLaunchKernelGGL(k_sam_measure<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.as<unsigned long long>(), d_cnt.as<uint32_t>());
         size_t t2 = tb + 256;
         if (e == hipSuccess) e = bk::prim::exclusive_sum(d_tmp.p, t2, d_bytes.as<unsigned long long>(), d_at.as<unsigned long long>(), (size_t)n + 1, s);
         unsigned long long bytes = 0;
@@ -691,7 +753,8 @@ extern "C" int bk_sam_format(bk_ctx *c, const bk_sam_job *job, bk_sam_sink sink,
         t_settle += now() - t0;
         if (rc != BK_OK) break;
         t0 = now();
-        hipLaunchKernelGGL(k_sam_write, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.as<unsigned long long>(), d_text[q].as<char>());
+        if (tags) hipLaunchKernelGGL(k_sam_write<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.as<unsigned long long>(), d_text[q].as<char>());
+        else hipLaunchKernelGGL(k_sam_write<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.as<unsigned long long>(), d_text[q].as<char>());
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ev_written[q], s);
         if (e == hipSuccess) e = hipStreamWaitEvent(cs, ev_written[q], 0);

@@ -95,7 +95,16 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->constraint_chunk = (uint64_t)value;
         return old;
     }
-    if (n == "primer_buf_bytes")           // (read only) what bk_primer_correct's staging holds now: 0 until its first call
+    if (n == "samtag_chunk") {             // requests bk_samtags stages at a time
+        int64_t old = (int64_t)c->samtag_chunk;
+        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
+        c->samtag_chunk = (uint64_t)value;
+        return old;
+    }
+    if (n == "samtag_buf_bytes")           // (read only) what bk_samtags' staging holds now: 0 until its first call
+        return (int64_t)(c->buf.samtag_reqs.cap() * sizeof(bk_samtag_req) + c->buf.samtag_bases.cap() + c->buf.samtag_tmp.cap() + c->buf.samtag_gofs.cap() * 8 +
+                         c->buf.samtag_nm.cap() * 2 + (c->buf.samtag_len.cap() + c->buf.samtag_at.cap()) * 8 + c->buf.samtag_text.cap());
+    if (n == "primer_buf_bytes")          // (read only) what bk_primer_correct's staging holds now: 0 until its first call
         return (int64_t)(c->buf.primer_reqs.cap() * sizeof(bk_primer_req) + c->buf.primer_res.cap() * sizeof(bk_primer_res));
     if (n == "kmer_bits" || n == "use_ktab") {
         int64_t old = n == "use_ktab" ? c->use_ktab : c->ix.k;

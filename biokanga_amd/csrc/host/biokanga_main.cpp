@@ -9,6 +9,7 @@
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
 //                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-5 lociconstraints.csv] [-T host threads] [-F logfile] [--device n | --devices 0-7]
+//                  [--sam-tags NM,MD]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -222,6 +223,8 @@ struct AlignOpts {
     int primer_subs = 0;                   // -6: align at min(-s + this, 15), then correct 5' primer artefacts back under -s (0: off)
     int user_subs = 10;                    // -s as given (m_MaxSubs); P.max_subs is the rate the reads are aligned at (m_InitalAlignSubs)
     std::vector<regex_t> re_excl, re_incl;
+    int sam_tags = 0;                      // --sam-tags: mask of BK_SAMTAG_NM | BK_SAMTAG_MD written behind QUAL of accepted records (0: none, the reference's lines)
+    uint64_t sam_tag_bytes() const { return ((sam_tags & BK_SAMTAG_NM) ? 8u : 0u) + ((sam_tags & BK_SAMTAG_MD) ? 16u : 0u); }      // .. about what they add to a line
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
 
@@ -360,6 +363,26 @@ int read_align_opts(Args &a, AlignOpts &o)
     if (o.ml_mode == 5 && !(o.fmt == 0 || o.fmt == 4 || o.fmt == 5 || o.fmt == 6)) {      // kanga.cpp:830-834
         diag("Error: reporting all multiloci alignments '-r5' is only available with output formats '-M0', '-M4', '-M5' and '-M6'");
         return 1;
+    }
+    // --sam-tags NM | MD | NM,MD (ours: the reference writes no optional field on an accepted record)
+    if (a.has("sam-tags")) {
+        const std::string spec = a.str("sam-tags");
+        for (size_t at = 0; at <= spec.size();) {
+            size_t end = spec.find(',', at);
+            if (end == std::string::npos) end = spec.size();
+            const std::string name = spec.substr(at, end - at);
+            if (name == "NM") o.sam_tags |= BK_SAMTAG_NM;
+            else if (name == "MD") o.sam_tags |= BK_SAMTAG_MD;
+            else {
+                diag("Error: SAM tags '--sam-tags %s' must be a list of NM and MD ('%s' is neither)", spec.c_str(), name.c_str());
+                return 1;
+            }
+            at = end + 1;
+        }
+        if (o.fmt >= 0 && o.fmt <= 4) {
+            diag("Error: SAM tags '--sam-tags %s' are only available with SAM / BAM output formats '-M5' and '-M6'", spec.c_str());
+            return 1;
+        }
     }
     if (a.has("O") && o.fmt == 6) {                 // kanga.cpp:1015-1021
         diag("Error: Output induced substitution mode '-O<file>' not available in '-M6' output mode\n");
@@ -945,14 +968,14 @@ int parse_align_args(int argc, char **argv, int first, Args &a)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}};
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}};
     if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
     if (!a.has("i") || !a.has("I") || !a.has("o")) {
         fprintf(stderr, "usage: %s align -i <reads> -I <genome.sfx> -o <out.sam> [-s subs] [-e delta] [-Q strand] [-m mode] [-n maxNs] "
-                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full]\n", g_proc.c_str());
+                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD]\n", g_proc.c_str());
         return 1;
     }
     return 0;
@@ -1022,7 +1045,7 @@ void start_early_buffers(AlignRun &r)
     const bool out_special = stat(r.opath.c_str(), &ost) == 0 && !S_ISREG(ost.st_mode);      // a FIFO, /dev/fd/N of a process substitution, /dev/null
     r.sam_plain = o.fmt >= 5 && !out_special && !is_bam_name(r.opath) && !is_gz_name(r.opath);
     r.pre_early = r.sam_plain && r.all_plain && r.plain_bytes >= bk::env::sam_early_min(256ULL << 20);      // (tests lower the input size from which the file is started early)
-    const uint64_t pre_early_est = (1u << 20) + r.plain_bytes + r.plain_bytes / (o.pe_mode ? 2 : 3);
+    const uint64_t pre_early_est = (1u << 20) + r.plain_bytes + r.plain_bytes / (o.pe_mode ? 2 : 3) + o.sam_tag_bytes() * r.est_reads;
     if (r.pre_early) r.pre.start(r.opath.c_str(), pre_early_est, 2);
 }
 
@@ -1130,7 +1153,7 @@ void start_sam_file_late(AlignRun &r)
     if (!r.sam_plain || r.pre.fd >= 0) return;
     if (nr < (size_t)bk::env::sam_device_min(200000ULL)) return;                // (tests lower the size from which the large-run machinery is used)
     uint64_t est = (1u << 20) + r.rs.name_bytes() + 40ULL * nr + (r.o.pe_mode ? 24ULL * nr : 0) + (uint64_t)r.n_ent * 128;
-    est += (uint64_t)(g_qual_mode != 3 ? 2 : 1) * r.rs.base_bytes();
+    est += (uint64_t)(g_qual_mode != 3 ? 2 : 1) * r.rs.base_bytes() + r.o.sam_tag_bytes() * nr;
     r.pre.start(r.opath.c_str(), est);
 }
 
@@ -1187,7 +1210,7 @@ void start_sam_head(AlignRun &r)
             hj.bases = nullptr; hj.n_bases = 0; hj.offs = nullptr; hj.lens = nullptr;
         }
         r.pk_job = hj;
-        const uint64_t per_rec = (rs.name_bytes() + (uint64_t)(g_qual_mode != 3 ? 2 : 1) * rs.base_bytes()) / std::max<size_t>(nr, 1) + 64 + (o.pe_mode ? 24 : 0);
+        const uint64_t per_rec = (rs.name_bytes() + (uint64_t)(g_qual_mode != 3 ? 2 : 1) * rs.base_bytes()) / std::max<size_t>(nr, 1) + 64 + (o.pe_mode ? 24 : 0) + o.sam_tag_bytes();
         if (bk_sam_prepare(r.ctx, &hj, (uint32_t)std::min<uint64_t>(per_rec + per_rec / 8, 1u << 20), &r.sam_prep) != BK_OK) { r.sam_prep = nullptr; r.pk_job = bk_sam_job{}; }
     }
     // The read store's bases - 5 GB of a 50 M-read run, a third of a second to hand back at the exit - have served too once the device
@@ -1572,6 +1595,7 @@ int write_reports(AlignRun &r)
 
     Report R{a, r.rs, r.rec, r.ents, r.species, r.n_ent, r.multi_dist, r.order, o.pe_mode, o.ml_mode, o.max_ml, o.fmt, o.nthreads, o.micro_indel, o.splice_len, o.max_rpt_sam_seqs};
     R.ctx = r.ctx;
+    R.sam_tags = (uint32_t)o.sam_tags;
     R.site_prefs = r.with_site_prefs ? &r.site_prefs : nullptr;
     R.pre = r.pre.fd >= 0 ? &r.pre : nullptr;
     r.S.done_with_head_start();

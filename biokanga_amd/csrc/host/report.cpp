@@ -206,6 +206,70 @@ static std::vector<uint8_t> seqs_with_hits(const std::vector<bk_hit> &hits, uint
     return has;
 }
 
+// --sam-tags where the host formats the records itself (gzip'd SAM, pipes, runs under BK_SAM_DEVICE_MIN, BAM): NM and MD of every
+// accepted record come from the first device in one go (bk_samtags: the walk of the line as written, against the sequence as indexed);
+// the formatters append them.  The CIGAR numbers are the ones format_rec / format_stripe write.
+struct HostSamTags {
+    std::vector<uint32_t> slot;        // record -> request (kNone: not asked about)
+    std::vector<uint16_t> nm;          // by request; BK_SAMTAG_NONE: no tags
+    std::vector<uint64_t> ofs;         // by request (+ 1): its MD text in `text`
+    std::vector<char> text;
+    static constexpr uint32_t kNone = 0xFFFFFFFFu;
+    // the request of record i, or kNone when it gets no tags
+    uint32_t of(size_t i) const { const uint32_t q = slot.empty() ? kNone : slot[i]; return q != kNone && nm[q] != BK_SAMTAG_NONE ? q : kNone; }
+    size_t md_len(uint32_t q) const { return ofs.empty() ? 0 : (size_t)(ofs[q + 1] - ofs[q]); }
+};
+
+static int host_sam_tags(Report &R, HostSamTags &T)
+{
+    const bk::RecordSet &recs = R.rec;
+    const size_t nr = recs.hits.size();
+    if (R.ctx == nullptr) { diag("Fatal: '--sam-tags' needs a device context for the tags"); return 1; }
+    T.slot.assign(nr, HostSamTags::kNone);
+    std::vector<bk_samtag_req> reqs;
+    for (size_t i = 0; i < nr; i++) {
+        const bk_hit &h = recs.hits[i];
+        if (h.nar != BK_NAR_ACCEPTED || (h.strand != '+' && h.strand != '-')) continue;
+        const size_t rd = recs.RD(i);
+        const uint32_t len = R.rs.lens[rd];
+        const uint32_t clip5 = h.strand == '+' ? recs.TL(i) : recs.TR(i), clip3 = h.strand == '+' ? recs.TR(i) : recs.TL(i), m = recs.a_len(h, i);
+        long gap = 0;
+        uint32_t m2 = 0;
+        uint8_t gop = 0;
+        if (recs.has_seg2(i)) {
+            const bk_seg2 &g = recs.seg2[rd];
+            const long d = (long)g.match_loci - ((long)h.match_loci + h.match_len);
+            if (g.flags & 4) { gop = 'N'; gap = d; }
+            else if (g.flags & 2) { gop = 'I'; gap = (long)len - ((long)h.match_len + g.match_len); }
+            else { gop = 'D'; gap = d < 0 ? -d : d; }
+            m2 = g.match_len;
+        }
+        if (len > 0xffffu || clip5 > 0xffffu || clip3 > 0xffffu || m > 0xffffu || m2 > 0xffffu || gap > 0x7fffffffL || gap < -0x7fffffffL) continue;      // (no such walk: no tags)
+        bk_samtag_req q{};
+        q.read_ofs = R.rs.offs[rd]; q.chrom_id = h.chrom_id; q.pos = recs.a_start(h, i); q.read_len = (uint16_t)len; q.strand = h.strand; q.gop = gop;
+        q.c5 = (uint16_t)clip5; q.m = (uint16_t)m; q.c3 = (uint16_t)clip3; q.m2 = (uint16_t)m2; q.gap = (int32_t)gap;
+        T.slot[i] = (uint32_t)reqs.size();
+        reqs.push_back(q);
+    }
+    const uint64_t n = reqs.size();
+    T.nm.assign(n + 1, (uint16_t)BK_SAMTAG_NONE);
+    const bool md = (R.sam_tags & BK_SAMTAG_MD) != 0;
+    int rc;
+    if (!md) rc = bk_samtags(R.ctx, reqs.data(), n, R.rs.bases.data(), R.rs.bases.size(), T.nm.data(), nullptr, nullptr, 0, nullptr);
+    else {
+        T.ofs.assign(n + 1, 0);
+        T.text.resize(16 * n + (1u << 16));
+        uint64_t needed = 0;
+        rc = bk_samtags(R.ctx, reqs.data(), n, R.rs.bases.data(), R.rs.bases.size(), T.nm.data(), T.ofs.data(), T.text.data(), T.text.size(), &needed);
+        if (rc == BK_ERR_MEM && needed > T.text.size()) {        // (more mismatches than the guess: the call says what the text takes)
+            T.text.resize(needed);
+            rc = bk_samtags(R.ctx, reqs.data(), n, R.rs.bases.data(), R.rs.bases.size(), T.nm.data(), T.ofs.data(), T.text.data(), T.text.size(), &needed);
+        }
+    }
+    if (rc != BK_OK) { diag("Fatal: the SAM tags could not be made on the device: %s", bk_strerror(rc)); return 1; }
+    return 0;
+}
+
     // ".bam" (more than 5 characters of name, kanga.cpp:848-857): BGZF-compressed BAM with its BAI index
 int report_bam(Report &R, const std::string &opath)
 {
@@ -221,6 +285,8 @@ int report_bam(Report &R, const std::string &opath)
     const int pe_mode = R.pe_mode, fmt = R.fmt, nthreads = R.nthreads, max_rpt_sam_seqs = R.max_rpt_sam_seqs;
     int rc = 0;
     std::vector<uint8_t> has_hit = seqs_with_hits(hits, n_ent, nthreads);
+    HostSamTags tags;
+    if (R.sam_tags && host_sam_tags(R, tags)) return 1;
     const bool all = (uint32_t)max_rpt_sam_seqs >= n_ent;
     std::string text = "@HD\tVN:1.4\tSO:coordinate";
     std::vector<int32_t> ref_of(n_ent + 1, -1);
@@ -290,7 +356,11 @@ int report_bam(Report &R, const std::string &opath)
             const char *qn = rs.name(recs.RD(i));
             const uint32_t l_qn = (uint32_t)strlen(qn) + 1;
             const char *tag = acc ? nullptr : kNarTag[h.nar < 20 ? h.nar : 0];
-            const uint32_t aux = tag ? 3 + (uint32_t)strlen(tag) + 1 : 0;
+            uint32_t aux = tag ? 3 + (uint32_t)strlen(tag) + 1 : 0;
+            // --sam-tags: NM as C up to 255, else S; MD as Z
+            const uint32_t tq = R.sam_tags ? tags.of(i) : HostSamTags::kNone;
+            if (tq != HostSamTags::kNone)
+                aux += ((R.sam_tags & BK_SAMTAG_NM) ? (tags.nm[tq] <= 255 ? 4u : 5u) : 0u) + ((R.sam_tags & BK_SAMTAG_MD) ? 3u + (uint32_t)tags.md_len(tq) + 1u : 0u);
             const bool two = acc && recs.has_seg2(i);
             // soft clips in target order: read orientation for '+', swapped for '-' (Aligner.cpp:5961-5984)
             const uint32_t clip5 = acc ? (h.strand == '+' ? recs.TL(i) : recs.TR(i)) : 0u, clip3 = acc ? (h.strand == '+' ? recs.TR(i) : recs.TL(i)) : 0u;
@@ -342,6 +412,20 @@ int report_bam(Report &R, const std::string &opath)
                 q += len;
             }
             if (tag) { *q++ = 'Y'; *q++ = 'U'; *q++ = 'Z'; size_t tl = strlen(tag) + 1; memcpy(q, tag, tl); q += tl; }
+            if (tq != HostSamTags::kNone) {
+                if (R.sam_tags & BK_SAMTAG_NM) {
+                    const uint16_t nm = tags.nm[tq];
+                    *q++ = 'N'; *q++ = 'M';
+                    if (nm <= 255) { *q++ = 'C'; *q++ = (uint8_t)nm; }
+                    else { *q++ = 'S'; memcpy(q, &nm, 2); q += 2; }
+                }
+                if (R.sam_tags & BK_SAMTAG_MD) {
+                    const size_t ml = tags.md_len(tq);
+                    *q++ = 'M'; *q++ = 'D'; *q++ = 'Z';
+                    memcpy(q, tags.text.data() + tags.ofs[tq], ml); q += ml;
+                    *q++ = 0;
+                }
+            }
             if (acc) S.al.push_back({(uint64_t)at, (uint64_t)(at + 4 + block), ref, (int32_t)pos0, (int32_t)(pos0 + hit_len - 1)});
             S.n++;
         }
@@ -446,6 +530,7 @@ int report_text(Report &R)
             return w + n;
         };
         // one record (CAligner::ReportBAMread, Aligner.cpp:5850-5924,6036-6054); false when the read is not reported
+        HostSamTags tags;                                   // --sam-tags, filled when the host formats (below)
         auto format_rec = [&](size_t k, Stripe &st) -> bool {
             uint32_t i = order[k];
             const bk_hit &h = hits[i];
@@ -455,7 +540,8 @@ int report_text(Report &R)
             uint32_t len = rs.lens[recs.RD(i)];
             const char *nm = rs.name(recs.RD(i));
             const size_t nml = strlen(nm);
-            char *w = st.room(nml + 2 * (size_t)len + 400);
+            const uint32_t tq = R.sam_tags ? tags.of(i) : HostSamTags::kNone;
+            char *w = st.room(nml + 2 * (size_t)len + 400 + (tq != HostSamTags::kNone ? tags.md_len(tq) : 0));
             memcpy(w, nm, nml);
             w += nml;
             int flag = 0, tlen = 0;
@@ -510,6 +596,10 @@ int report_text(Report &R)
                 w += len;
                 *w++ = '\t';
                 w = put_qual(w, s, len, h.strand != '+');
+                if (tq != HostSamTags::kNone) {
+                    if (R.sam_tags & BK_SAMTAG_NM) { w = put_str(w, "\tNM:i:"); w = put_num(w, (long)tags.nm[tq]); }
+                    if (R.sam_tags & BK_SAMTAG_MD) { w = put_str(w, "\tMD:Z:"); const size_t ml = tags.md_len(tq); memcpy(w, tags.text.data() + tags.ofs[tq], ml); w += ml; }
+                }
                 *w++ = '\n';
             } else {
                 w = put_str(w, "\t*\t0\t255\t");
@@ -608,7 +698,7 @@ int report_text(Report &R)
             uint64_t n_rep = 0, n_bytes = 0;
             int drc = BK_ERR_PARAMS;
             if (bk::env::sam_device_fail()) { if (job.prep) bk_sam_prep_free(job.prep); }       // (tests: the device declines after its head start)
-            else if (job_ok) drc = bk_sam_format(R.ctx, &job, sink, &st, &n_rep, &n_bytes);
+            else if (job_ok) drc = R.sam_tags ? bk_sam_format_tags(R.ctx, &job, R.sam_tags, sink, &st, &n_rep, &n_bytes) : bk_sam_format(R.ctx, &job, sink, &st, &n_rep, &n_bytes);
             else if (job.prep) bk_sam_prep_free(job.prep);
             if (drc == BK_OK) {
                 out.pos += (off_t)n_bytes;
@@ -625,6 +715,7 @@ int report_text(Report &R)
                 fprintf(stderr, "bk timing: device SAM formatter declined (%s): host threads format\n", bk_strerror(drc));
         }
         if (!device_done && R.restore_reads && R.restore_reads() != 0) { diag("Fatal: unable to reload the reads for the host formatter"); return 1; }
+        if (!device_done && R.sam_tags && host_sam_tags(R, tags)) return 1;
         // records are formatted by all host threads into per-thread buffers, one stripe of the sorted order
         // each, and written out in order (the reference formats serially, ~4.5 us per read)
         const size_t per_thread = 131072;

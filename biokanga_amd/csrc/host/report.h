@@ -22,6 +22,7 @@ struct Report {
     const std::vector<uint32_t> &order;           // records in the reference's output order
     int pe_mode, ml_mode, max_ml, fmt, nthreads, micro_indel, splice_len, max_rpt_sam_seqs;
     bk_ctx *ctx = nullptr;                        // a context whose device formats plain SAM records (bk_sam_format); may be null
+    uint32_t sam_tags = 0;                        // --sam-tags: BK_SAMTAG_NM | BK_SAMTAG_MD behind QUAL of accepted SAM / BAM records (made on ctx's device)
     const bk::SitePrefs *site_prefs = nullptr;    // -8: the table the BED / CSV score column is taken from (null: the column is 0)
     SamPrealloc *pre = nullptr;                   // SAM text: the output file, created early and being preallocated; may be null
     bk_sam_prep *sam_prep = nullptr;              // the device formatter's head start (bk_sam_prepare), consumed or freed by report_text / report_bam

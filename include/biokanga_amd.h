@@ -239,6 +239,7 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "chunk_reads" (reads per pass over the phases)   "max_read_len"   "site_chunk" (requests bk_site_octamers stages at a time)
  *   "primer_chunk" (requests bk_primer_correct stages at a time; "primer_buf_bytes": what its staging holds now, read only)
  *   "constraint_chunk" (requests bk_constraints_check stages at a time)
+ *   "samtag_chunk" (requests bk_samtags stages at a time; "samtag_buf_bytes": what its staging holds now, read only)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -679,6 +680,46 @@ void bk_sam_prep_free(bk_sam_prep *prep);
 int  bk_sam_prep_wait(bk_sam_prep *prep);
 typedef int (*bk_sam_sink)(void *user, const char *text, uint64_t n_bytes, uint64_t text_offset);
 int  bk_sam_format(bk_ctx *ctx, const bk_sam_job *job, bk_sam_sink sink, void *user, uint64_t *n_reported, uint64_t *n_bytes);
+
+/* ---- NM:i and MD:Z of SAM records (--sam-tags) ----------------------------------------------------------------------
+ * The reference writes neither; consumers want both.  The tags are a literal walk of the line as written - what any SAM consumer would
+ * compute from it - against the sequence AS INDEXED (codes a c g t n of the .sfx, the lower-case flag gone; the indexer turns every 13th
+ * N of a long N run into a random base, so the FASTA may differ):
+ *   the record's POS, CIGAR and SEQ (SEQ already reverse complemented for '-'); S and I consume SEQ only, N and D the target only, M
+ *   both, base by base.  An M base matches when SEQ's letter equals the target's and is one of ACGT; an N on either side mismatches.
+ *   NM:i = mismatching M bases + all I bases + all D bases.
+ *   MD:Z = [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*: run lengths always written (0 at either end and between adjacent mismatches), a mismatch
+ *   writes the target's letter, D writes ^ and the deleted target letters; N, I and S write nothing and a match run continues across them.
+ * A record whose CIGAR is not a well-formed walk - a number <= 0, a walk that does not consume exactly SEQ, or one that leaves its
+ * sequence - gets no tags (nor does one whose NM would not fit 16 bits).  The CIGAR is [c5 S] m M [c3 S] [gap N|I|D m2 M], the only
+ * shape the writers make. */
+#define BK_SAMTAG_NM 1
+#define BK_SAMTAG_MD 2
+#define BK_SAMTAG_NONE 0xFFFFu     /* the NM answer of a request without tags */
+typedef struct bk_samtag_req {
+    uint64_t read_ofs;           /* the read's first base in `bases` (a byte per base as loaded, code in the low three bits) */
+    uint32_t chrom_id;           /* RNAME's EntryID                                                          */
+    uint32_t pos;                /* 0-based position of the first M base in that sequence (POS - 1)         */
+    uint16_t read_len;           /* bases of the read = letters of SEQ                                       */
+    uint8_t  strand;             /* '+' | '-': for '-' SEQ is the read reverse complemented                  */
+    uint8_t  gop;                /* 0: one M run; 'N' | 'I' | 'D': the operation in front of the second       */
+    uint16_t c5, m, c3, m2;      /* [c5 S] m M [c3 S] [gap gop m2 M]; m2 is ignored without gop              */
+    int32_t  gap;
+} bk_samtag_req;                 /* 32 bytes */
+/* host arrays, blocking; in chunks of "samtag_chunk" requests through staging the context owns (made by the first call: a run without
+ * the option allocates nothing; "samtag_buf_bytes", read only, says what it holds).  nm_out[i] = NM of request i or BK_SAMTAG_NONE;
+ * md_ofs[0..n] = where request i's MD text starts in md_text (md_ofs[n] = all of it; a request without tags has none), no terminators.
+ * md_ofs == NULL and md_text == NULL: NM alone.  *md_needed (may be NULL) = the bytes of all MD text; when md_cap is smaller the call
+ * returns BK_ERR_MEM and has written nothing but *md_needed.  A request whose sequence does not exist, whose read leaves `bases`
+ * (n_bases bytes) or whose walk is malformed answers "no tags" for itself only.  BK_ERR_PARAMS, before anything is launched: a NULL
+ * array, one of md_ofs / md_text without the other, a strand other than '+' / '-'. */
+int  bk_samtags(bk_ctx *ctx, const bk_samtag_req *reqs, uint64_t n, const uint8_t *bases, uint64_t n_bases, uint16_t *nm_out,
+                uint64_t *md_ofs, char *md_text, uint64_t md_cap, uint64_t *md_needed);
+/* bk_sam_format with the tags of the mask `tags` (BK_SAMTAG_NM | BK_SAMTAG_MD) inside the lines of accepted records:
+ * ...QUAL\tNM:i:<n>\tMD:Z:<s>\n, only the tags asked for, NM first; measured in the measuring pass and written in the writing pass of
+ * the formatter.  A record without tags (see above) and the lines of unaccepted reads are as bk_sam_format writes them; tags == 0 IS
+ * bk_sam_format.  BK_ERR_PARAMS: bits beyond the two. */
+int  bk_sam_format_tags(bk_ctx *ctx, const bk_sam_job *job, uint32_t tags, bk_sam_sink sink, void *user, uint64_t *n_reported, uint64_t *n_bytes);
 
 /* ---- test hook: the search stage on its own ------------------------------------------------------------------------
  * LocateFirstExact / LocateLastExact (SfxArrayV2.cpp:7765-7876, :7914-8027) are two kernels here (k-mer table + key arrays, bk_search.hip); to
