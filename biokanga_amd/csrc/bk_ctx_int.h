@@ -131,6 +131,7 @@ struct bk_ctx {
     double swin_covered = 0;  // .. share of the suffix array it holds
     bool swin_denied = false; // it did not fit beside a batch's scratch when first asked for
     bool swin_rebuilt = false; // a batch has already made the partial array again for its own core lengths (maybe_build_swin does that once)
+    int prep_search0 = 1;    // the fused read preparation also runs phase 0's pass A where it can (prep_search0_on, bk_engine_int.h)
     int iv_poison = 0;       // test hook: the interval records a phase can use are filled with ones in front of its search (a slot read but not written shows)
     int use_wave = 1;        // 1: k_light / k_wave for reads <= 256 bp, 0: k_extend / k_heavy only
     int lazy_search = 1;     // 1: small k-mer buckets are handed to the extend kernels unverified
@@ -176,6 +177,7 @@ struct bk_ctx {
     int dbg_stop_phase = -1, dbg_phase = 0, dbg_cur = 0;
     uint32_t dbg_n = 0, dbg_ivc = 0;
     bool dbg_valid = false;
+    bool dbg_by_read = false;       // the stopped phase's interval slots go by read number (bk_iv_slot.h)
     bool debug = false;      // BK_DEBUG in the environment when the context was created: per-phase counts on stderr
     uint32_t chunk_reads = 64u << 20;
     uint64_t site_chunk = 8u << 20;       // bk_site_octamers stages this many requests at a time ("site_chunk")

@@ -3,6 +3,7 @@
 // Host-side helpers that more than one kernel file needs (stripe capacity, list compaction, row expansion) are declared at the end.
 #pragma once
 #include "bk_device.h"
+#include "bk_iv_slot.h"
 
 namespace bk {
 
@@ -73,10 +74,11 @@ __device__ __forceinline__ RdRow read_row(const DevBatch &b, uint32_t r, int str
 // core interval slot of (read, strand, core): [strand][core][a], a = the read's position in the phase's ACTIVE list (DevBatch::act),
 // so that lanes working on neighbouring active reads touch neighbouring words in every phase - indexed by read number, a later
 // phase found one record in two to four of a line still in use.  The records live for one phase: written by its search passes,
-// read by its extend kernels (which reach a read of the wave list through its position, act[a]).
-__device__ __forceinline__ uint64_t iv_slot(const DevBatch &b, uint32_t a, int st, int c)
+// read by its extend kernels (which reach a read of the wave list through its position, act[a]).  Where DevBatch::iv_by_read is set the
+// read's number r takes the position's place (bk_iv_slot.h); every caller has both.
+__device__ __forceinline__ uint64_t iv_slot(const DevBatch &b, uint32_t a, uint32_t r, int st, int c)
 {
-    return (uint64_t)(st * (int)b.iv_cores + c) * b.iv_stride + a;
+    return iv_slot_at(b.iv_cores, b.iv_stride, iv_index(b.iv_by_read, a, r), st, c);
 }
 
 // core interval records.  4-byte indexes keep {start, count} of a slot in ONE 8-byte word (b.iv2), so every
@@ -392,11 +394,12 @@ void launch_fill_u64(unsigned long long *p, uint64_t n, unsigned long long v, hi
 // 4-bit rows of both strands for every read of the batch (general kernel family, paired-end kernels): k_pack_reads (+ the exceptions
 // of a packed batch), bk_prep.hip
 void launch_pack_rows(const DevBatch &b, hipStream_t s, const uint32_t *pairs = nullptr, uint32_t n_pairs = 0);
-struct CompactJobs { StripeSet set; uint32_t *dense[3]; uint32_t *total[3]; uint32_t *max_out; int n; };
+struct CompactJobs { StripeSet set; uint32_t *dense[3]; uint32_t *total[3]; uint32_t cap[3]; uint32_t *max_out; int n; };      // cap: entries per stripe, list by list
 // capacity of one stripe of a list that `blocks` blocks append at most `per_block` entries each to (bk::StripeSet)
 inline uint32_t stripe_cap(unsigned blocks, unsigned per_block) { return ((blocks + kListStripes - 1) / kListStripes) * per_block; }
 // the stripes of up to three lists -> their dense forms (bk_prep.hip)
-void launch_compact(const StripeSet &set, uint32_t *const *dense, uint32_t *const *total, int n, uint32_t *max_out, hipStream_t s);
+// (caps: a stripe capacity per list where the lists' stripes differ in it; null: set.cap for all)
+void launch_compact(const StripeSet &set, uint32_t *const *dense, uint32_t *const *total, int n, uint32_t *max_out, hipStream_t s, const uint32_t *caps = nullptr);
 // 4-bit rows for the reads of `list` in a lean batch (bk_prep.hip)
 void expand_rd4(const DevBatch &b, const uint32_t *list, uint32_t n_list, hipStream_t s);
 

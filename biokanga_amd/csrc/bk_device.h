@@ -164,7 +164,9 @@ struct DevBatch {
     uint64_t *iv_first;         // core intervals [strand][core][read]: start (suffix array index) ...
     uint32_t *iv_n;             // ... and count | flags - separate arrays only for 5-byte indexes
     uint2 *iv2;                 // 4-byte indexes: {start, count | flags} in one word; then iv_first/iv_n are null
-    uint32_t iv_stride;         // records per (strand, core) plane of the interval arrays in this phase = length of its active list
+    uint32_t iv_stride;         // records per (strand, core) plane of the interval arrays in this phase = the chunk's reads (no active list is longer)
+    uint32_t iv_by_read;        // this phase's slots go by read number, not by position in the active list (bk_iv_slot.h): phase 0 behind a read
+                                //   preparation that searched
     const uint32_t *act;        // the phase's active list (read numbers): interval records and the wave list are indexed by position in it
     uint32_t *wave_work;        // per read: candidates the wave kernel will walk (sum of its core intervals), left by k_flat when it hands the read on; may be null
     uint2 *iv32;                // [strand][read]: suffix array interval of the read's first k + 16 bases {start, count; count 0xffffffff = not known},
@@ -195,6 +197,8 @@ struct PhaseCtl {
     uint32_t n_deep;            // work items pass B handed to k_search_deep ("search_split")
     uint32_t pad[8];
 };
+// the searching form of the fused read preparation (bk_prep.hip): phase 0's pass A inside it; its work items for pass B go through `stage` into `list`
+struct PrepSearch0 { const DevIndex *ix; int lazy; uint32_t *list, *list_cnt, *stage; };
 constexpr int kMaxPhases = 72;          // AlignReads runs at most MaxTotMM + 2 <= 65 LocateCoreMultiples calls (cMaxTotAllowedSubs 63)
 
 struct HeavyScratch {

@@ -6,6 +6,7 @@
 // Ownership: every buffer this file grows is a bk::DevBuf of bk_ctx::buf (bk_devbuf.h, bk_ctx_int.h) and is grown by one ensure_* function
 // here; a chunk's temporaries are local DevBufs, so an early return frees them.  Nothing here frees device memory by hand.
 #include "bk_engine_int.h"
+#include "bk_iv_slot.h"
 #include "bk_plan_table.h"
 #include "bk_wave_form.h"
 
@@ -441,8 +442,21 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                              !c->debug && c->async_phases;
     const bool check_maxlen = !tm.on;                 // (a call that only enqueues: its caller named the longest read, nobody has looked)
     if (check_maxlen) launch_max_len(b.lens, n, P(kMaxPhases + 1) + 0, s);
+    b.iv_stride = n;                               // interval records: a plane per (strand, core), a record per read of the chunk in each
+    // "prep_search0": the fused read preparation also runs phase 0's pass A - one core per strand pass, probed from the bases its lanes
+    // hold - and leaves pass B's work list; that phase's records then go by read number (DevBatch::iv_by_read)
+    const bool search0 = bk::prep_search0_on(c, reg_path, cores_fit, cmax_bound[0]);
+    const int lazy0 = (reg_path && c->lazy_search) ? 1 : 0;
+    PrepSearch0 ps0{&c->ix, lazy0, nullptr, P(0) + 2, nullptr};
+    if (search0) {
+        { int rs = ensure_slist(c, (uint64_t)n * (uint64_t)nstr, s); if (rs) return rs; }
+        ps0.list = m.slist.get();
+        ps0.stage = m.slist_stage.get();
+        b.iv_by_read = 1;
+        if (c->iv_poison) launch_clear_iv(b, nullptr, n, 1, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
+    }
     hipEvent_t e0 = tm.begin(s);
-    launch_prep(c->cfg, b, d_act[0], P(0) + 0, P(0) + 1, d_stage[0], d_stripe_cnt, s);
+    launch_prep(c->cfg, b, d_act[0], P(0) + 0, P(0) + 1, d_stage[0], d_stripe_cnt, s, search0 ? &ps0 : nullptr);
     HIP_TRY(hipGetLastError());
     tm.end(Span::Prep, e0, s);
     uint32_t n_act = n;
@@ -466,11 +480,12 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         tm.end(Span::Heavy, eb, s);
         n_act = 0;
     }
-    b.iv_stride = n;                               // interval records and the wave list go by position in the phase's active list
     if (no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe of the wave kernel
     for (int phase = 0; no_readback ? phase < max_phases : n_act > 0; phase++) {
         const uint32_t *ext_list = d_act[cur];
         b.act = ext_list;
+        const bool searched = search0 && phase == 0;       // pass A of this phase ran inside the read preparation
+        b.iv_by_read = searched ? 1u : 0u;                 // (every later phase: by position in its active list)
         if (no_readback) cmax = cmax_bound[phase];
         const uint32_t n_bound = n_act;            // (no read-back: the chunk's size; else the list's length)
         uint32_t *ctl_p = P(phase), *ctl_n = P(phase + 1);
@@ -484,12 +499,14 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
                 // (no clearing of the interval records: pass A stores the slot of every core a read has, empty results included, or hands
                 // it to pass B, which stores it on every path; the consumers never look at a core the read does not have.  "iv_poison"
                 // puts ones into the slots this phase can use, so that a slot read without having been written shows.)
-                if (c->iv_poison) launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
-                hipEvent_t ea = tm.begin(s);
-                launch_search_a(c->ix, c->cfg, b, d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, d_slist, ctl_p + 2,
-                                m.slist_stage.get(), d_stripe_cnt, s);
-                HIP_TRY(hipGetLastError());
-                tm.end(Span::SearchA, ea, s);
+                if (!searched) {
+                    if (c->iv_poison) launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
+                    hipEvent_t ea = tm.begin(s);
+                    launch_search_a(c->ix, c->cfg, b, d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, d_slist, ctl_p + 2,
+                                    m.slist_stage.get(), d_stripe_cnt, s);
+                    HIP_TRY(hipGetLastError());
+                    tm.end(Span::SearchA, ea, s);
+                }
                 // pass B's work list, grouped by k-mer bucket: the sort's size is the list's length when that was read back, else what
                 // the previous chunk's phase needed (plus a margin; capped at the sort buffers)
                 uint64_t n_slist_bound = lanes;
@@ -533,7 +550,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         if (phase == c->dbg_stop_phase) {
             // (test hook, bk_debug_intervals: the interval records the search of this phase wrote stay where they are; nothing of the
             // phase's extension or of the phases behind it runs, so the batch's result records are not to be used)
-            c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = phase; c->dbg_valid = true;
+            c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = phase; c->dbg_by_read = searched; c->dbg_valid = true;
             break;
         }
         hipEvent_t e2 = tm.begin(s);
@@ -599,7 +616,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         if (phase > 70) return BK_ERR_INTERNAL;
     }
     if (c->dbg_stop_phase >= 0 && !c->dbg_valid) {       // (no read reached that phase: an empty list - ctl[kMaxPhases] is never written)
-        c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = kMaxPhases; c->dbg_valid = true;
+        c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = kMaxPhases; c->dbg_by_read = false; c->dbg_valid = true;
     }
     if (no_readback) {
         // what the phases needed goes to the host on its own time: it sizes the next chunk's sorts (and says whether a read was handed to the
@@ -1189,14 +1206,16 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
         const int n = core_offsets(len, cl, cd, p.max_slides, dummy, 0);
         nc[a] = n <= kMaxCoresFast ? (uint32_t)n : 0u;
     }
+    // (a phase whose slots go by read - bk_iv_slot.h; 4-byte indexes only - is handed out by position all the same)
+    const bool by_read = c->dbg_by_read && c->buf.iv2.get() != nullptr;
     std::vector<uint2> h2;
-    if (c->buf.iv2.get()) h2.resize(na);
+    if (c->buf.iv2.get()) h2.resize(by_read ? stride : na);
     for (uint32_t pl = 0; pl < planes; pl++) {
         uint64_t *f = first + (size_t)pl * na;
         uint32_t *q = count + (size_t)pl * na;
         if (c->buf.iv2.get()) {
-            HIP_TRY(hipMemcpy(h2.data(), c->buf.iv2.get() + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
-            for (uint32_t a = 0; a < na; a++) { f[a] = h2[a].x; q[a] = h2[a].y; }
+            HIP_TRY(hipMemcpy(h2.data(), c->buf.iv2.get() + (size_t)pl * stride, h2.size() * 8, hipMemcpyDeviceToHost));
+            for (uint32_t a = 0; a < na; a++) { const uint2 v = h2[iv_index(by_read, a, act[a])]; f[a] = v.x; q[a] = v.y; }
         } else {
             HIP_TRY(hipMemcpy(f, c->buf.iv_first.get() + (size_t)pl * stride, (size_t)na * 8, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(q, c->buf.iv_n.get() + (size_t)pl * stride, (size_t)na * 4, hipMemcpyDeviceToHost));

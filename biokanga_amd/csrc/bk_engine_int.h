@@ -53,7 +53,7 @@ void launch_snp_sites(const DevIndex &ix, const uint32_t *planes, uint64_t g0, u
 void launch_count_seqs(const bk_hit *out, uint32_t n, const uint32_t *id2idx, uint32_t n_ent, unsigned long long *counts, hipStream_t s);
 void launch_fill_u64(unsigned long long *p, uint64_t n, unsigned long long v, hipStream_t s);
 void launch_prep(const DevAlignCfg &cfg, const DevBatch &b, uint32_t *act, uint32_t *act_cnt, uint32_t *cmax, uint32_t *stage,
-                 uint32_t *stripe_cnt, hipStream_t s);
+                 uint32_t *stripe_cnt, hipStream_t s, const PrepSearch0 *s0 = nullptr);
 void launch_search(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
                    int phase, int cmax, int nstr, int lazy, hipStream_t s);
 void launch_extend(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
@@ -140,6 +140,15 @@ inline uint32_t iv_cores_for(const bk_ctx *c, uint32_t maxlen)
 // whether pass B runs as two launches ("search_split"): the knob when somebody set it, else wherever pass B's work list is not grouped - on
 // a grouped list a repeat family's items lie side by side already
 inline bool search_split_on(const bk_ctx *c) { return c->search_split_set ? c->search_split != 0 : !(c->sort_lists & 1); }
+
+// whether the read preparation also runs phase 0's pass A ("prep_search0"): the register-window path with its fused preparation, the
+// second-level keys behind a two-word k-mer table, 4-byte elements, every read's cores within kMaxCoresFast and none with a second core in
+// phase 0 (cmax0: the most phase-0 cores a read of the batch can have), not under -N
+inline bool prep_search0_on(const bk_ctx *c, bool reg_path, bool cores_fit, int cmax0)
+{
+    return c->prep_search0 && reg_path && c->ix.k2 != nullptr && c->ix.ktab2 != nullptr && c->ix.sa_hi == nullptr && c->buf.iv2.get() != nullptr &&
+           cores_fit && cmax0 == 1 && !c->params.best_matches;
+}
 
 // 64-bit words of a read's 2 bit/base row in the register-window kernel family that takes reads of up to maxlen bases
 inline uint32_t rd2w_for(uint32_t maxlen)

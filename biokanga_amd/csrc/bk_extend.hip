@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) k_extend(DevIndex ix, DevAlignCfg cfg, De
         if (!is_heavy)
             for (int st = s0; st <= s1; st++)
                 for (int c = 0; c < nc; c++)
-                    if (iv_count(b, iv_slot(b, a, st, c)) > (uint32_t)cfg.heavy_thresh) is_heavy = true;
+                    if (iv_count(b, iv_slot(b, a, r, st, c)) > (uint32_t)cfg.heavy_thresh) is_heavy = true;
         if (is_heavy) {
             heavy[atomicAdd(heavy_cnt, 1u)] = r;
         } else {
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) k_extend(DevIndex ix, DevAlignCfg cfg, De
                 const uint64_t *rdw = b.rd4 + ((uint64_t)r * 2 + st) * b.wpr;
                 for (int c = 0; c < nc && !done; c++) {
                     n_search++;
-                    uint64_t slot = iv_slot(b, a, st, c);
+                    uint64_t slot = iv_slot(b, a, r, st, c);
                     uint32_t n;
                     uint64_t first;
                     iv_get(b, slot, first, n);
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
                 sv[u] = make_uint2(0, 0);
                 if (spec && u < slots_max) {
                     const int sti = u >= cmaxs ? 1 : 0;
-                    sv[u] = b.iv2[iv_slot(b, a, s0 + sti, u - sti * cmaxs)];
+                    sv[u] = b.iv2[iv_slot(b, a, r, s0 + sti, u - sti * cmaxs)];
                 }
             }
         }
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
                     const int sti = q >= cmaxs ? 1 : 0, c = q - sti * cmaxs;
                     uint64_t f64 = 0;
                     uint32_t cnt = 0;
-                    if (c < nc) iv_get(b, iv_slot(b, a, s0 + sti, c), f64, cnt);
+                    if (c < nc) iv_get(b, iv_slot(b, a, r, s0 + sti, c), f64, cnt);
                     if (cnt & kLazyFlag) lazy_bits |= 1u << (q & 31);
                     if ((cnt & kElemFlag) && cf) lazy_bits |= 0x10000u << q;       // (cf: at most sixteen slots; else the evaluation reads the records again)
                     cnt &= ~kIvFlags;
@@ -366,7 +366,8 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
                     else {
                         const int sti = q >= cmaxs ? 1 : 0;
                         uint32_t iv_c;
-                        iv_get(b, iv_slot(b, blockIdx.x * blockDim.x + ri, s0 + sti, q - sti * cmaxs), iv_f, iv_c);
+                        const uint32_t a_ri = blockIdx.x * blockDim.x + ri;
+                        iv_get(b, iv_slot(b, a_ri, iv_index_read(b.iv_by_read, a_ri, act), s0 + sti, q - sti * cmaxs), iv_f, iv_c);
                         lazy = (iv_c & kLazyFlag) != 0;
                         elem = (iv_c & kElemFlag) != 0;
                     }
@@ -644,8 +645,8 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
             const int sti = best_q >= cmaxs ? 1 : 0, c = best_q - sti * cmaxs, st = s0 + sti;
             const int last = len - cl;
             const int ofs = c * cd < last ? c * cd : last;
-            const uint64_t bf = cf ? (uint64_t)s_first[t * slots_max + best_q] : iv_start(b, iv_slot(b, a, st, c));
-            const bool belem = cf ? ((s_lazy[t] >> (16 + best_q)) & 1) != 0 : (iv_count(b, iv_slot(b, a, st, c)) & kElemFlag) != 0;
+            const uint64_t bf = cf ? (uint64_t)s_first[t * slots_max + best_q] : iv_start(b, iv_slot(b, a, r, st, c));
+            const bool belem = cf ? ((s_lazy[t] >> (16 + best_q)) & 1) != 0 : (iv_count(b, iv_slot(b, a, r, st, c)) & kElemFlag) != 0;
             hit_left = SMALL ? (uint64_t)my_hit_t : (belem ? bf : sa_get<WIDE>(ix, bf + best_j)) - (uint64_t)ofs;
             hit_strand = st ? '-' : '+';
             if (ent_lds) {

@@ -1107,6 +1107,7 @@ int bk_ctx_clone(bk_ctx **out, const bk_ctx *src, int device_id)
     c->use_k3 = src->use_k3;
     c->sort_lists = src->sort_lists; c->sort_lists_set = src->sort_lists_set;
     c->search_split = src->search_split; c->search_split_set = src->search_split_set;
+    c->prep_search0 = src->prep_search0;
     c->grow_enabled = src->grow_enabled && src->grow_state.load() != 4; c->grow_after = src->grow_after; c->grow_wait = src->grow_wait;       // (a clone of a grown context has what it grew)
     c->use_ktab = src->use_ktab; c->k_req = src->k_req; c->use_k2 = src->use_k2; c->use_isa = src->use_isa; c->use_wave = src->use_wave; c->use_tgt2 = src->use_tgt2;
     c->ix.n = src->ix.n;

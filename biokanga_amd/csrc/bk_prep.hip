@@ -1,7 +1,7 @@
 // bk_prep.hip - read preparation (gfx950): CSeqTrans::ReverseComplement (SeqTrans.cpp:458-512) + the N policy of ProcCoredApprox
 // (Aligner.cpp:9041-9063) + the first active list, from 1 byte/base reads or from packed 2 bit/base words; the checks of a packed
 // batch; the compaction of striped work lists; 4-bit rows for the reads a general-family kernel is handed.
-#include "bk_dev_util.h"
+#include "bk_dev_search_a.h"
 #include "bk_plan_table.h"
 
 namespace bk {
@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) k_compact_lists(CompactJobs J)
             const int mid = (lo + hi + 1) >> 1;
             if (s_pre[mid] <= i) lo = mid; else hi = mid - 1;
         }
-        dense[old + i] = stage[(uint64_t)lo * J.set.cap + (i - s_pre[lo])];
+        dense[old + i] = stage[(uint64_t)lo * J.cap[li] + (i - s_pre[lo])];
     }
 }
 
@@ -146,7 +146,9 @@ __device__ __forceinline__ void revcomp2(const uint64_t (&f)[W], int len, uint64
 }
 
 // exceptions of a packed batch, one lane each.  k_mark_exc counts them into the reads' meta words BEFORE the read preparation runs
-// (bits 16..30: N bases, bit 31: a code the reference refuses - what the N policy needs to know); k_exc_rows gives the reads that
+// (bits 16..30: N bases, bit 31: a code the reference refuses - what the N policy needs to know) and leaves the number of a read's first
+// exception in the first two words of its result record, which nobody has written yet and the preparation writes last: its searching form
+// walks the read's exceptions from there (search0_nfields); k_exc_rows gives the reads that
 // have one their 4-bit rows (lean batches; widened from the 2-bit rows), k_apply_exc then writes the codes into the rows of both strands
 __global__ void __launch_bounds__(256) k_mark_exc(DevBatch b)
 {
@@ -157,6 +159,7 @@ __global__ void __launch_bounds__(256) k_mark_exc(DevBatch b)
     if (rr >= b.n_reads) return;
     if (e.code == 4) atomicAdd(&b.rmeta[rr], ((uint32_t)e.run + 1u) << 16);
     else atomicOr(&b.rmeta[rr], 1u << 31);
+    if (i == 0 || b.pk_exc[i - 1].read != e.read) { b.out[rr].chrom_id = (uint32_t)i; b.out[rr].match_loci = (uint32_t)(i >> 32); }
 }
 
 __global__ void __launch_bounds__(256) k_exc_rows(DevBatch b)
@@ -325,24 +328,57 @@ __global__ void __launch_bounds__(256) k_pack_reads(DevBatch b, const uint32_t *
 #ifndef BK_PREP_TRANSPOSE
 #define BK_PREP_TRANSPOSE 1
 #endif
-template <int NW, bool PACKED>
-__global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b, StripeSet out)
+
+// The searching form (SEARCH0) also runs phase 0's pass A for the reads it lets through: core 0 of each strand pass (the engine takes this
+// form only where no read of the batch has a second core in phase 0), probed from the bases the lane holds - never from the rows it
+// stores, which leave through other lanes - through the stages of bk_dev_search_a.h.  Records go to slots numbered by READ
+// (DevBatch::iv_by_read: the lane does not know where the list's compaction will put its read), slots for pass B to the stripes of `wl`
+// as list 1, by block as the active list is.
+
+// fields lo .. hi (0 <= lo <= hi <= 31) of a word of 32 2-bit fields, first field in the top bits: the low bit of each
+__device__ __forceinline__ uint64_t n_fields(int lo, int hi)
 {
-    __shared__ uint32_t s_cnt, s_base, s_cmax;
+    return (~0ULL >> (2 * lo)) & (~0ULL << (62 - 2 * hi)) & 0x5555555555555555ULL;
+}
+// which of the first 32 bases of 4-bit words w0, w1 are not a,c,g,t, as such fields
+__device__ __forceinline__ uint64_t n_fields_of(uint64_t w0, uint64_t w1)
+{
+    return ((uint64_t)squeeze2((w0 >> 2) & 0x1111111111111111ULL) << 32) | squeeze2((w1 >> 2) & 0x1111111111111111ULL);
+}
+// the same for a read of a packed batch, whose words say nothing about its N: from its exceptions, the first of which k_mark_exc named.
+// nf: the read's first 32 bases, nr: its reverse complement's
+__device__ __forceinline__ void search0_nfields(const DevBatch &b, uint32_t r, int len, uint64_t first_exc, uint64_t &nf, uint64_t &nr)
+{
+    const uint32_t me = r + b.pk_read0;
+    for (uint64_t j = first_exc; j < b.pk_nexc; j++) {
+        const bk_nbase e = b.pk_exc[j];
+        if (e.read != me) break;
+        const int lo = (int)e.pos, hi = (int)e.pos + (int)e.run;
+        if (lo < 32) nf |= n_fields(lo, hi < 31 ? hi : 31);
+        const int rl = len - 1 - hi, rh = len - 1 - lo;             // (checked batches: hi < len)
+        if (rl < 32 && rh >= 0) nr |= n_fields(rl > 0 ? rl : 0, rh < 31 ? rh : 31);
+    }
+}
+
+template <int NW, bool PACKED, bool SEARCH0>
+__global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b, StripeSet out, DevIndex ix, int lazy, StripeSet wl)
+{
+    __shared__ uint32_t s_cnt, s_base, s_cmax, s_cnt2, s_base2;
     // TR: rows and result records leave through the wave's words of LDS (see the kernel's end): reads of up to 128 bases
     constexpr bool TR = NW == 8 && BK_PREP_TRANSPOSE;
     __shared__ uint4 s_tr[TR ? 4 : 1][TR ? 64 * (NW / 2) : 1];
     extern __shared__ uint2 s_plan[];                               // phase 0's row of the plan table (bk_plan_table.h): b.plan_n <= 16 NW + 1 entries
     plan_stage(s_plan, b, 0, threadIdx.x, 256);
-    if (threadIdx.x == 0) { s_cnt = 0; s_cmax = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0; s_cmax = 0; s_cnt2 = 0; }
     __syncthreads();
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     const bool lean = b.rd2 != nullptr;
     const int wv = threadIdx.x >> 6;
     const bool wave_full = (r | 63u) < b.n_reads;                    // every lane of this wave has a read
-    bool go = false, has_n = false;
+    bool go = false, has_n = false, srch = false;
     uint32_t my_cmax = 0;
-    int len = 0;
+    int len = 0, cl0 = 1;
+    uint64_t first_exc = 0;                                         // (SEARCH0, PACKED: where the read's exceptions start)
     uint64_t fw[PACKED ? 1 : NW], rv[PACKED ? 1 : NW];              // 4 bit/base rows (1 byte/base input)
     uint64_t f2[NW / 2], r2[NW / 2];                                // 2 bit/base rows
     bk_hit h;
@@ -368,6 +404,7 @@ __global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b,
             const uint32_t pre = b.rmeta[r];                        // k_mark_exc: what the exception list holds for this read
             num_ns = (int)((pre >> 16) & 0x7FFFu);
             bad = (pre >> 31) != 0;
+            if (SEARCH0 && pre != 0) first_exc = ((uint64_t)b.out[r].match_loci << 32) | b.out[r].chrom_id;
         } else {
             // forward rows from the bytes; the reverse complement rows come from them by bit work (revcomp2) unless the read has an N
             // or the batch keeps 4-bit rows for every read - then the bytes are walked a second time from the other end
@@ -436,8 +473,50 @@ __global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b,
             if (g.n_phases > 0) {
                 if (g.nc <= kMaxCoresFast) my_cmax = (uint32_t)g.nc;
                 go = true;
+                srch = g.nc >= 1 && g.nc <= kMaxCoresFast;          // (pass A's test for core 0)
+                cl0 = g.cl;
             }
         }
+    }
+    // phase 0's pass A for core 0 of the read's strand passes.  A lane without a search goes round the look-ups: pa[].on stays off
+    PassACore pa[2];
+    uint32_t slot[2] = {0, 0}, cix[2] = {kNoIv32, kNoIv32}, my_off2[2] = {0, 0};
+    if (SEARCH0) {
+        const int k = ix.k;
+        pass_a_clear(pa[0]);
+        pass_a_clear(pa[1]);
+        if (srch) {
+            uint64_t nf = 0, nr = 0;                                // the N among each strand's first 32 bases
+            if (has_n) {
+                if (PACKED) search0_nfields(b, r, len, first_exc, nf, nr);
+                else { nf = n_fields_of(fw[0], fw[PACKED ? 0 : 1]); nr = n_fields_of(rv[0], rv[PACKED ? 0 : 1]); }
+            }
+            const int nstr = cfg.align_strand == 0 ? 2 : 1;
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                if (u < nstr) {
+                    const int strand = cfg.align_strand == 2 ? 1 : u;
+                    const uint64_t x = strand ? r2[0] : f2[0], nm = strand ? nr : nf;      // 32 bases from the core's start, offset 0
+                    pa[u].on = true;
+                    pa[u].cl = cl0;
+                    pa[u].p0 = spread2to4((uint32_t)(x >> 32)) & top_mask(cl0);
+                    pa[u].q2raw = k == 16 ? (uint32_t)x : (uint32_t)((x << (2 * k)) >> 32);
+                    // an N in the k-mer, or among the core's bases behind it that the second-level keys would take: the full search's
+                    const int rem2 = cl0 - k, nk = rem2 < kK2Bases ? rem2 : kK2Bases;
+                    uint64_t nbad = nm & (~0ULL << (64 - 2 * k));
+                    if (nk > 0) nbad |= (nm << (2 * k)) & (~0ULL << (64 - 2 * nk));
+                    if (nbad) pa[u].p0 |= 0x4000000000000000ULL;
+                    slot[u] = (uint32_t)iv_slot_at(b.iv_cores, b.iv_stride, r, strand, 0);
+                    if (b.iv32 != nullptr && cl0 >= k + kK2Bases) cix[u] = (uint32_t)strand * b.n_reads + r;
+                }
+            }
+        }
+        pass_a_table(ix, k, pa[0]);
+        pass_a_table(ix, k, pa[1]);
+        pass_a_keys(ix, k, lazy, pa[0]);
+        pass_a_keys(ix, k, lazy, pa[1]);
+        pass_a_result(k, lazy, pa[0]);
+        pass_a_result(k, lazy, pa[1]);
     }
     // the list append comes before the rows are written: its barriers wait for every store the wave has issued
     const int lane = threadIdx.x & 63;
@@ -450,11 +529,35 @@ __global__ void __launch_bounds__(256) k_prep_fused(DevAlignCfg cfg, DevBatch b,
         w = __builtin_amdgcn_readfirstlane(w);
         my_off = w + (uint32_t)__popcll(m & ((1ULL << lane) - 1));
     }
+    if (SEARCH0) {
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint64_t m2 = __ballot(pa[u].push);
+            if (m2) {
+                uint32_t w = 0;
+                if (lane == 0) w = atomicAdd(&s_cnt2, (uint32_t)__popcll(m2));
+                w = __builtin_amdgcn_readfirstlane(w);
+                my_off2[u] = w + (uint32_t)__popcll(m2 & ((1ULL << lane) - 1));
+            }
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0 && s_cnt) s_base = stripe_reserve(out, 0, s_cnt);
     if (threadIdx.x == 64 && s_cmax) stripe_max(out, s_cmax);
+    if (SEARCH0 && threadIdx.x == 128 && s_cnt2) s_base2 = stripe_reserve(wl, 1, s_cnt2);
     __syncthreads();
     if (go) stripe_put(out, 0, s_base + my_off, r);
+    if (SEARCH0) {
+        // every slot of a core the read has is stored, as pass A stores it: the record, or the work item pass B stores its result over
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            if (pa[u].push) stripe_put(wl, 1, s_base2 + my_off2[u], slot[u]);
+            if (pa[u].on) {
+                iv_put(b, slot[u], pa[u].first, pa[u].nval);
+                if (cix[u] != kNoIv32) b.iv32[cix[u]] = pa[u].leave;
+            }
+        }
+    }
     if (r < b.n_reads) {
         b.rmeta[r] = (uint32_t)len | (has_n ? kReadHasN : 0u);
         // 4 bit/base rows [read][strand][wpr] (zero padded, 16-byte aligned): every read of a batch without 2-bit rows; in lean
@@ -655,11 +758,11 @@ void launch_min_len(const uint32_t *lens, uint32_t n, uint32_t *out, hipStream_t
 }
 
 // the stripes of up to three lists -> their dense forms (appended behind total[i] entries; the counts and the maximum follow)
-void launch_compact(const StripeSet &set, uint32_t *const *dense, uint32_t *const *total, int n, uint32_t *max_out, hipStream_t s)
+void launch_compact(const StripeSet &set, uint32_t *const *dense, uint32_t *const *total, int n, uint32_t *max_out, hipStream_t s, const uint32_t *caps)
 {
     CompactJobs J;
     J.set = set;
-    for (int i = 0; i < 3; i++) { J.dense[i] = dense[i < n ? i : 0]; J.total[i] = total[i < n ? i : 0]; }
+    for (int i = 0; i < 3; i++) { J.dense[i] = dense[i < n ? i : 0]; J.total[i] = total[i < n ? i : 0]; J.cap[i] = caps ? caps[i < n ? i : 0] : set.cap; }
     J.max_out = max_out;
     J.n = n;
     hipLaunchKernelGGL(k_compact_lists, dim3(1024, (unsigned)n), dim3(256), 0, s, J);
@@ -676,8 +779,10 @@ void launch_pack_rows(const DevBatch &b, hipStream_t s, const uint32_t *pairs, u
 }
 
 // stage: at least n_reads + (kListStripes + 2) * 1024 entries; stripe_cnt: kListStripes * 16 words, zero between launches
+// s0 != nullptr: the searching form (register-kernel path only; b.iv_by_read set) - phase 0's pass A runs inside the fused kernel, whose
+// work items for pass B go through the stripes of s0->stage (at least strands x n_reads + (kListStripes + 2) * 1024 entries) into s0->list
 void launch_prep(const DevAlignCfg &cfg, const DevBatch &b, uint32_t *act, uint32_t *act_cnt, uint32_t *cmax, uint32_t *stage,
-                 uint32_t *stripe_cnt, hipStream_t s)
+                 uint32_t *stripe_cnt, hipStream_t s, const PrepSearch0 *s0 = nullptr)
 {
     const bool packed = b.pk_words != nullptr;
     const unsigned eblocks = (unsigned)((b.pk_nexc + 255) / 256);
@@ -688,22 +793,41 @@ void launch_prep(const DevAlignCfg &cfg, const DevBatch &b, uint32_t *act, uint3
         out.stage[0] = out.stage[1] = out.stage[2] = stage;
         out.cap = stripe_cap(blocks, 256);
         const size_t plan_lds = (size_t)b.plan_n * sizeof(uint2);       // phase 0's row of the plan table
+        StripeSet wl = out;                                              // (the searching form's second list: same counters, its own stripes)
+        DevIndex ix{};
+        int lazy = 0;
+        if (s0 != nullptr) {
+            wl.stage[0] = wl.stage[1] = wl.stage[2] = s0->stage;
+            wl.cap = stripe_cap(blocks, 256 * (cfg.align_strand == 0 ? 2 : 1));
+            ix = *s0->ix;
+            lazy = s0->lazy;
+        }
+#define PREP(NWV, PK) do { if (s0 != nullptr) hipLaunchKernelGGL((k_prep_fused<NWV, PK, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out, ix, lazy, wl); \
+                           else hipLaunchKernelGGL((k_prep_fused<NWV, PK, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out, ix, lazy, wl); } while (0)
         if (packed) {
             // the exception list first tells every read how many N it holds (the N policy is decided in the fused kernel), and
             // afterwards writes the codes into 4-bit rows: existing ones, or - lean batches - rows made for just these reads
             launch_fill_u64(reinterpret_cast<unsigned long long *>(b.rmeta), ((uint64_t)b.n_reads + 1) / 2, 0ULL, s);      // (rmeta is allocated in whole 8-byte words)
             if (eblocks) hipLaunchKernelGGL(k_mark_exc, dim3(eblocks), dim3(256), 0, s, b);
-            if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-            else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-            else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-            else hipLaunchKernelGGL((k_prep_fused<kNwLongest, true>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
+            if (b.nw == 8) PREP(8, true);
+            else if (b.nw == 16) PREP(16, true);
+            else if (b.nw == kNwLong) PREP(kNwLong, true);
+            else PREP(kNwLongest, true);
             if (eblocks && b.rd2 != nullptr) hipLaunchKernelGGL(k_exc_rows, dim3(eblocks), dim3(256), 0, s, b);
             if (eblocks) hipLaunchKernelGGL(k_apply_exc, dim3(eblocks), dim3(256), 0, s, b);
-        } else if (b.nw == 8) hipLaunchKernelGGL((k_prep_fused<8, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-        else if (b.nw == 16) hipLaunchKernelGGL((k_prep_fused<16, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-        else if (b.nw == kNwLong) hipLaunchKernelGGL((k_prep_fused<kNwLong, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-        else hipLaunchKernelGGL((k_prep_fused<kNwLongest, false>), dim3(blocks), dim3(256), plan_lds, s, cfg, b, out);
-        launch_compact(out, &act, &act_cnt, 1, cmax, s);
+        } else if (b.nw == 8) PREP(8, false);
+        else if (b.nw == 16) PREP(16, false);
+        else if (b.nw == kNwLong) PREP(kNwLong, false);
+        else PREP(kNwLongest, false);
+#undef PREP
+        if (s0 != nullptr) {
+            uint32_t *const dense[2] = {act, s0->list}, *const total[2] = {act_cnt, s0->list_cnt};
+            const uint32_t caps[2] = {out.cap, wl.cap};
+            StripeSet both = out;
+            both.stage[1] = s0->stage;
+            launch_compact(both, dense, total, 2, cmax, s, caps);
+        } else
+            launch_compact(out, &act, &act_cnt, 1, cmax, s);
         return;
     }
     launch_pack_rows(b, s);

@@ -5,7 +5,7 @@
 //   k_search_deep     pass B's tails in a launch of their own ("search_split"): suffix array + target behind the key levels, full searches
 #include <algorithm>
 
-#include "bk_dev_k2.h"
+#include "bk_dev_search_a.h"
 #include "bk_dev_prof.h"
 #include "bk_plan_table.h"
 
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) k_search(DevIndex ix, DevAlignCfg cfg, De
     int strand = cfg.align_strand == 2 ? 1 : si;
     const RdRow rdw = read_row(b, r, strand, (meta & kReadHasN) != 0);
     uint64_t first, count;
-    uint64_t slot = iv_slot(b, (uint32_t)a, strand, c);
+    uint64_t slot = iv_slot(b, (uint32_t)a, r, strand, c);
     if (lazy && ix.k > 0 && cl >= ix.k) {
         uint64_t p0 = rdw.nib16(my_ofs) & top_mask(cl);
         uint64_t lo, hi;
@@ -90,23 +90,18 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
   for (uint64_t tile0 = (uint64_t)blockIdx.x * (256 * ILP); tile0 < total; tile0 += (uint64_t)gridDim.x * (256 * ILP), item_advance(cur, ig)) {
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    bool on[ILP], push[ILP], have_code[ILP];
-    uint64_t slot[ILP], p0[ILP], first[ILP], lo[ILP], hi[ILP];
-    uint32_t nval[ILP], q2raw[ILP];            // q2raw: the 16 bases behind the k-mer's, 2 bits each
-    int cl[ILP];
+    PassACore pa[ILP];                  // the items of this lane, stage by stage (bk_dev_search_a.h)
+    uint64_t slot[ILP];
     // The core at offset 0 of phases 0, 1, 2 .. begins with the same k + 15 bases whenever it is that long, so the interval those bases
     // select is looked up once: phase 0 leaves it in iv32 (here, or pass B after its key bisection), the later phases' offset-0 lanes
     // take it from there instead of fetching a k-mer table line and a key line each (a quarter of the searches at C2).
-    constexpr uint32_t kNoIv32 = 0xFFFFFFFFu;
     uint32_t cix[ILP];                  // entry of iv32 this lane reads (phase > 0) or writes (phase 0); kNoIv32 = neither
-    uint2 cv[ILP];
-    bool cached[ILP];
-    uint32_t key0[ILP];
     // stage 1: the item, its read row
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
-        on[u] = false; push[u] = false; have_code[u] = false; slot[u] = 0; p0[u] = 0; q2raw[u] = 0; first[u] = 0; nval[u] = 0; cl[u] = 1; lo[u] = hi[u] = 0;
-        cix[u] = kNoIv32; cv[u] = make_uint2(0, kNoIv32); cached[u] = false;
+        pass_a_clear(pa[u]);
+        slot[u] = 0;
+        cix[u] = kNoIv32;
         uint64_t a;
         int si, c;
         item_decode(cur, threadIdx.x + (uint32_t)u * (uint32_t)stride, ig, a, si, c);
@@ -115,35 +110,35 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
             const uint32_t meta = b.rmeta[r];
             const int len = (int)(meta & kReadLenMask);
             const int strand_c = cfg.align_strand == 2 ? 1 : si;
-            if (b.iv32 != nullptr && c == 0 && phase > 0) cv[u] = b.iv32[(uint32_t)strand_c * b.n_reads + r];     // (requested with the length)
+            if (b.iv32 != nullptr && c == 0 && phase > 0) pa[u].cv = b.iv32[(uint32_t)strand_c * b.n_reads + r];     // (requested with the length)
             const PlanGeo g = plan_lookup(s_plan, b.plan_n, len);
             const int cd = g.cd, nc = g.nc;
-            cl[u] = g.cl;
+            pa[u].cl = g.cl;
             if (c < nc && nc <= kMaxCoresFast) {
-                on[u] = true;
-                if (b.iv32 != nullptr && c == 0 && cl[u] >= k + kK2Bases) {
+                pa[u].on = true;
+                if (b.iv32 != nullptr && c == 0 && pa[u].cl >= k + kK2Bases) {
                     cix[u] = (uint32_t)strand_c * b.n_reads + r;
                     // (a plain count, or the record of a bucket of one suffix handed on as it is - kElemFlag: the same bucket, the same suffix,
                     // whatever the core's length - where unverified buckets may be handed on at all)
-                    cached[u] = phase > 0 && cv[u].y != kNoIv32 && (cv[u].y < (1u << kKindShift) || (lazy && (cv[u].y & kIvFlags) == kIvFlags));
+                    pa[u].cached = phase > 0 && pa[u].cv.y != kNoIv32 && (pa[u].cv.y < (1u << kKindShift) || (lazy && (pa[u].cv.y & kIvFlags) == kIvFlags));
                 }
-                const int my_ofs = c * cd < len - cl[u] ? c * cd : len - cl[u];
+                const int my_ofs = c * cd < len - pa[u].cl ? c * cd : len - pa[u].cl;
                 const int strand = cfg.align_strand == 2 ? 1 : si;
-                slot[u] = iv_slot(b, (uint32_t)a, strand, c);
+                slot[u] = iv_slot(b, (uint32_t)a, r, strand, c);
                 if (b.rd2 != nullptr && !(meta & kReadHasN)) {
                     // 32 bases from the core's start out of the 2-bit row: the k-mer code's bases and the 16 that follow them
                     const uint64_t *row = b.rd2 + ((uint64_t)r * 2 + strand) * (b.nw / 2);
                     const uint64_t x = bits64_2(row, my_ofs);
-                    p0[u] = spread2to4((uint32_t)(x >> 32)) & top_mask(cl[u]);
-                    q2raw[u] = k == 16 ? (uint32_t)x : (uint32_t)(bits64_2(row, my_ofs + k) >> 32);
+                    pa[u].p0 = spread2to4((uint32_t)(x >> 32)) & top_mask(pa[u].cl);
+                    pa[u].q2raw = k == 16 ? (uint32_t)x : (uint32_t)(bits64_2(row, my_ofs + k) >> 32);
                 } else {
                     const uint64_t *rdw = b.rd4 + ((uint64_t)r * 2 + strand) * b.wpr;
-                    p0[u] = nib16(rdw, my_ofs) & top_mask(cl[u]);
+                    pa[u].p0 = nib16(rdw, my_ofs) & top_mask(pa[u].cl);
                     const uint64_t q4 = nib16(rdw, my_ofs + k);
-                    q2raw[u] = squeeze2(q4);
+                    pa[u].q2raw = squeeze2(q4);
                     // an N among the core's bases behind the k-mer cannot be put to the 2-bit keys: the full search takes the core
-                    const int rem2 = cl[u] - k;
-                    if (rem2 > 0 && (q4 & 0x4444444444444444ULL & top_mask(rem2 < kK2Bases ? rem2 : kK2Bases))) p0[u] |= 0x4000000000000000ULL;
+                    const int rem2 = pa[u].cl - k;
+                    if (rem2 > 0 && (q4 & 0x4444444444444444ULL & top_mask(rem2 < kK2Bases ? rem2 : kK2Bases))) pa[u].p0 |= 0x4000000000000000ULL;
                 }
             }
         }
@@ -151,97 +146,17 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
     PROFS(0);
     // stage 2: k-mer table
 #pragma unroll
-    for (int u = 0; u < ILP; u++) {
-        nval[u] = kKindFull << kKindShift;
-        push[u] = on[u];
-        have_code[u] = on[u] && !cached[u] && cl[u] >= k && !(p0[u] & 0x4444444444444444ULL & top_mask(k));
-        key0[u] = kK2Above;
-        if (have_code[u]) {
-            const uint64_t code = (uint64_t)(squeeze2(p0[u]) >> (32 - 2 * k));
-            if (ix.ktab2 != nullptr) {
-                // {bucket start, second-level key of its first suffix}: a bucket of one - every second one a read of a unique region
-                // meets, and a third of those its other strand runs into by chance - is settled by the line that names it
-                const uint2 e0 = ix.ktab2[code], e1 = ix.ktab2[code + 1];
-                lo[u] = e0.x; hi[u] = e1.x; key0[u] = e0.y;             // (a bucket of one: its key; a larger one: the map of its keys' first five bits)
-            } else {
-                ktab_get_pair(ix, code, lo[u], hi[u]);
-            }
-        }
-    }
+    for (int u = 0; u < ILP; u++) pass_a_table(ix, k, pa[u]);
     PROFS(1);
     // stage 3: small buckets from the key array
-    // (a lane loads the keys its bucket has - one to three for most - and no more: this kernel lives on the rate at which the
-    // texture path takes lane requests, and sixteen keys for every lane cost a third more time than the search saved)
-    uint32_t key[ILP][kInlineBucket];
-    bool absent[ILP];                   // the table's line says that no key of the bucket continues the way the core does
-    bool carry[ILP];                    // a bucket of one suffix whose table entry carries the suffix itself: handed on as it is (kElemFlag)
 #pragma unroll
-    for (int u = 0; u < ILP; u++) {
-        const uint64_t size = hi[u] - lo[u];
-        const uint32_t m = k2_mask(cl[u] - k);
-        absent[u] = have_code[u] && ix.ktab2 != nullptr && size >= 2 && ktab2_absent(key0[u], m, q2raw[u] & m);
-        carry[u] = have_code[u] && lazy && ix.ktab2 != nullptr && ix.ktab2_elem && size == 1;
-        const bool key_in_entry = size == 1 && ix.ktab2 != nullptr && !ix.ktab2_elem;
-#pragma unroll
-        for (uint32_t j = 0; j < kInlineBucket; j++)
-            key[u][j] = (have_code[u] && !absent[u] && !carry[u] && size <= kInlineBucket && j < size) ? (key_in_entry ? key0[u] : ix.k2[lo[u] + j]) : kK2Above;
-    }
+    for (int u = 0; u < ILP; u++) pass_a_keys(ix, k, lazy, pa[u]);
     PROFS(2);
     // stage 4: results
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
-        uint2 leave = make_uint2(0, kNoIv32);               // what phase 0 leaves in iv32 for this read and strand
-        if (cached[u] && (cv[u].y & kElemFlag)) {
-            // phase 0 met a bucket of one suffix here and handed the suffix on: so does this phase
-            first[u] = cv[u].x;
-            nval[u] = cv[u].y;
-            push[u] = false;
-        } else if (cached[u]) {
-            // the interval of the first k + 15 bases, as the bucket compare below would have produced it
-            first[u] = cv[u].x;
-            const uint32_t cnt = cv[u].y;
-            if (cnt == 0 || cl[u] <= k + kK2Bases) { nval[u] = cnt; push[u] = false; }
-            else if (lazy && cnt <= kLazyBucket) { nval[u] = cnt | kLazyFlag; push[u] = false; }
-            else nval[u] = cnt | (kKindDeep << kKindShift);
-        }
-        if (carry[u]) {
-            // (the table's line named the bucket and the suffix in it: no key line, no suffix array line - the window the extension fetches
-            // says whether the core is there)
-            first[u] = key0[u];
-            nval[u] = 1u | kIvFlags;
-            push[u] = false;
-            leave = make_uint2(key0[u], 1u | kIvFlags);
-        } else if (have_code[u]) {
-            const uint64_t size = hi[u] - lo[u];
-            if (size == 0 || absent[u]) { first[u] = lo[u]; nval[u] = 0; push[u] = false; leave = make_uint2((uint32_t)lo[u], 0u); }
-            else if (size <= kInlineBucket) {
-                const uint32_t m = k2_mask(cl[u] - k), q2 = q2raw[u] & m;
-                uint32_t lb = 0, ub = 0;
-                bool suspect = false;                          // a key of the N kind counted as equal: pass B has a look at the target
-#pragma unroll
-                for (uint32_t j = 0; j < kInlineBucket; j++) {
-                    const int cm = k2_cmp(key[u][j], m, q2);
-                    lb += cm < 0;
-                    ub += cm <= 0;
-                    suspect |= cm == 0 && k2_nkind(key[u][j]);
-                }
-                if (suspect) {
-                    first[u] = lo[u];
-                    nval[u] = (uint32_t)size | (kKindK2 << kKindShift);
-                } else {
-                    first[u] = lo[u] + lb;
-                    const uint32_t cnt = ub - lb;
-                    leave = make_uint2((uint32_t)first[u], cnt);
-                    if (cnt == 0 || cl[u] <= k + kK2Bases) { nval[u] = cnt; push[u] = false; }
-                    else if (lazy && cnt <= kLazyBucket) { nval[u] = cnt | kLazyFlag; push[u] = false; }
-                    else nval[u] = cnt | (kKindDeep << kKindShift);
-                }
-            } else if (size < (1ULL << kKindShift)) {
-                first[u] = lo[u];
-                nval[u] = (uint32_t)size | (kKindK2 << kKindShift);        // (pass B leaves the interval in iv32 after its key bisection)
-            }
-        }
-        if (phase == 0 && cix[u] != kNoIv32) b.iv32[cix[u]] = leave;
+        pass_a_result(k, lazy, pa[u]);
+        if (phase == 0 && cix[u] != kNoIv32) b.iv32[cix[u]] = pa[u].leave;
     }
     PROFS(3);
     // work-list appends, one global atomic per block.  The interval records are stored after them: the barriers of the append
@@ -255,7 +170,7 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
         my_off[u] = 0;
-        const uint64_t m = __ballot(push[u]);
+        const uint64_t m = __ballot(pa[u].push);
         if (m) {
             uint32_t w = 0;
             if (lane == 0) w = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
@@ -271,8 +186,8 @@ __global__ void __launch_bounds__(256) k_search_a_ilp(DevIndex ix, DevAlignCfg c
     PROFS(5);
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
-        if (push[u]) stripe_put_tile(out, 0, s_base + my_off[u], (uint32_t)slot[u], tile);
-        if (on[u]) iv_put(b, slot[u], first[u], nval[u]);
+        if (pa[u].push) stripe_put_tile(out, 0, s_base + my_off[u], (uint32_t)slot[u], tile);
+        if (pa[u].on) iv_put(b, slot[u], pa[u].first, pa[u].nval);
     }
     __syncthreads();                                        // (s_cnt / s_base are the next tile's, too)
   }
@@ -337,8 +252,8 @@ __global__ void __launch_bounds__(256) k_search_b(DevIndex ix, DevAlignCfg cfg, 
     uint32_t a;
     int strand, c;
     slot_decode(slot32, sg, a, strand, c);                  // (reciprocals of iv_stride and iv_cores from the launch)
-    BK_B_TRIP();
-    const uint32_t r = b.act[a];
+    if (!b.iv_by_read) BK_B_TRIP();
+    const uint32_t r = iv_index_read(b.iv_by_read, a, b.act);      // (slots that go by read decode straight to it: no trip to the list)
     BK_B_TRIP();
     const uint32_t meta = b.rmeta[r];
     const int len = (int)(meta & kReadLenMask);
@@ -528,8 +443,8 @@ __global__ void __launch_bounds__(256) k_search_deep(DevIndex ix, DevBatch b, in
     uint32_t a;
     int strand, c;
     slot_decode(slot32, sg, a, strand, c);
-    BK_B_TRIP();
-    const uint32_t r = b.act[a];
+    if (!b.iv_by_read) BK_B_TRIP();
+    const uint32_t r = iv_index_read(b.iv_by_read, a, b.act);      // (slots that go by read decode straight to it: no trip to the list)
     BK_B_TRIP();
     const uint32_t meta = b.rmeta[r];
     const int len = (int)(meta & kReadLenMask);
@@ -674,12 +589,12 @@ void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
 // that phase show in the results.
 __global__ void __launch_bounds__(256) k_clear_iv(DevBatch b, const uint32_t *__restrict__ p_n_act, int cmax, int st0, int st1, uint32_t word)
 {
-    const uint32_t n_act = *p_n_act;
+    const uint32_t n_act = b.iv_by_read ? b.n_reads : *p_n_act;       // (slots by read: every read's, the list may not exist yet)
     const uint64_t per_strand = (uint64_t)cmax * n_act, total = per_strand * (uint64_t)(st1 - st0 + 1);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
         const int st = st0 + (int)(i / per_strand);
         const uint64_t q = i % per_strand;
-        const uint64_t slot = iv_slot(b, (uint32_t)(q % n_act), st, (int)(q / n_act));
+        const uint64_t slot = iv_slot(b, (uint32_t)(q % n_act), (uint32_t)(q % n_act), st, (int)(q / n_act));
         if (b.iv2) b.iv2[slot] = make_uint2(word, word);
         else { b.iv_first[slot] = word ? ~0ULL : 0ULL; b.iv_n[slot] = word; }
     }

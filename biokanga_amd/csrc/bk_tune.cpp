@@ -157,6 +157,11 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->search_split_set = true;
         return old;
     }
+    if (n == "prep_search0") {             // host only: phase 0's pass A inside the read preparation (1) or as its own launch (0); the same records either way
+        int64_t old = c->prep_search0;
+        c->prep_search0 = value ? 1 : 0;
+        return old;
+    }
     if (n == "use_tgt2") {
         int64_t old = c->use_tgt2;
         c->use_tgt2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);

@@ -274,7 +274,7 @@ __global__ void __launch_bounds__(256, NW <= 8 ? ((HASH || !SW) ? 4 : BK_WAVE8_B
             if (ls < 32 && c_l < nc && st_l <= s1) {
                 uint64_t f;
                 uint32_t cn;
-                iv_get(b, iv_slot(b, pos, st_l, c_l), f, cn);
+                iv_get(b, iv_slot(b, pos, r, st_l, c_l), f, cn);
                 WaveCoreInfo &ci = s_core[wib][sti_l][c_l];
                 ci.first = f;
                 ci.n = cn;                    // bit 31: unverified bucket (<= kLazyBucket members)
@@ -724,7 +724,7 @@ __global__ void __launch_bounds__(256) k_keys_wave(DevAlignCfg cfg, DevBatch b, 
     uint64_t best_first = 0, work = 0;
     for (int st = s0; st <= s1; st++)
         for (int c = 0; c < nc; c++) {
-            uint64_t slot = iv_slot(b, pos, st, c);
+            uint64_t slot = iv_slot(b, pos, r, st, c);
             uint64_t f;
             uint32_t raw;
             iv_get(b, slot, f, raw);

@@ -219,6 +219,8 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "search_split" (pass B of the search in two launches: the key levels, then - a lane per item again, all of one kind - the bisections
  *   over suffix array and target that they leave and the full searches; 1 by default where the work list is not grouped, 0 where it is.
  *   Host only: which kernels are launched; the same records either way)
+ *   "prep_search0" (phase 0's first search pass inside the read preparation instead of a launch of its own; 1 by default, in effect on
+ *   the register-window path with the two-word k-mer table and 4-byte elements.  Host only; the same records either way)
  *   "use_wave" (wave kernel, 0: general hash-set kernel)   "use_isa" (inverse suffix
  *   array dedupe, 0: hash set)   "use_tgt2" (2 bit/base window compare)   "heavy_thresh" (longest interval the lane/flat kernels take, 0..100)
  *   "use_swin" (suffix-ordered window array: 0 none - every window from the 2-bit target; 1 for the part of the suffix array the wave kernel's long
