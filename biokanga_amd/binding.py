@@ -21,6 +21,7 @@ EXPORTED_SYMBOLS = [
     "bk_host_register", "bk_host_unregister", "bk_ctx_reserve", "bk_stream_create_packed", "bk_align_batch_device_async", "bk_ctx_create_ex", "bk_ctx_set_chrom_filter", "bk_sam_prep_wait", "bk_debug_intervals", "bk_image_policy",
     "bk_contam_create", "bk_contam_destroy", "bk_contam_match",
     "bk_samtags", "bk_sam_format_tags",
+    "bk_coverage_runs", "bk_coverage_text",
 ]
 
 
@@ -83,6 +84,11 @@ SAMTAG_REQ_DTYPE = np.dtype([("read_ofs", "<u8"), ("chrom_id", "<u4"), ("pos", "
                              ("c5", "<u2"), ("m", "<u2"), ("c3", "<u2"), ("m2", "<u2"), ("gap", "<i4")])
 assert SAMTAG_REQ_DTYPE.itemsize == 32
 SAMTAG_NM, SAMTAG_MD, SAMTAG_NONE = 1, 2, 0xFFFF
+# bk_cov_req: the M runs of one accepted record - m M [gap N|I|D m2 M] from `pos` (0-based) of sequence chrom_id; bk_cov_run: a run of equal depth
+COV_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("pos", "<u4"), ("m", "<u2"), ("m2", "<u2"), ("gap", "<i4")])
+COV_RUN_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])
+assert COV_REQ_DTYPE.itemsize == 16 and COV_RUN_DTYPE.itemsize == 16
+COV_TOTALS = ("runs", "covered", "depth_sum", "max_depth", "flagged")
 MAX_CONSTRAINED_SEQS, MAX_CONSTRAINTS, CONSTRAINT_R = 64, 6400, 0x10
 CONSTRAINT_UNTOUCHED, CONSTRAINT_TOUCHED, CONSTRAINT_VIOLATED, CONSTRAINT_BAD = 0, 1, 2, 0x80
 CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("mask", "u1"), ("_r", "u1", (3,))])
@@ -138,6 +144,7 @@ class _SamJob(ctypes.Structure):
 
 
 _SAM_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
+_COV_RUN_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
 
 
 def lib_path():
@@ -305,6 +312,10 @@ def load_library():
     lib.bk_sam_format_tags.restype = i32
     lib.bk_samtags.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64)]
     lib.bk_samtags.restype = i32
+    lib.bk_coverage_runs.argtypes = [vp, vp, u64, _COV_RUN_SINK, vp, ctypes.POINTER(u64 * 5)]
+    lib.bk_coverage_runs.restype = i32
+    lib.bk_coverage_text.argtypes = [vp, vp, u64, _SAM_SINK, vp, ctypes.POINTER(u64 * 5)]
+    lib.bk_coverage_text.restype = i32
     lib.bk_contam_create.argtypes = [ctypes.POINTER(vp), i32, vp, u32]
     lib.bk_contam_create.restype = i32
     lib.bk_contam_destroy.argtypes = [vp]
@@ -768,6 +779,41 @@ class Aligner:
             raise err
         raw = text.tobytes()
         return nm[:n], [None if nm[i] == SAMTAG_NONE else raw[int(ofs[i]):int(ofs[i + 1])] for i in range(n)]
+
+    def coverage_runs(self, reqs):
+        """bk_coverage_runs: the per-base depth of COV_REQ_DTYPE requests as maximal runs of equal non-zero depth -> (COV_RUN_DTYPE array
+        in output order, totals as a dict of COV_TOTALS, the number of runs each sink call delivered)"""
+        reqs = np.ascontiguousarray(reqs, dtype=COV_REQ_DTYPE)
+        parts = []
+
+        def sink(user, runs, n, ofs):
+            if ofs != sum(len(p) for p in parts):
+                return 1
+            parts.append(np.frombuffer(ctypes.string_at(runs, n * COV_RUN_DTYPE.itemsize), dtype=COV_RUN_DTYPE))
+            return 0
+        tot = (ctypes.c_uint64 * 5)()
+        rc = self.lib.bk_coverage_runs(self.h, reqs.ctypes.data if len(reqs) else None, len(reqs), _COV_RUN_SINK(sink), None, ctypes.byref(tot))
+        if rc:
+            raise BkError(rc, "bk_coverage_runs")
+        runs = np.concatenate(parts) if parts else np.zeros(0, dtype=COV_RUN_DTYPE)
+        return runs, dict(zip(COV_TOTALS, (int(v) for v in tot))), [len(p) for p in parts]
+
+    def coverage_text(self, reqs):
+        """bk_coverage_text: the same runs as bedGraph text, formatted by the device -> (the text as bytes, totals, the bytes each sink
+        call delivered)"""
+        reqs = np.ascontiguousarray(reqs, dtype=COV_REQ_DTYPE)
+        parts = []
+
+        def sink(user, text, n, ofs):
+            if ofs != sum(len(p) for p in parts):
+                return 1
+            parts.append(ctypes.string_at(text, n))
+            return 0
+        tot = (ctypes.c_uint64 * 5)()
+        rc = self.lib.bk_coverage_text(self.h, reqs.ctypes.data if len(reqs) else None, len(reqs), _SAM_SINK(sink), None, ctypes.byref(tot))
+        if rc:
+            raise BkError(rc, "bk_coverage_text")
+        return b"".join(parts), dict(zip(COV_TOTALS, (int(v) for v in tot))), [len(p) for p in parts]
 
     def sam_format(self, bases, offs, lens, names, hits, order, report_unaligned=True, pe_mode=0, *, src=None, seg2=None,
                    trim_left=None, trim_right=None, tags=None, packed=False):

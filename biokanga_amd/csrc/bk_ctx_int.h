@@ -58,6 +58,17 @@ struct BatchBufs {
     DevBuf<uint16_t> samtag_nm;
     DevBuf<unsigned long long> samtag_len, samtag_at;
     DevBuf<char> samtag_text;
+    DevBuf<bk_cov_req> cov_reqs;          // bk_coverage_*: one chunk of requests and its flag bytes (everything cov_: made by the first call)
+    DevBuf<uint8_t> cov_flags, cov_tmp;   //   (cov_tmp: the scans' temporary)
+    DevBuf<int32_t> cov_depth;            // a slice's deltas, then its depth: one per base, one more behind every sequence
+    DevBuf<uint64_t> cov_ent_ofs;         // n_ent + 1: where every sequence starts when each is followed by one position that stays 0
+    DevBuf<char> cov_names;               // n_ent x 81 bytes, by entry index
+    DevBuf<uint32_t> cov_tile_n[2];       // run starts / run ends in every tile of a slice ..
+    DevBuf<unsigned long long> cov_tile_at[2];    // .. and their exclusive sums (+ 1: the slice's runs)
+    DevBuf<unsigned long long> cov_tot;   // covered positions, sum of depth, largest depth
+    DevBuf<bk_cov_run> cov_runs;          // one chunk of runs
+    DevBuf<unsigned long long> cov_len, cov_at;   // the formatter: the chunk's line lengths and where each line starts
+    DevBuf<char> cov_text;
     DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
@@ -184,6 +195,11 @@ struct bk_ctx {
     uint64_t primer_chunk = 8u << 20;     // .. and bk_primer_correct this many ("primer_chunk")
     uint64_t constraint_chunk = 4u << 20; // .. and bk_constraints_check this many ("constraint_chunk")
     uint64_t samtag_chunk = 2u << 20;     // .. and bk_samtags this many ("samtag_chunk")
+    uint64_t cov_req_chunk = 8u << 20;    // .. and bk_coverage_* this many ("coverage_req_chunk")
+    uint64_t cov_slice_bases = 0;         // target bases per slice ("coverage_slice_bases"; 0: the first call derives it from the free memory)
+    uint64_t cov_run_chunk = 1u << 20;    // runs per sink call ("coverage_run_chunk")
+    void *cov_host = nullptr;             // page-locked: a chunk of runs, or a piece of text, on its way to the sink (16 bytes per run of a chunk)
+    uint64_t cov_host_cap = 0;
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)

@@ -1159,6 +1159,7 @@ void bk_ctx_destroy(bk_ctx *c)
     c->release_batch_buffers();
     if (c->h_small) (void)hipHostFree(c->h_small);
     for (void *&t : c->sam_text) if (t) { (void)hipHostFree(t); t = nullptr; }
+    if (c->cov_host) (void)hipHostFree(c->cov_host);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_plan) (void)hipHostFree(c->h_plan);
     if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);

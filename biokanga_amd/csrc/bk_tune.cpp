@@ -104,6 +104,30 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
     if (n == "samtag_buf_bytes")           // (read only) what bk_samtags' staging holds now: 0 until its first call
         return (int64_t)(c->buf.samtag_reqs.cap() * sizeof(bk_samtag_req) + c->buf.samtag_bases.cap() + c->buf.samtag_tmp.cap() + c->buf.samtag_gofs.cap() * 8 +
                          c->buf.samtag_nm.cap() * 2 + (c->buf.samtag_len.cap() + c->buf.samtag_at.cap()) * 8 + c->buf.samtag_text.cap());
+    if (n == "coverage_req_chunk") {       // requests bk_coverage_* stages at a time
+        int64_t old = (int64_t)c->cov_req_chunk;
+        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
+        c->cov_req_chunk = (uint64_t)value;
+        return old;
+    }
+    if (n == "coverage_slice_bases") {     // target bases per slice; 0 (the default): the next call derives it from the free memory
+        int64_t old = (int64_t)c->cov_slice_bases;
+        if (value < 0) return BK_ERR_PARAMS;
+        c->cov_slice_bases = (uint64_t)value;
+        return old;
+    }
+    if (n == "coverage_run_chunk") {       // runs per sink call
+        int64_t old = (int64_t)c->cov_run_chunk;
+        if (value < 1 || value > (1LL << 26)) return BK_ERR_PARAMS;
+        c->cov_run_chunk = (uint64_t)value;
+        return old;
+    }
+    if (n == "coverage_buf_bytes") {       // (read only) what bk_coverage_*'s staging holds now, device and page-locked: 0 until its first call
+        const bk::BatchBufs &B = c->buf;
+        return (int64_t)(B.cov_reqs.cap() * sizeof(bk_cov_req) + B.cov_flags.cap() + B.cov_tmp.cap() + B.cov_depth.cap() * 4 + B.cov_ent_ofs.cap() * 8 + B.cov_names.cap() +
+                         (B.cov_tile_n[0].cap() + B.cov_tile_n[1].cap()) * 4 + (B.cov_tile_at[0].cap() + B.cov_tile_at[1].cap() + B.cov_tot.cap() + B.cov_len.cap() + B.cov_at.cap()) * 8 +
+                         B.cov_runs.cap() * sizeof(bk_cov_run) + B.cov_text.cap() + c->cov_host_cap);
+    }
     if (n == "primer_buf_bytes")          // (read only) what bk_primer_correct's staging holds now: 0 until its first call
         return (int64_t)(c->buf.primer_reqs.cap() * sizeof(bk_primer_req) + c->buf.primer_res.cap() * sizeof(bk_primer_res));
     if (n == "kmer_bits" || n == "use_ktab") {

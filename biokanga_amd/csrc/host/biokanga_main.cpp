@@ -9,7 +9,7 @@
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
 //                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-5 lociconstraints.csv] [-T host threads] [-F logfile] [--device n | --devices 0-7]
-//                  [--sam-tags NM,MD]
+//                  [--sam-tags NM,MD] [--coverage depth.bedgraph]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -55,6 +55,7 @@
 #include "read_loader.h"
 #include "contaminants.h"
 #include "report.h"
+#include "coverage.h"
 
 namespace {
 using namespace bkcli;
@@ -225,6 +226,7 @@ struct AlignOpts {
     std::vector<regex_t> re_excl, re_incl;
     int sam_tags = 0;                      // --sam-tags: mask of BK_SAMTAG_NM | BK_SAMTAG_MD written behind QUAL of accepted records (0: none, the reference's lines)
     uint64_t sam_tag_bytes() const { return ((sam_tags & BK_SAMTAG_NM) ? 8u : 0u) + ((sam_tags & BK_SAMTAG_MD) ? 16u : 0u); }      // .. about what they add to a line
+    std::string coverage_path;             // --coverage: per-base depth of the accepted records into this bedGraph (empty: none; made on the first device)
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
 
@@ -383,6 +385,12 @@ int read_align_opts(Args &a, AlignOpts &o)
             diag("Error: SAM tags '--sam-tags %s' are only available with SAM / BAM output formats '-M5' and '-M6'", spec.c_str());
             return 1;
         }
+    }
+    // --coverage <file> (ours: the depth of the final record set, whatever the output format)
+    if (a.has("coverage")) {
+        o.coverage_path = a.str("coverage");
+        if (o.coverage_path.empty()) { diag("Error: coverage file '--coverage' needs a file name"); return 1; }
+        if (o.coverage_path == a.str("o")) { diag("Error: coverage file '--coverage %s' is the output file '-o' itself", o.coverage_path.c_str()); return 1; }
     }
     if (a.has("O") && o.fmt == 6) {                 // kanga.cpp:1015-1021
         diag("Error: Output induced substitution mode '-O<file>' not available in '-M6' output mode\n");
@@ -968,14 +976,14 @@ int parse_align_args(int argc, char **argv, int first, Args &a)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}};
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}, {"coverage", "coverage"}};
     if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err)) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
     if (!a.has("i") || !a.has("I") || !a.has("o")) {
         fprintf(stderr, "usage: %s align -i <reads> -I <genome.sfx> -o <out.sam> [-s subs] [-e delta] [-Q strand] [-m mode] [-n maxNs] "
-                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD]\n", g_proc.c_str());
+                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD] [--coverage depth.bedgraph]\n", g_proc.c_str());
         return 1;
     }
     return 0;
@@ -1607,6 +1615,7 @@ int write_reports(AlignRun &r)
     const std::string opath = a.str("o");
     int rr = (o.fmt >= 5 && is_bam_name(opath)) ? report_bam(R, opath) : report_text(R);
     if (R.sam_prep) { bk_sam_prep_free(R.sam_prep); R.sam_prep = nullptr; }        // (the report took another path)
+    if (rr == 0 && !o.coverage_path.empty()) rr = write_coverage(R, o.coverage_path);      // --coverage: behind the writer, on the first device
     if (rr == 0 && r.with_site_prefs) {             // WriteSitePrefs, behind the writers and the -O statistics (Aligner.cpp:743)
         std::string csv;
         bk::site_prefs_csv(r.site_prefs, csv);

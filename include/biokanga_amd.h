@@ -242,6 +242,9 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "primer_chunk" (requests bk_primer_correct stages at a time; "primer_buf_bytes": what its staging holds now, read only)
  *   "constraint_chunk" (requests bk_constraints_check stages at a time)
  *   "samtag_chunk" (requests bk_samtags stages at a time; "samtag_buf_bytes": what its staging holds now, read only)
+ *   "coverage_slice_bases" (target bases bk_coverage_* takes per slice, one int32 each; 0 - the default - until the first call
+ *   derives it from the free memory), "coverage_run_chunk" (runs per sink call), "coverage_req_chunk" (requests staged at a time),
+ *   "coverage_buf_bytes" (what its staging holds now, device and page-locked; read only)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -722,6 +725,53 @@ int  bk_samtags(bk_ctx *ctx, const bk_samtag_req *reqs, uint64_t n, const uint8_
  * the formatter.  A record without tags (see above) and the lines of unaccepted reads are as bk_sam_format writes them; tags == 0 IS
  * bk_sam_format.  BK_ERR_PARAMS: bits beyond the two. */
 int  bk_sam_format_tags(bk_ctx *ctx, const bk_sam_job *job, uint32_t tags, bk_sam_sink sink, void *user, uint64_t *n_reported, uint64_t *n_bytes);
+
+/* ---- per-base depth of the accepted records as a bedGraph (--coverage) ------------------------------------------------
+ * Ours, as --sam-tags is: the reference has no such output.  THE RULE: the depth at a target position is the number of accepted
+ * records whose line as written has an M base there.  The walk is the one --sam-tags uses, the numbers put_cigar prints -
+ * [c5 S] m M [c3 S] [gap N|I|D m2 M] from POS: M counts; S and I touch no target base; N and D skip `gap` target bases without
+ * counting them; behind an I the second M run starts where the first ended.  Every record counts on its own - both mates of a
+ * pair even where they overlap, every locus of a read under -r5.
+ * The output is a bedGraph: one line name<TAB>start<TAB>end<TAB>depth<LF> per maximal run of equal non-zero depth, 0-based,
+ * half-open, decimal numbers without padding, sequences in index order, runs by start; no track line, no zero-depth runs (what
+ * `bedtools genomecov -bg -split` prints); a run never spans two sequences.
+ * On the device: the target is taken in slices of whole sequences (as many as fit "coverage_slice_bases"; a longer sequence
+ * gets a slice of its own), one int32 per base; a lane per request adds +1 / -1 at the ends of its M runs, an inclusive sum turns
+ * the deltas into depth, the run starts and run ends are counted per tile, placed by a prefix sum and written out
+ * "coverage_run_chunk" runs at a time.  bk_coverage_text formats every chunk of runs on the device (a lane per line: measure,
+ * prefix sum, write) and hands the text on in pieces of 16 * "coverage_run_chunk" bytes: lines may straddle two sink calls.
+ * Requests may come in any order (the answer does not depend on it); in output order neighbouring lanes hit neighbouring words. */
+typedef struct bk_cov_req {
+    uint32_t chrom_id;           /* the sequence's EntryID                                                    */
+    uint32_t pos;                /* 0-based position of the first M base in that sequence                    */
+    uint16_t m;                  /* the first M run                                                           */
+    uint16_t m2;                 /* the second M run; 0: none                                                 */
+    int32_t  gap;                /* target bases between the runs (N, D); 0 behind an I                       */
+} bk_cov_req;                    /* 16 bytes */
+typedef struct bk_cov_run {
+    uint32_t chrom_id;
+    uint32_t start, end;         /* 0-based, half-open                                                        */
+    uint32_t depth;
+} bk_cov_run;                    /* 16 bytes */
+typedef struct bk_cov_totals {
+    uint64_t runs;               /* runs delivered = lines of the bedGraph                                    */
+    uint64_t covered;            /* positions with depth > 0                                                  */
+    uint64_t depth_sum;          /* sum of depth over all positions = M bases of the requests that counted   */
+    uint64_t max_depth;
+    uint64_t flagged;            /* requests flagged (below)                                                  */
+} bk_cov_totals;
+/* runs[0 .. n_runs) in output order; run_offset = how many were delivered before; must return 0 */
+typedef int (*bk_cov_run_sink)(void *user, const bk_cov_run *runs, uint64_t n_runs, uint64_t run_offset);
+/* Host requests, blocking, everything on the context's stream; the sinks are called on the caller's thread, one call at a time,
+ * with increasing offsets.  Staging belongs to the context and is made by the first call (a run without the option allocates
+ * nothing; "coverage_buf_bytes", read only, says what is held).
+ * A request is FLAGGED when its sequence does not exist, m is 0, gap is negative or either M run leaves its sequence: it
+ * contributes nothing from either run, is counted in totals->flagged and harms no other request.
+ * BK_ERR_PARAMS, before anything is launched: reqs == NULL with n > 0, a NULL sink, n >= 2^31.  n == 0 delivers nothing (totals
+ * may be NULL).
+ * Both calls share every kernel but the formatter's. */
+int  bk_coverage_runs(bk_ctx *ctx, const bk_cov_req *reqs, uint64_t n, bk_cov_run_sink sink, void *user, bk_cov_totals *totals);
+int  bk_coverage_text(bk_ctx *ctx, const bk_cov_req *reqs, uint64_t n, bk_sam_sink sink, void *user, bk_cov_totals *totals);
 
 /* ---- test hook: the search stage on its own ------------------------------------------------------------------------
  * LocateFirstExact / LocateLastExact (SfxArrayV2.cpp:7765-7876, :7914-8027) are two kernels here (k-mer table + key arrays, bk_search.hip); to
