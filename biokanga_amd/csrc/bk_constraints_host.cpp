@@ -4,32 +4,7 @@
 // bk_constraints.hip.
 #include "bk_engine_int.h"
 
-#include <chrono>
-
 using namespace bk;
-
-namespace {
-// page-locked host memory of the staging, grown like a DevBuf: the old block goes first, contents are not kept
-template <class T> struct PinBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t ensure(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        void *q = nullptr;
-        const hipError_t e = hipHostMalloc(&q, n * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        p = static_cast<T *>(q); cap = n;
-        return hipSuccess;
-    }
-};
-}  // namespace
 
 struct bk_constraints {
     bk_ctx *c = nullptr;
@@ -61,8 +36,7 @@ int bk_constraints_create(bk_ctx *c, const bk_constraint *cons, uint32_t n, bk_c
 {
     if (!c || !out || (n && !cons) || n > BK_MAX_CONSTRAINTS) return BK_ERR_PARAMS;
     *out = nullptr;
-    std::vector<uint32_t> len_of;                                            // by sequence id; 0: no such sequence
-    for (const auto &e : c->entries) { if (e.entry_id >= len_of.size()) len_of.resize((size_t)e.entry_id + 1, 0); len_of[e.entry_id] = e.seq_len; }
+    const std::vector<uint32_t> len_of = seq_len_by_id(c);                   // (0: no such sequence)
     std::vector<bk_constraint> v(cons, cons + n);
     for (const bk_constraint &k : v)
         if (k.chrom_id >= len_of.size() || !len_of[k.chrom_id] || k.start > k.end || k.end >= len_of[k.chrom_id] || !k.mask || (k.mask & ~0x1fu)) return BK_ERR_PARAMS;
@@ -119,9 +93,8 @@ int bk_constraints_check(bk_constraints *set, const bk_constraint_req *reqs, uin
     // (BK_TIMING=1: where the pass spends its time, on stderr like the other stage clocks; the kernels are waited for either way)
     const bool timing = bk::env::timing();
     double ms[7] = {0, 0, 0, 0, 0, 0, 0};               // requests up, touch, list down, gather, bases up, check, statuses down
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    auto now = []() { return 1e3 * bk::now_s(); };
     uint64_t n_touched = 0, n_gathered = 0;
-    const int nthreads = std::max(1, std::min(8, effective_cpus()));
     auto one = [&](uint64_t at, uint32_t m) -> int {
         double t0 = now(), t1;
         auto lap = [&](int k) { t1 = now(); ms[k] += t1 - t0; t0 = t1; };
@@ -130,37 +103,29 @@ int bk_constraints_check(bk_constraints *set, const bk_constraint_req *reqs, uin
         if (timing) { HIP_TRY(hipStreamSynchronize(s)); lap(0); }
         launch_constraint_touch(c->ix, set->dev, set->d_reqs.get(), m, n_bases, set->d_status.get(), set->d_list.get(), set->d_cnt.get(), s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(set->h_cnt.p, set->d_cnt.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(set->h_cnt.get(), set->d_cnt.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         lap(1);
-        const uint32_t n_list = *set->h_cnt.p;
+        const uint32_t n_list = *set->h_cnt.get();
         if (n_list > m) return BK_ERR_INTERNAL;
         if (n_list) {
-            HIP_TRY(hipMemcpyAsync(set->h_list.p, set->d_list.get(), (size_t)n_list * sizeof(ConstraintHit), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(set->h_list.get(), set->d_list.get(), (size_t)n_list * sizeof(ConstraintHit), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             lap(2);
             // the listed reads' bases, back to back in list order (the kernel served these requests: their reads lie inside `bases`)
             HIP_TRY(set->h_gofs.ensure(n_list));
             HIP_TRY(set->d_gofs.ensure(n_list));
             uint64_t total = 0;
-            for (uint32_t t = 0; t < n_list; t++) { set->h_gofs.p[t] = total; total += reqs[at + set->h_list.p[t].req].read_len; }
+            for (uint32_t t = 0; t < n_list; t++) { set->h_gofs.get()[t] = total; total += reqs[at + set->h_list.get()[t].req].read_len; }
             HIP_TRY(set->h_bases.ensure(std::max<uint64_t>(total, 1)));
             HIP_TRY(set->d_bases.ensure(std::max<uint64_t>(total, 1)));
-            auto gather = [&](uint32_t lo, uint32_t hi) {
-                for (uint32_t t = lo; t < hi; t++) {
-                    const bk_constraint_req &q = reqs[at + set->h_list.p[t].req];
-                    memcpy(set->h_bases.p + set->h_gofs.p[t], bases + q.read_ofs, q.read_len);
-                }
-            };
-            if (total < (8u << 20) || nthreads == 1) gather(0, n_list);
-            else {
-                std::vector<std::thread> th;
-                for (int k = 0; k < nthreads; k++) th.emplace_back(gather, (uint32_t)((uint64_t)n_list * k / nthreads), (uint32_t)((uint64_t)n_list * (k + 1) / nthreads));
-                for (auto &x : th) x.join();
-            }
+            gather_reads(set->h_bases.get(), set->h_gofs.get(), bases, total, n_list, [&](uint32_t t) {
+                const bk_constraint_req &q = reqs[at + set->h_list.get()[t].req];
+                return std::make_pair((uint64_t)q.read_ofs, (uint32_t)q.read_len);
+            });
             lap(3);
-            HIP_TRY(hipMemcpyAsync(set->d_gofs.get(), set->h_gofs.p, (size_t)n_list * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            if (total) HIP_TRY(hipMemcpyAsync(set->d_bases.get(), set->h_bases.p, total, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(set->d_gofs.get(), set->h_gofs.get(), (size_t)n_list * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            if (total) HIP_TRY(hipMemcpyAsync(set->d_bases.get(), set->h_bases.get(), total, hipMemcpyHostToDevice, s));
             if (timing) { HIP_TRY(hipStreamSynchronize(s)); lap(4); }
             launch_constraint_check(c->ix, set->dev, set->d_reqs.get(), set->d_list.get(), n_list, set->d_bases.get(), set->d_gofs.get(), set->d_status.get(), s);
             HIP_TRY(hipGetLastError());

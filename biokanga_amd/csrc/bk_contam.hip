@@ -22,6 +22,7 @@
 
 #include "../../include/biokanga_amd.h"
 #include "bk_cpus.h"
+#include "bk_devbuf.h"
 
 namespace {
 
@@ -173,9 +174,12 @@ k_contam(const uint8_t *__restrict__ bases, const uint32_t *__restrict__ offs, c
 }
 
 struct Slot {
-    uint8_t *h_bases = nullptr, *h_pe2 = nullptr, *d_bases = nullptr, *d_pe2 = nullptr;
-    uint32_t *h_offs = nullptr, *h_lens = nullptr, *d_offs = nullptr, *d_lens = nullptr;
-    uint16_t *h_out = nullptr, *d_out = nullptr;
+    bk::PinBuf<uint8_t> h_bases, h_pe2;
+    bk::PinBuf<uint32_t> h_offs, h_lens;
+    bk::PinBuf<uint16_t> h_out;                        // two per read
+    bk::DevBuf<uint8_t> d_bases, d_pe2;
+    bk::DevBuf<uint32_t> d_offs, d_lens;
+    bk::DevBuf<uint16_t> d_out;
     hipEvent_t done = nullptr;
     uint64_t first = 0;                                // the chunk in flight: reads [first, first + n)
     uint32_t n = 0;
@@ -186,7 +190,7 @@ struct Slot {
 struct bk_contam {
     int device = 0;
     hipStream_t stream = nullptr;
-    void *d_set = nullptr;
+    bk::DevBuf<uint8_t> d_set;
     uint32_t set_bytes = 0;
     bool in_lds = false;
     int blocks = 0;
@@ -201,23 +205,10 @@ void free_all(bk_contam *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (Slot &s : c->slot) {
-        if (s.h_bases) (void)hipHostFree(s.h_bases);
-        if (s.h_pe2) (void)hipHostFree(s.h_pe2);
-        if (s.h_offs) (void)hipHostFree(s.h_offs);
-        if (s.h_lens) (void)hipHostFree(s.h_lens);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.d_bases) (void)hipFree(s.d_bases);
-        if (s.d_pe2) (void)hipFree(s.d_pe2);
-        if (s.d_offs) (void)hipFree(s.d_offs);
-        if (s.d_lens) (void)hipFree(s.d_lens);
-        if (s.d_out) (void)hipFree(s.d_out);
+    for (Slot &s : c->slot)
         if (s.done) (void)hipEventDestroy(s.done);
-        s = Slot{};
-    }
-    if (c->d_set) (void)hipFree(c->d_set);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                          // (the buffers go with their owners, while the device is current)
 }
 
 // the staging and device buffers of the chunks, made at the first match call: kSlots x (64 MB of bases + 13 bytes per read of 2^20) on either side
@@ -225,14 +216,11 @@ bool make_slots(bk_contam *c)
 {
     if (c->have_slots) return true;
     for (Slot &s : c->slot) {
-        bool ok = hipHostMalloc((void **)&s.h_bases, kChunkBases) == hipSuccess && hipHostMalloc((void **)&s.h_pe2, kChunkReads) == hipSuccess &&
-                  hipHostMalloc((void **)&s.h_offs, 4ull * kChunkReads) == hipSuccess && hipHostMalloc((void **)&s.h_lens, 4ull * kChunkReads) == hipSuccess &&
-                  hipHostMalloc((void **)&s.h_out, 4ull * kChunkReads) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s.d_bases, kChunkBases) == hipSuccess && hipMalloc((void **)&s.d_pe2, kChunkReads) == hipSuccess &&
-             hipMalloc((void **)&s.d_offs, 4ull * kChunkReads) == hipSuccess && hipMalloc((void **)&s.d_lens, 4ull * kChunkReads) == hipSuccess &&
-             hipMalloc((void **)&s.d_out, 4ull * kChunkReads) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-        if (!ok) return false;
+        // (the first failure ends it; a later call finds what was made and goes on from there)
+        if (s.h_bases.ensure(kChunkBases) || s.h_pe2.ensure(kChunkReads) || s.h_offs.ensure(kChunkReads) || s.h_lens.ensure(kChunkReads) || s.h_out.ensure(2ull * kChunkReads) ||
+            s.d_bases.ensure(kChunkBases) || s.d_pe2.ensure(kChunkReads) || s.d_offs.ensure(kChunkReads) || s.d_lens.ensure(kChunkReads) || s.d_out.ensure(2ull * kChunkReads))
+            return false;
+        if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return false;
     }
     c->have_slots = true;
     return true;
@@ -299,8 +287,8 @@ extern "C" int bk_contam_create(bk_contam **out, int device_id, const bk_contam_
     c->in_lds = bytes <= kContamLdsBudget;
     hipDeviceProp_t prop;
     if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&prop, device_id) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_set, img.size() * 8) != hipSuccess ||
-        hipMemcpy(c->d_set, img.data(), img.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || c->d_set.ensure(img.size() * 8) != hipSuccess ||
+        hipMemcpy(c->d_set.get(), img.data(), img.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
         free_all(c);
         return BK_ERR_MEM;
     }
@@ -323,7 +311,7 @@ extern "C" int bk_contam_match(bk_contam *c, const uint8_t *bases, const uint64_
     auto collect = [&](Slot &s) -> int {               // the results of the slot's chunk, once it is through
         if (!s.n) return BK_OK;
         if (hipEventSynchronize(s.done) != hipSuccess) return BK_ERR_INTERNAL;
-        memcpy(out + 2 * s.first, s.h_out, 4ull * s.n);
+        memcpy(out + 2 * s.first, s.h_out.get(), 4ull * s.n);
         s.n = 0;
         return BK_OK;
     };
@@ -339,8 +327,8 @@ extern "C" int bk_contam_match(bk_contam *c, const uint8_t *bases, const uint64_
             const uint32_t len = lens[at + n];
             const uint32_t take = (len >= (uint32_t)kMinReadLen && len <= (uint32_t)kMaxReadLen) ? len : 0;
             if (nb + take > kChunkBases) break;
-            s.h_offs[n] = (uint32_t)nb;
-            s.h_lens[n] = take;
+            s.h_offs.get()[n] = (uint32_t)nb;
+            s.h_lens.get()[n] = take;
             nb += take;
             src += len;
             n++;
@@ -353,28 +341,28 @@ extern "C" int bk_contam_match(bk_contam *c, const uint8_t *bases, const uint64_
                 if (!offs) for (size_t i = 0; i < lo; i++) from += lens[first + i];
                 for (size_t i = lo; i < hi; i++) {
                     const uint32_t len = lens[first + i];
-                    if (s.h_lens[i]) memcpy(s.h_bases + s.h_offs[i], bases + (offs ? offs[first + i] : from), len);
+                    if (s.h_lens.get()[i]) memcpy(s.h_bases.get() + s.h_offs.get()[i], bases + (offs ? offs[first + i] : from), len);
                     from += len;
-                    s.h_pe2[i] = is_pe2 ? (uint8_t)(is_pe2[first + i] != 0) : (uint8_t)all_pe2;
+                    s.h_pe2.get()[i] = is_pe2 ? (uint8_t)(is_pe2[first + i] != 0) : (uint8_t)all_pe2;
                 }
             });
         }
         s.first = at;
         s.n = n;
         at += n;
-        bool ok = (nb == 0 || hipMemcpyAsync(s.d_bases, s.h_bases, nb, hipMemcpyHostToDevice, c->stream) == hipSuccess) &&
-                  hipMemcpyAsync(s.d_offs, s.h_offs, 4ull * n, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-                  hipMemcpyAsync(s.d_lens, s.h_lens, 4ull * n, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
-                  hipMemcpyAsync(s.d_pe2, s.h_pe2, n, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+        bool ok = (nb == 0 || hipMemcpyAsync(s.d_bases.get(), s.h_bases.get(), nb, hipMemcpyHostToDevice, c->stream) == hipSuccess) &&
+                  hipMemcpyAsync(s.d_offs.get(), s.h_offs.get(), 4ull * n, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+                  hipMemcpyAsync(s.d_lens.get(), s.h_lens.get(), 4ull * n, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+                  hipMemcpyAsync(s.d_pe2.get(), s.h_pe2.get(), n, hipMemcpyHostToDevice, c->stream) == hipSuccess;
         if (ok) {
             const int blocks = (int)std::min<uint64_t>((uint64_t)c->blocks, (n + kWaves - 1) / kWaves);
             if (c->in_lds)
-                hipLaunchKernelGGL(k_contam<true>, dim3(blocks), dim3(64 * kWaves), c->set_bytes, c->stream, s.d_bases, s.d_offs, s.d_lens, s.d_pe2, 0, n,
-                                   trim5, trim3, (const SetHdr *)c->d_set, s.d_out);
+                hipLaunchKernelGGL(k_contam<true>, dim3(blocks), dim3(64 * kWaves), c->set_bytes, c->stream, s.d_bases.get(), s.d_offs.get(), s.d_lens.get(), s.d_pe2.get(), 0, n,
+                                   trim5, trim3, (const SetHdr *)c->d_set.get(), s.d_out.get());
             else
-                hipLaunchKernelGGL(k_contam<false>, dim3(blocks), dim3(64 * kWaves), 0, c->stream, s.d_bases, s.d_offs, s.d_lens, s.d_pe2, 0, n, trim5,
-                                   trim3, (const SetHdr *)c->d_set, s.d_out);
-            ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(s.h_out, s.d_out, 4ull * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                hipLaunchKernelGGL(k_contam<false>, dim3(blocks), dim3(64 * kWaves), 0, c->stream, s.d_bases.get(), s.d_offs.get(), s.d_lens.get(), s.d_pe2.get(), 0, n, trim5,
+                                   trim3, (const SetHdr *)c->d_set.get(), s.d_out.get());
+            ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(s.h_out.get(), s.d_out.get(), 4ull * n, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
                  hipEventRecord(s.done, c->stream) == hipSuccess;
         }
         if (!ok) { s.n = 0; rc = BK_ERR_INTERNAL; }

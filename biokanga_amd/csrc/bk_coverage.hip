@@ -16,6 +16,7 @@
 
 #include "bk_ctx_int.h"
 #include "bk_env.h"
+#include "bk_wait.h"
 #include "bk_samtags.h"
 
 namespace {
@@ -196,8 +197,6 @@ struct CovSinks {
     void *user;
 };
 
-double cov_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-
 int coverage(bk_ctx *c, const bk_cov_req *reqs, uint64_t n, const CovSinks &sink, bk_cov_totals *totals)
 {
     if (!c || (n && !reqs) || (!sink.runs && !sink.text) || n >= (1ULL << 31)) return BK_ERR_PARAMS;
@@ -207,15 +206,15 @@ int coverage(bk_ctx *c, const bk_cov_req *reqs, uint64_t n, const CovSinks &sink
     if (!n_ent || !c->ix.id2idx) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    bk::BatchBufs &B = c->buf;
+    bk::CovStage &B = c->cov;
     const bool timing = bk::env::timing();
-    const double t_start = cov_now();
+    const double t_start = bk::now_s();
     enum { T_UP, T_MARK, T_SCAN, T_COUNT, T_EMIT, T_TEXT, T_OUT, T_N };
     double t_acc[T_N] = {0}, t_last = t_start;
     auto lap = [&](int what) -> hipError_t {                    // (BK_TIMING only: the stage is waited for and its time booked)
         if (!timing) return hipSuccess;
         const hipError_t e = hipStreamSynchronize(s);
-        const double t = cov_now();
+        const double t = bk::now_s();
         t_acc[what] += t - t_last;
         t_last = t;
         return e;
@@ -225,103 +224,99 @@ int coverage(bk_ctx *c, const bk_cov_req *reqs, uint64_t n, const CovSinks &sink
     std::vector<uint64_t> ent_ofs((size_t)n_ent + 1);
     ent_ofs[0] = 0;
     for (uint32_t e = 0; e < n_ent; e++) ent_ofs[e + 1] = ent_ofs[e] + c->entries[e].seq_len + 1;
-    if (!c->cov_slice_bases) {
+    if (!B.slice_bases) {
         // a budget, not a measured optimum: three quarters of what is free now for the slice's int32s, the rest for the staging
         // below (some hundred MB at the default chunks), the tile tables (24 bytes per 2048 positions) and whatever comes later
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        c->cov_slice_bases = std::max<uint64_t>((uint64_t)(free_b - free_b / 4) / 4, 1u << 16);
+        B.slice_bases = std::max<uint64_t>((uint64_t)(free_b - free_b / 4) / 4, 1u << 16);
     }
     std::vector<uint32_t> slice_first;                          // the slices: entries [slice_first[k], slice_first[k + 1])
     uint64_t max_len = 0;
     for (uint32_t e = 0; e < n_ent;) {
         uint32_t z = e + 1;
-        while (z < n_ent && ent_ofs[z + 1] - ent_ofs[e] <= c->cov_slice_bases) z++;
+        while (z < n_ent && ent_ofs[z + 1] - ent_ofs[e] <= B.slice_bases) z++;
         slice_first.push_back(e);
         max_len = std::max(max_len, ent_ofs[z] - ent_ofs[e]);
         e = z;
     }
     slice_first.push_back(n_ent);
     const uint64_t max_tiles = (max_len + kCovTile - 1) / kCovTile;
-    const uint32_t req_chunk = (uint32_t)std::min<uint64_t>(n, c->cov_req_chunk), run_chunk = (uint32_t)c->cov_run_chunk;
+    const uint32_t req_chunk = (uint32_t)std::min<uint64_t>(n, B.req_chunk), run_chunk = (uint32_t)B.run_chunk;
 
-    if (!B.cov_ent_ofs.cap()) {
-        HIP_TRY(B.cov_ent_ofs.ensure((size_t)n_ent + 1));
-        HIP_TRY(hipMemcpyAsync(B.cov_ent_ofs.get(), ent_ofs.data(), ((size_t)n_ent + 1) * 8, hipMemcpyHostToDevice, s));
+    if (!B.ent_ofs.cap()) {
+        HIP_TRY(B.ent_ofs.ensure((size_t)n_ent + 1));
+        HIP_TRY(hipMemcpyAsync(B.ent_ofs.get(), ent_ofs.data(), ((size_t)n_ent + 1) * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    if (sink.text && !B.cov_names.cap()) {
+    if (sink.text && !B.names.cap()) {
         std::vector<char> names((size_t)n_ent * kCovNameStride, 0);
         for (uint32_t e = 0; e < n_ent; e++) { memcpy(&names[(size_t)e * kCovNameStride], c->entries[e].name, kCovNameStride); names[(size_t)e * kCovNameStride + kCovNameStride - 1] = 0; }
-        HIP_TRY(B.cov_names.ensure(names.size()));
-        HIP_TRY(hipMemcpyAsync(B.cov_names.get(), names.data(), names.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(B.names.ensure(names.size()));
+        HIP_TRY(hipMemcpyAsync(B.names.get(), names.data(), names.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    HIP_TRY(B.cov_reqs.ensure(req_chunk));
-    HIP_TRY(B.cov_flags.ensure(req_chunk));
-    HIP_TRY(B.cov_depth.ensure(max_len));
-    for (int k = 0; k < 2; k++) { HIP_TRY(B.cov_tile_n[k].ensure(max_tiles + 1)); HIP_TRY(B.cov_tile_at[k].ensure(max_tiles + 1)); }
-    HIP_TRY(B.cov_tot.ensure(3));
-    HIP_TRY(B.cov_runs.ensure(run_chunk));
-    if (sink.text) { HIP_TRY(B.cov_len.ensure((size_t)run_chunk + 1)); HIP_TRY(B.cov_at.ensure((size_t)run_chunk + 1)); }
+    HIP_TRY(B.reqs.ensure(req_chunk));
+    HIP_TRY(B.flags.ensure(req_chunk));
+    HIP_TRY(B.depth.ensure(max_len));
+    for (int k = 0; k < 2; k++) { HIP_TRY(B.tile_n[k].ensure(max_tiles + 1)); HIP_TRY(B.tile_at[k].ensure(max_tiles + 1)); }
+    HIP_TRY(B.tot.ensure(3));
+    HIP_TRY(B.runs.ensure(run_chunk));
+    if (sink.text) { HIP_TRY(B.len.ensure((size_t)run_chunk + 1)); HIP_TRY(B.at.ensure((size_t)run_chunk + 1)); }
     size_t tb = 0, tb1 = 0;
-    HIP_TRY(bk::prim::inclusive_sum(nullptr, tb1, B.cov_depth.get(), B.cov_depth.get(), (size_t)max_len, s));
+    HIP_TRY(bk::prim::inclusive_sum(nullptr, tb1, B.depth.get(), B.depth.get(), (size_t)max_len, s));
     tb = std::max(tb, tb1);
-    HIP_TRY(bk::prim::exclusive_sum(nullptr, tb1, B.cov_tile_n[0].get(), B.cov_tile_at[0].get(), (size_t)max_tiles + 1, s));
+    HIP_TRY(bk::prim::exclusive_sum(nullptr, tb1, B.tile_n[0].get(), B.tile_at[0].get(), (size_t)max_tiles + 1, s));
     tb = std::max(tb, tb1);
     if (sink.text) {
-        HIP_TRY(bk::prim::exclusive_sum(nullptr, tb1, B.cov_len.get(), B.cov_at.get(), (size_t)run_chunk + 1, s));
+        HIP_TRY(bk::prim::exclusive_sum(nullptr, tb1, B.len.get(), B.at.get(), (size_t)run_chunk + 1, s));
         tb = std::max(tb, tb1);
     }
-    HIP_TRY(B.cov_tmp.ensure(tb + 256));
+    HIP_TRY(B.tmp.ensure(tb + 256));
     const uint64_t host_need = std::max<uint64_t>((uint64_t)run_chunk * sizeof(bk_cov_run), 256);
-    if (c->cov_host_cap < host_need) {
-        if (c->cov_host) { (void)hipHostFree(c->cov_host); c->cov_host = nullptr; c->cov_host_cap = 0; }
-        HIP_TRY(hipHostMalloc(&c->cov_host, host_need, hipHostMallocDefault));
-        c->cov_host_cap = host_need;
-    }
+    HIP_TRY(B.host.ensure(host_need));
     const uint64_t host_piece = host_need;                      // (a larger buffer left by an earlier call changes nothing about the pieces)
-    HIP_TRY(hipMemsetAsync(B.cov_tot.get(), 0, 3 * 8, s));
+    HIP_TRY(hipMemsetAsync(B.tot.get(), 0, 3 * 8, s));
 
     std::vector<uint8_t> flags(req_chunk);
     std::vector<unsigned long long> at_start, at_end;
     uint64_t n_runs = 0, n_flagged = 0, text_at = 0;
-    if (timing) { HIP_TRY(hipStreamSynchronize(s)); t_last = cov_now(); }
+    if (timing) { HIP_TRY(hipStreamSynchronize(s)); t_last = bk::now_s(); }
     for (size_t k = 0; k + 1 < slice_first.size(); k++) {
         const uint32_t e0 = slice_first[k], e1 = slice_first[k + 1];
         const uint64_t len = ent_ofs[e1] - ent_ofs[e0], n_tiles = (len + kCovTile - 1) / kCovTile;
-        int32_t *depth = B.cov_depth.get();
+        int32_t *depth = B.depth.get();
         HIP_TRY(hipMemsetAsync(depth, 0, (size_t)len * 4, s));
         for (uint64_t at = 0; at < n; at += req_chunk) {
             const uint32_t m = (uint32_t)std::min<uint64_t>(req_chunk, n - at);
             HIP_TRY(hipStreamSynchronize(s));                   // (the chunk before has been read)
             if (n > req_chunk || k == 0) {                      // (a call of one chunk still has its requests on the device)
-                if (bk::upload_host(B.cov_reqs.get(), reqs + at, (size_t)m * sizeof(bk_cov_req), c->device)) return BK_ERR_INTERNAL;
+                if (bk::upload_host(B.reqs.get(), reqs + at, (size_t)m * sizeof(bk_cov_req), c->device)) return BK_ERR_INTERNAL;
             }
             HIP_TRY(lap(T_UP));
-            hipLaunchKernelGGL(k_cov_mark, dim3((m + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.cov_ent_ofs.get(), reinterpret_cast<const uint4 *>(B.cov_reqs.get()), m, e0,
-                               e1, depth, k == 0 ? B.cov_flags.get() : nullptr);
+            hipLaunchKernelGGL(k_cov_mark, dim3((m + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.ent_ofs.get(), reinterpret_cast<const uint4 *>(B.reqs.get()), m, e0,
+                               e1, depth, k == 0 ? B.flags.get() : nullptr);
             HIP_TRY(hipGetLastError());
             HIP_TRY(lap(T_MARK));
             if (k == 0) {
-                HIP_TRY(hipMemcpyAsync(flags.data(), B.cov_flags.get(), m, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(flags.data(), B.flags.get(), m, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
                 for (uint32_t t = 0; t < m; t++) n_flagged += flags[t];
             }
         }
-        size_t t2 = B.cov_tmp.cap();
-        HIP_TRY(bk::prim::inclusive_sum(B.cov_tmp.get(), t2, depth, depth, (size_t)len, s));
+        size_t t2 = B.tmp.cap();
+        HIP_TRY(bk::prim::inclusive_sum(B.tmp.get(), t2, depth, depth, (size_t)len, s));
         HIP_TRY(lap(T_SCAN));
-        for (int q = 0; q < 2; q++) HIP_TRY(hipMemsetAsync(B.cov_tile_n[q].get() + n_tiles, 0, 4, s));
-        hipLaunchKernelGGL(k_cov_count, dim3((uint32_t)((n_tiles + kCovWaves - 1) / kCovWaves)), dim3(kCovBlock), 0, s, depth, len, B.cov_tile_n[0].get(), B.cov_tile_n[1].get(),
-                           B.cov_tot.get());
+        for (int q = 0; q < 2; q++) HIP_TRY(hipMemsetAsync(B.tile_n[q].get() + n_tiles, 0, 4, s));
+        hipLaunchKernelGGL(k_cov_count, dim3((uint32_t)((n_tiles + kCovWaves - 1) / kCovWaves)), dim3(kCovBlock), 0, s, depth, len, B.tile_n[0].get(), B.tile_n[1].get(),
+                           B.tot.get());
         HIP_TRY(hipGetLastError());
         at_start.resize(n_tiles + 1);
         at_end.resize(n_tiles + 1);
         for (int q = 0; q < 2; q++) {
-            t2 = B.cov_tmp.cap();
-            HIP_TRY(bk::prim::exclusive_sum(B.cov_tmp.get(), t2, B.cov_tile_n[q].get(), B.cov_tile_at[q].get(), (size_t)n_tiles + 1, s));
-            HIP_TRY(hipMemcpyAsync((q ? at_end : at_start).data(), B.cov_tile_at[q].get(), ((size_t)n_tiles + 1) * 8, hipMemcpyDeviceToHost, s));
+            t2 = B.tmp.cap();
+            HIP_TRY(bk::prim::exclusive_sum(B.tmp.get(), t2, B.tile_n[q].get(), B.tile_at[q].get(), (size_t)n_tiles + 1, s));
+            HIP_TRY(hipMemcpyAsync((q ? at_end : at_start).data(), B.tile_at[q].get(), ((size_t)n_tiles + 1) * 8, hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(lap(T_COUNT));
@@ -334,49 +329,49 @@ int coverage(bk_ctx *c, const bk_cov_req *reqs, uint64_t n, const CovSinks &sink
             const uint64_t t_lo = (uint64_t)(std::upper_bound(at_start.begin(), at_start.end(), lo) - at_start.begin()) - 1;
             const uint64_t t_hi = (uint64_t)(std::upper_bound(at_end.begin(), at_end.end(), hi - 1) - at_end.begin()) - 1;
             if (t_hi < t_lo || t_hi >= n_tiles) return BK_ERR_INTERNAL;
-            hipLaunchKernelGGL(k_cov_emit, dim3((uint32_t)((t_hi - t_lo + kCovWaves) / kCovWaves)), dim3(kCovBlock), 0, s, c->ix, B.cov_ent_ofs.get(), e0, e1, depth, len, B.cov_tile_at[0].get(),
-                               B.cov_tile_at[1].get(), t_lo, t_hi, lo, hi, B.cov_runs.get());
+            hipLaunchKernelGGL(k_cov_emit, dim3((uint32_t)((t_hi - t_lo + kCovWaves) / kCovWaves)), dim3(kCovBlock), 0, s, c->ix, B.ent_ofs.get(), e0, e1, depth, len, B.tile_at[0].get(),
+                               B.tile_at[1].get(), t_lo, t_hi, lo, hi, B.runs.get());
             HIP_TRY(hipGetLastError());
             HIP_TRY(lap(T_EMIT));
             if (sink.runs) {
-                HIP_TRY(hipMemcpyAsync(c->cov_host, B.cov_runs.get(), (size_t)cnt * sizeof(bk_cov_run), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(B.host.get(), B.runs.get(), (size_t)cnt * sizeof(bk_cov_run), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
-                if (const int rc = sink.runs(sink.user, static_cast<const bk_cov_run *>(c->cov_host), cnt, n_runs)) return rc < 0 ? BK_ERR_INTERNAL : BK_ERR_FILEACCESS;
+                if (const int rc = sink.runs(sink.user, reinterpret_cast<const bk_cov_run *>(B.host.get()), cnt, n_runs)) return rc < 0 ? BK_ERR_INTERNAL : BK_ERR_FILEACCESS;
             } else {
                 unsigned long long bytes = 0;
-                HIP_TRY(hipMemsetAsync(B.cov_len.get() + cnt, 0, 8, s));
-                hipLaunchKernelGGL(k_cov_text_measure, dim3((cnt + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.cov_names.get(), B.cov_runs.get(), cnt, B.cov_len.get());
+                HIP_TRY(hipMemsetAsync(B.len.get() + cnt, 0, 8, s));
+                hipLaunchKernelGGL(k_cov_text_measure, dim3((cnt + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.names.get(), B.runs.get(), cnt, B.len.get());
                 HIP_TRY(hipGetLastError());
-                t2 = B.cov_tmp.cap();
-                HIP_TRY(bk::prim::exclusive_sum(B.cov_tmp.get(), t2, B.cov_len.get(), B.cov_at.get(), (size_t)cnt + 1, s));
-                HIP_TRY(hipMemcpyAsync(&bytes, B.cov_at.get() + cnt, 8, hipMemcpyDeviceToHost, s));
+                t2 = B.tmp.cap();
+                HIP_TRY(bk::prim::exclusive_sum(B.tmp.get(), t2, B.len.get(), B.at.get(), (size_t)cnt + 1, s));
+                HIP_TRY(hipMemcpyAsync(&bytes, B.at.get() + cnt, 8, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(B.cov_text.ensure(bytes));
-                hipLaunchKernelGGL(k_cov_text_write, dim3((cnt + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.cov_names.get(), B.cov_runs.get(), cnt, B.cov_at.get(),
-                                   B.cov_text.get());
+                HIP_TRY(B.text.ensure(bytes));
+                hipLaunchKernelGGL(k_cov_text_write, dim3((cnt + kCovBlock - 1) / kCovBlock), dim3(kCovBlock), 0, s, c->ix, B.names.get(), B.runs.get(), cnt, B.at.get(),
+                                   B.text.get());
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(lap(T_TEXT));
                 for (uint64_t o = 0; o < bytes; o += host_piece) {           // (a line may lie across two pieces)
                     const uint64_t piece = std::min<uint64_t>(host_piece, bytes - o);
-                    HIP_TRY(hipMemcpyAsync(c->cov_host, B.cov_text.get() + o, piece, hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipMemcpyAsync(B.host.get(), B.text.get() + o, piece, hipMemcpyDeviceToHost, s));
                     HIP_TRY(hipStreamSynchronize(s));
-                    if (const int rc = sink.text(sink.user, static_cast<const char *>(c->cov_host), piece, text_at)) return rc < 0 ? BK_ERR_INTERNAL : BK_ERR_FILEACCESS;
+                    if (const int rc = sink.text(sink.user, reinterpret_cast<const char *>(B.host.get()), piece, text_at)) return rc < 0 ? BK_ERR_INTERNAL : BK_ERR_FILEACCESS;
                     text_at += piece;
                 }
             }
             n_runs += cnt;
-            if (timing) { t_acc[T_OUT] += cov_now() - t_last; t_last = cov_now(); }
+            if (timing) { t_acc[T_OUT] += bk::now_s() - t_last; t_last = bk::now_s(); }
         }
     }
     unsigned long long tot[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, B.cov_tot.get(), sizeof(tot), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tot, B.tot.get(), sizeof(tot), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (totals) { totals->runs = n_runs; totals->covered = tot[0]; totals->depth_sum = tot[1]; totals->max_depth = tot[2]; totals->flagged = n_flagged; }
     if (timing)
         fprintf(stderr, "bk timing: coverage: %llu requests, %zu slices of up to %llu positions, %llu runs, %llu bytes of text: clear + upload %.2f, k_cov_mark %.2f, scan %.2f, k_cov_count + tile sums %.2f, "
                         "k_cov_emit %.2f, text kernels %.2f, copies + sink %.2f, whole call %.1f ms\n",
                 (unsigned long long)n, slice_first.size() - 1, (unsigned long long)max_len, (unsigned long long)n_runs, (unsigned long long)text_at, 1e3 * t_acc[T_UP], 1e3 * t_acc[T_MARK],
-                1e3 * t_acc[T_SCAN], 1e3 * t_acc[T_COUNT], 1e3 * t_acc[T_EMIT], 1e3 * t_acc[T_TEXT], 1e3 * t_acc[T_OUT], 1e3 * (cov_now() - t_start));
+                1e3 * t_acc[T_SCAN], 1e3 * t_acc[T_COUNT], 1e3 * t_acc[T_EMIT], 1e3 * t_acc[T_TEXT], 1e3 * t_acc[T_OUT], 1e3 * (bk::now_s() - t_start));
     return BK_OK;
 }
 

@@ -1,21 +1,27 @@
 // bk_ctx_int.h - internal: the context behind the C ABI (include/biokanga_amd.h), shared by bk_engine.cpp (batch driver)
 // and bk_stream.cpp (overlapped host <-> device pipeline).  Not part of the boundary.
-// Who owns what: every device allocation of a context is a bk::DevBuf, whose capacity is the buffer's own size.  The index image and the
-// grow worker's tables are bk_ctx::image (ImageBufs, filled by bk_image.cpp), the small fixed buffers (counters, phase control, the SNP
-// planes) bk_ctx::fixed (FixedBufs), and everything the batch driver and the entry points grow on demand bk_ctx::buf (BatchBufs).
-// bk_ctx_destroy frees nothing by name: release_image_buffers() and release_batch_buffers() give the lot back.  POD structs that travel to
-// kernels (DevIndex - set from the image by publish_index alone - HeavyScratch, DevBatch) carry raw pointers into them.
+// Who owns what: every device allocation of a context is a bk::DevBuf and every page-locked one a bk::PinBuf, whose capacity is the
+// buffer's own size (bk_devbuf.h).  The index image and the grow worker's tables are bk_ctx::image (ImageBufs, filled by bk_image.cpp), the
+// small fixed buffers (counters, phase control, the SNP planes) bk_ctx::fixed (FixedBufs), the engine's scratch and what the batch entry
+// points grow on demand bk_ctx::buf (BatchBufs); each request pass over finished alignments keeps its own staging (bk_stage.h: bk_ctx::snp,
+// site, primer, samtag, cov).  bk_ctx_destroy frees nothing by name: release_image_buffers(), release_batch_buffers() and
+// release_pinned_buffers() give the lot back.  POD structs that travel to kernels (DevIndex - set from the image by publish_index alone -
+// HeavyScratch, DevBatch) carry raw pointers into them.
 #pragma once
 #include <atomic>
 #include <thread>
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstring>
+#include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "bk_device.h"
 #include "bk_devbuf.h"
+#include "bk_stage.h"
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -27,7 +33,7 @@
     } while (0)
 
 namespace bk {
-// the context's device buffers that are grown on demand (capacities in elements: DevBuf::cap)
+// the engine's scratch: the device buffers the batch driver and the batch entry points grow on demand (capacities in elements: DevBuf::cap)
 struct BatchBufs {
     // batch scratch (ensure_batch_scratch: sized together by cap_reads / cap_wpr / cap_rd2w / cap_iv_cores of the context)
     DevBuf<uint64_t> rd4, rd2, iv_first;  // packed read rows (4 bit, 2 bit: DevBatch::rd4, rd2), interval records of an index beyond 2^32
@@ -47,28 +53,6 @@ struct BatchBufs {
     DevBuf<uint16_t> in_lens16;           // (packed batches only: empty, or as long as the rest of the group)
     DevBuf<uint32_t> in_words;
     DevBuf<bk_nbase> in_exc;
-    DevBuf<bk_snp_site> snp_sites;        // site list of the last bk_snp_sites call
-    DevBuf<bk_site_req> site_reqs;        // bk_site_octamers: one chunk of requests and its results
-    DevBuf<bk_site_res> site_res;
-    DevBuf<bk_primer_req> primer_reqs;    // bk_primer_correct: one chunk of requests and its results (made by its first call)
-    DevBuf<bk_primer_res> primer_res;
-    DevBuf<bk_samtag_req> samtag_reqs;    // bk_samtags: one chunk of requests, its reads' bases and where each starts in them, the answers
-    DevBuf<uint8_t> samtag_bases, samtag_tmp;     //   (made by its first call; samtag_tmp: the offset scan's temporary)
-    DevBuf<uint64_t> samtag_gofs;
-    DevBuf<uint16_t> samtag_nm;
-    DevBuf<unsigned long long> samtag_len, samtag_at;
-    DevBuf<char> samtag_text;
-    DevBuf<bk_cov_req> cov_reqs;          // bk_coverage_*: one chunk of requests and its flag bytes (everything cov_: made by the first call)
-    DevBuf<uint8_t> cov_flags, cov_tmp;   //   (cov_tmp: the scans' temporary)
-    DevBuf<int32_t> cov_depth;            // a slice's deltas, then its depth: one per base, one more behind every sequence
-    DevBuf<uint64_t> cov_ent_ofs;         // n_ent + 1: where every sequence starts when each is followed by one position that stays 0
-    DevBuf<char> cov_names;               // n_ent x 81 bytes, by entry index
-    DevBuf<uint32_t> cov_tile_n[2];       // run starts / run ends in every tile of a slice ..
-    DevBuf<unsigned long long> cov_tile_at[2];    // .. and their exclusive sums (+ 1: the slice's runs)
-    DevBuf<unsigned long long> cov_tot;   // covered positions, sum of depth, largest depth
-    DevBuf<bk_cov_run> cov_runs;          // one chunk of runs
-    DevBuf<unsigned long long> cov_len, cov_at;   // the formatter: the chunk's line lengths and where each line starts
-    DevBuf<char> cov_text;
     DevBuf<uint8_t> chrom_accept;         // bk_ctx_set_chrom_filter: by sequence id, what the PE rules ask of the -Z / -z filters
     DevBuf<unsigned long long> htab;      // HeavyScratch::htab, slot_epoch (size_heavy_scratch)
     DevBuf<uint32_t> slot_epoch;
@@ -154,15 +138,21 @@ struct bk_ctx {
     uint64_t tot_seq_len = 0;
     std::string dataset;
     std::vector<bk_entry_info> entries;
-    // SNP pile-up (count planes: fixed.snp_planes): site list of the last bk_snp_sites call (device side: buf.snp_sites)
-    std::vector<bk_snp_site> snp_sites;
-
-    bk::BatchBufs buf;                    // every device buffer that is grown on demand
-    void release_batch_buffers() { buf = bk::BatchBufs{}; }
+    bk::BatchBufs buf;                    // the engine's scratch, grown on demand
+    // the request passes' staging and chunk knobs (bk_stage.h; SNP pile-up: the count planes are fixed.snp_planes)
+    bk::SnpStage snp;
+    bk::SiteStage site;
+    bk::PrimerStage primer;
+    bk::SamtagStage samtag;
+    bk::CovStage cov;
+    void release_batch_buffers()
+    {
+        buf = bk::BatchBufs{}; snp = bk::SnpStage{}; site = bk::SiteStage{}; primer = bk::PrimerStage{}; samtag = bk::SamtagStage{}; cov = bk::CovStage{};
+    }
     // what the batch scratch was sized for (scratch_bytes_per_read, maybe_build_swin)
     uint32_t cap_reads = 0, cap_wpr = 0, cap_iv_cores = 0;
-    uint32_t *h_small = nullptr;          // pinned mirror of fixed.small (two PhaseCtl lines when the phase loop reads its counts back)
-    bk::PhaseCtl *h_ctl = nullptr;        // pinned: the last chunk's counts (fixed.ctl), copied behind its kernels
+    bk::PinBuf<uint32_t> h_small;         // pinned mirror of fixed.small (two PhaseCtl lines when the phase loop reads its counts back)
+    bk::PinBuf<bk::PhaseCtl> h_ctl;       // pinned: the last chunk's counts (fixed.ctl), copied behind its kernels
     hipEvent_t ev_ctl = nullptr;
     bool ctl_pending = false, hist_valid = false;
     uint32_t ctl_pending_reads = 0, ctl_pending_maxlen = 0;
@@ -175,8 +165,7 @@ struct bk_ctx {
     int rccl_ranks = 0;
     // the plan table (buf.plan): what it was made for - the longest read, the configuration fields make_plan reads - and the pinned
     // copy it is uploaded from (the host's own look-ups go there too).  Made again when a batch has a longer read or a field has changed.
-    uint2 *h_plan = nullptr;
-    size_t h_plan_cap = 0;
+    bk::PinBuf<uint2> h_plan;
     uint32_t plan_maxlen = 0;
     int plan_key[4] = {-1, -1, -1, -1};   // max_subs, mm_delta, min_core_len, slides_per100
     hipEvent_t ev_plan = nullptr;         // behind the last upload: the pinned copy is not written before it has been read
@@ -191,22 +180,14 @@ struct bk_ctx {
     bool dbg_by_read = false;       // the stopped phase's interval slots go by read number (bk_iv_slot.h)
     bool debug = false;      // BK_DEBUG in the environment when the context was created: per-phase counts on stderr
     uint32_t chunk_reads = 64u << 20;
-    uint64_t site_chunk = 8u << 20;       // bk_site_octamers stages this many requests at a time ("site_chunk")
-    uint64_t primer_chunk = 8u << 20;     // .. and bk_primer_correct this many ("primer_chunk")
-    uint64_t constraint_chunk = 4u << 20; // .. and bk_constraints_check this many ("constraint_chunk")
-    uint64_t samtag_chunk = 2u << 20;     // .. and bk_samtags this many ("samtag_chunk")
-    uint64_t cov_req_chunk = 8u << 20;    // .. and bk_coverage_* this many ("coverage_req_chunk")
-    uint64_t cov_slice_bases = 0;         // target bases per slice ("coverage_slice_bases"; 0: the first call derives it from the free memory)
-    uint64_t cov_run_chunk = 1u << 20;    // runs per sink call ("coverage_run_chunk")
-    void *cov_host = nullptr;             // page-locked: a chunk of runs, or a piece of text, on its way to the sink (16 bytes per run of a chunk)
-    uint64_t cov_host_cap = 0;
+    uint64_t constraint_chunk = 4u << 20; // bk_constraints_check stages this many requests at a time ("constraint_chunk"; the staging is the set's)
 
     hipEvent_t ev_wait = nullptr;         // an event the caller's thread sleeps on (bk_wait.h)
     bool entries_set = false, tgt2_built = false;     // .. and so do the entry table / the 2-bit target (made early for a window array that is made behind the upload too)
     bool tables_built = false;            // k-mer table, second-level keys, inverse suffix array exist (made behind the suffix array's upload)
     bool tables_under_way = false;        // .. are being made (tables_begin .. tables_end): publish_index leaves their pointers null
-    void *sam_text[2] = {nullptr, nullptr};   // bk_sam_format's page-locked text buffers, kept for the next call (giving page-locked memory back costs 0.1 s per GB)
-    uint64_t sam_text_cap = 0;
+    bk::PinBuf<char> sam_text[2];         // bk_sam_format's page-locked text buffers, kept for the next call (giving page-locked memory back costs 0.1 s per GB)
+    void release_pinned_buffers() { h_small.reset(); h_ctl.reset(); h_plan.reset(); sam_text[0].reset(); sam_text[1].reset(); }
     uint32_t n_chrom_accept = 0;          // entries of buf.chrom_accept (bk_ctx_set_chrom_filter)
     bk_timing timing{};
     std::vector<hipEvent_t> ev_pool;
@@ -243,16 +224,31 @@ int engine_prepare_packed(bk_ctx *c, const uint16_t *d_lens16, uint32_t nreads, 
 }  // namespace bk
 
 namespace bk {
+// bk::dev_malloc_bytes (bk_devbuf.h) is the hipMalloc for everything the library owns.  BK_POISON=<byte> (debugging aid) fills every allocation
+// with that byte, so a kernel that reads device memory nobody wrote meets the same bytes on every box, not whatever the previous process left in HBM.
+hipError_t dev_zero_now(void *p, size_t bytes);
 // Host -> device copy that runs near PCIe rate whatever the kind of host memory: pinned sources are DMA'd directly; pageable
 // ones (file mappings, std::vector) are copied by a few host threads into a pool of pinned staging buffers, each thread feeding
 // its own HIP stream, so that the DRAM / page-cache reads and the DMAs of different slices overlap (a plain hipMemcpy stages
 // through one thread: 6-8 GB/s).  Returns when the bytes are on the device.  bk_upload.cpp
-// hipMalloc for everything the context and its pipelines own.  BK_POISON=<byte> (debugging aid) fills every allocation with that byte, so a
-// kernel that reads device memory nobody wrote meets the same bytes on every box, not whatever the previous process left in HBM.
-hipError_t dev_malloc_bytes(void **p, size_t bytes);
-hipError_t dev_zero_now(void *p, size_t bytes);
-template <class T> inline hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc_bytes(reinterpret_cast<void **>(p), bytes); }
 int upload_host(void *d_dst, const void *h_src, size_t bytes, int device);
 int upload_file(void *d_dst, int fd, uint64_t file_ofs, size_t bytes, int device);       // the same from a file range, read() into the staging buffers
 bool host_is_pinned(const void *p);
+
+// what the request passes share (bk_requests.cpp)
+std::vector<uint32_t> seq_len_by_id(const bk_ctx *c);       // by sequence id; 0: no such sequence
+// part(lo, hi) over [0, n) on the caller's thread when the bytes to move are below 8 MB, else in slices on min(8, effective_cpus()) threads
+void gather_split(uint64_t total_bytes, uint32_t n, const std::function<void(uint32_t, uint32_t)> &part);
+// reads t = 0 .. n - 1 of `src`, where span_of(t) gives read t's offset and length in it, back to back into dst: read t at dst_ofs[t]
+// (~0: not this one); total_bytes is what moves
+template <class SpanOf> inline void gather_reads(uint8_t *dst, const uint64_t *dst_ofs, const uint8_t *src, uint64_t total_bytes, uint32_t n, SpanOf span_of)
+{
+    gather_split(total_bytes, n, [&](uint32_t lo, uint32_t hi) {
+        for (uint32_t t = lo; t < hi; t++) {
+            if (dst_ofs[t] == ~0ULL) continue;
+            const std::pair<uint64_t, uint32_t> sp = span_of(t);
+            memcpy(dst + dst_ofs[t], src + sp.first, sp.second);
+        }
+    });
+}
 }  // namespace bk

@@ -118,17 +118,13 @@ int plan_table_for(bk_ctx *c, uint32_t maxlen, hipStream_t s)
     if (!c->ev_plan) HIP_TRY(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming));
     else HIP_TRY(hipEventSynchronize(c->ev_plan));
     c->plan_maxlen = 0;
-    if (n > c->h_plan_cap) {
-        if (c->h_plan) { (void)hipHostFree(c->h_plan); c->h_plan = nullptr; c->h_plan_cap = 0; }
-        HIP_TRY(hipHostMalloc(&c->h_plan, n * sizeof(uint2)));
-        c->h_plan_cap = n;
-    }
+    HIP_TRY(c->h_plan.ensure(n));
     if (n > c->buf.plan.cap()) {
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(c->buf.plan.ensure(n));
     }
-    if (!plan_table_fill(c->cfg, (int)cover, rows, c->h_plan)) return BK_ERR_INTERNAL;
-    HIP_TRY(hipMemcpyAsync(c->buf.plan.get(), c->h_plan, n * sizeof(uint2), hipMemcpyHostToDevice, s));
+    if (!plan_table_fill(c->cfg, (int)cover, rows, c->h_plan.get())) return BK_ERR_INTERNAL;
+    HIP_TRY(hipMemcpyAsync(c->buf.plan.get(), c->h_plan.get(), n * sizeof(uint2), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(c->ev_plan, s));
     std::copy(key, key + 4, c->plan_key);
     c->plan_maxlen = cover;
@@ -332,22 +328,22 @@ int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipS
         HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
         uint32_t *list = c->buf.act[0].get();          // the phase work lists are free by now
         launch_loci_single(b.out, n, lc.offs.get(), lc.loci.get(), list, sm + 0, d_seg2, lc.trims.get(), s);
-        HIP_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, 16 * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        n_multi = c->h_small[0];
+        n_multi = c->h_small.get()[0];
         if (n_multi) {
             rc = size_heavy_scratch(c);
             if (rc) return rc;
             launch_loci_enum(c->ix, c->cfg, b, c->hs, list, n_multi, sm + 1, lc.offs.get(), lc.loci.get(), sm + 2, d_seg2 ? c->params.min_chimeric_len : 0,
                              maxlen > 512 ? 1 : 0, d_seg2, lc.trims.get(), s);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(c->h_small, sm, 16 * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, 16 * 4, hipMemcpyDeviceToHost, s));
         }
     }
     rc = lc.finish();
     if (rc) return rc;
-    if (n_multi && c->h_small[2] != 0) {               // a replay that did not reproduce LowHitInstances: never ignore
-        fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small[2]);
+    if (n_multi && c->h_small.get()[2] != 0) {               // a replay that did not reproduce LowHitInstances: never ignore
+        fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small.get()[2]);
         return BK_ERR_INTERNAL;
     }
     return BK_OK;
@@ -382,7 +378,7 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
 // number of 16-base dwords, which the wave kernel's length-specialised forms rely on
 int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, uint32_t minlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
 {
-    uint32_t *sm = c->fixed.small.get(), *hm = c->h_small;
+    uint32_t *sm = c->fixed.small.get(), *hm = c->h_small.get();
     HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
     const uint32_t wpr = words_per_read(maxlen);
     // register-resident window kernels handle reads of <= 128 / <= 256 / <= 16 * kNwLong / <= 16 * kNwLongest bases
@@ -429,10 +425,10 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     b.plan_stride = c->plan_maxlen + 1;
     b.plan_n = maxlen + 1;
     for (uint32_t len = 1; len <= maxlen; len++) {
-        const int n_phases = plan_unpack(c->h_plan[len]).n_phases;
+        const int n_phases = plan_unpack(c->h_plan.get()[len]).n_phases;
         max_phases = std::max(max_phases, n_phases);
         for (int ph = 0; ph < n_phases && ph <= kMaxPhases; ph++) {
-            const int nc = plan_unpack(c->h_plan[(size_t)ph * b.plan_stride + len]).nc;
+            const int nc = plan_unpack(c->h_plan.get()[(size_t)ph * b.plan_stride + len]).nc;
             if (nc > kMaxCoresFast) cores_fit = false;
             cmax_bound[ph] = std::max(cmax_bound[ph], std::min(nc, (int)kMaxCoresFast));
         }
@@ -621,7 +617,7 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
     if (no_readback) {
         // what the phases needed goes to the host on its own time: it sizes the next chunk's sorts (and says whether a read was handed to the
         // general kernel, which this schedule never launches: the core bound above rules it out)
-        HIP_TRY(hipMemcpyAsync(c->h_ctl, ctl, sizeof(PhaseCtl) * (kMaxPhases + 2), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->h_ctl.get(), ctl, sizeof(PhaseCtl) * (kMaxPhases + 2), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipEventRecord(c->ev_ctl, s));
         c->ctl_pending = true;
         c->ctl_pending_reads = n;
@@ -691,7 +687,7 @@ int take_phase_history(bk_ctx *c, bool wait)
     if (wait) HIP_TRY(bk::wait_event(c->ev_ctl));
     else if (hipEventQuery(c->ev_ctl) != hipSuccess) { (void)hipGetLastError(); return BK_OK; }
     c->ctl_pending = false;
-    const PhaseCtl *h = c->h_ctl;
+    const PhaseCtl *h = c->h_ctl.get();
     const double n = (double)std::max<uint32_t>(c->ctl_pending_reads, 1);
     for (int ph = 0; ph < kMaxPhases; ph++) {
         c->hist_slist[ph] = ph < c->ctl_pending_phases ? (double)h[ph].n_slist / n : 0.0;
@@ -742,10 +738,10 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
         HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
         launch_max_len(d_lens, nreads, c->fixed.small.get() + 5, s);
         launch_min_len(d_lens, nreads, c->fixed.small.get() + 6, s);
-        HIP_TRY(hipMemcpyAsync(c->h_small, c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        maxlen = c->h_small[5];
-        minlen = min_len_of(c->h_small[6]);
+        maxlen = c->h_small.get()[5];
+        minlen = min_len_of(c->h_small.get()[6]);
     }
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
     c->last_maxlen = maxlen;
@@ -877,7 +873,7 @@ int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_h
     }
     HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
     launch_pe(c->ix, c->cfg, b, pe->pe_mode, pe->pair_min_len, pe->pair_max_len, pe->pair_strand ? 1 : 0, d_hits, n_pairs,
-              c->buf.heavy.get(), c->fixed.small.get(), c->h_small, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
+              c->buf.heavy.get(), c->fixed.small.get(), c->h_small.get(), d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
     HIP_TRY(hipGetLastError());
     if (seg2_host && !seg2_dev) HIP_TRY(hipMemcpyAsync(seg2_host, d_seg2, (size_t)nreads * sizeof(bk_seg2), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1168,9 +1164,9 @@ int bk_pair_batch_seg2_device(bk_ctx *c, const void *d_bases, const void *d_offs
     hipStream_t s = c->stream;
     HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
     launch_max_len((const uint32_t *)d_lens, nreads, c->fixed.small.get() + 5, s);
-    HIP_TRY(hipMemcpyAsync(c->h_small, c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t maxlen = c->h_small[5];
+    const uint32_t maxlen = c->h_small.get()[5];
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
     DevReads in;
     in.bases = (const uint8_t *)d_bases; in.offs = (const uint64_t *)d_offs; in.lens = (const uint32_t *)d_lens;

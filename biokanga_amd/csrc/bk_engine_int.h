@@ -115,10 +115,9 @@ void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, cons
 // BK_TIMING=1: wall-clock of the set-up stages on stderr
 struct StageClock {
     bool on = env::timing();
-    double t0 = now();
-    static double now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+    double t0 = now_s();
     static double wall() { timespec ts; clock_gettime(CLOCK_REALTIME, &ts); return (double)(ts.tv_sec % 60) + 1e-9 * (double)ts.tv_nsec; }      // (a log's seconds)
-    void lap(const char *what) { if (!on) return; const double t = now(); fprintf(stderr, "bk timing: %-28s %7.1f ms   (done at :%06.3f)\n", what, 1e3 * (t - t0), wall()); t0 = t; }
+    void lap(const char *what) { if (!on) return; const double t = now_s(); fprintf(stderr, "bk timing: %-28s %7.1f ms   (done at :%06.3f)\n", what, 1e3 * (t - t0), wall()); t0 = t; }
 };
 
 

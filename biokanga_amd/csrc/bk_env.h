@@ -17,7 +17,7 @@ inline unsigned long long u64(const char *name, unsigned long long dflt)
 }
 
 // ---- diagnostics
-inline bool timing() { static const bool v = set("BK_TIMING"); return v; }                     // stage clocks on stderr; every hipMalloc / hipFree of more than 2 ms
+inline bool timing() { static const bool v = set("BK_TIMING"); return v; }                     // stage clocks on stderr; every allocation / free of device or page-locked memory of more than 2 ms
 inline bool debug_phases() { return set("BK_DEBUG"); }                                           // the phase loop reads its counts back and prints them per phase
 inline int poison() { static const int v = set("BK_POISON") ? atoi(getenv("BK_POISON")) : -1; return v; }      // every device allocation filled with this byte first
 inline bool inflate_debug() { static const bool v = set("BK_INFLATE_DEBUG"); return v; }       // pieces, sizes and stage times of a several-thread inflate

@@ -18,23 +18,42 @@ hipError_t dev_zero_now(void *p, size_t bytes)
     return e;
 }
 
+// the four functions every bk::DevBuf / bk::PinBuf goes through.  BK_TIMING: an allocation or a free that took the driver more than 2 ms says so
+template <class F> static hipError_t timed_driver_call(const char *what, size_t bytes, F f)
+{
+    if (!env::timing()) return f();
+    const double t0 = now_s();
+    const hipError_t e = f();
+    const double ms = 1e3 * (now_s() - t0);
+    if (ms > 2.0 && bytes) fprintf(stderr, "bk timing: %s of %.2f GB took %.1f ms\n", what, (double)bytes / 1e9, ms);
+    else if (ms > 2.0) fprintf(stderr, "bk timing: %s took %.1f ms\n", what, ms);
+    return e;
+}
+
 hipError_t dev_malloc_bytes(void **p, size_t bytes)
 {
     const int poison = env::poison();
-    const bool timing = env::timing();
-    timespec ta, tb;
-    if (timing) clock_gettime(CLOCK_MONOTONIC, &ta);
-    hipError_t e = hipMalloc(p, bytes);
-    if (timing) {          // (BK_TIMING: an allocation that took the driver more than 2 ms says so)
-        clock_gettime(CLOCK_MONOTONIC, &tb);
-        const double ms = 1e3 * (double)(tb.tv_sec - ta.tv_sec) + 1e-6 * (double)(tb.tv_nsec - ta.tv_nsec);
-        if (ms > 2.0) fprintf(stderr, "bk timing: hipMalloc of %.2f GB took %.1f ms\n", (double)bytes / 1e9, ms);
-    }
+    hipError_t e = timed_driver_call("hipMalloc", bytes, [&] { return hipMalloc(p, bytes); });
     if (e == hipSuccess && poison >= 0 && bytes) {
         e = hipMemset(*p, poison & 0xff, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();       // (a memset returns before it is done, and the contexts' streams do not wait for the null stream)
     }
     return e;
+}
+
+void free_dev(void *p)
+{
+    if (p) (void)timed_driver_call("hipFree", 0, [&] { return hipFree(p); });
+}
+
+hipError_t pin_malloc_bytes(void **p, size_t bytes)
+{
+    return timed_driver_call("hipHostMalloc", bytes, [&] { return hipHostMalloc(p, bytes, hipHostMallocDefault); });
+}
+
+void free_pin(void *p)
+{
+    if (p) (void)timed_driver_call("hipHostFree", 0, [&] { return hipHostFree(p); });
 }
 
 
@@ -90,20 +109,6 @@ int derive_cfg(bk_ctx *c)
     return BK_OK;
 }
 
-
-void free_dev(void *p)
-{
-    if (!p) return;
-    const bool timing = env::timing();
-    timespec ta, tb;
-    if (timing) clock_gettime(CLOCK_MONOTONIC, &ta);
-    (void)hipFree(p);
-    if (timing) {
-        clock_gettime(CLOCK_MONOTONIC, &tb);
-        const double ms = 1e3 * (double)(tb.tv_sec - ta.tv_sec) + 1e-6 * (double)(tb.tv_nsec - ta.tv_nsec);
-        if (ms > 2.0) fprintf(stderr, "bk timing: hipFree took %.1f ms\n", ms);
-    }
-}
 
 // zero-fill that stays correct for spans of 4 GiB and more: hipMemsetAsync is not trusted with those (bk_index.hip,
 // k_fill_u64), so large clears go through the fill kernel (8-byte words, plus a byte tail through hipMemsetAsync)
@@ -492,11 +497,11 @@ int setup_entries(bk_ctx *c, const bk_entry_info *entries, uint32_t n_entries)
     HIP_TRY(dev_zero_now(fx.ctr.get(), (size_t)kCtrStripes * 8 * 8));
     HIP_TRY(fx.small.ensure(16));
     HIP_TRY(fx.ctl.ensure(kMaxPhases + 2));
-    HIP_TRY(hipHostMalloc(&c->h_ctl, sizeof(PhaseCtl) * (kMaxPhases + 2)));
+    HIP_TRY(c->h_ctl.ensure(kMaxPhases + 2));
     HIP_TRY(bk::make_wait_event(&c->ev_ctl));
     HIP_TRY(bk::make_wait_event(&c->ev_wait));
     HIP_TRY(fx.ctr_aux.ensure(4));
-    HIP_TRY(hipHostMalloc(&c->h_small, 2 * sizeof(PhaseCtl)));
+    HIP_TRY(c->h_small.ensure(2 * sizeof(PhaseCtl) / sizeof(uint32_t)));
     int rc = derive_cfg(c);
     clk0.lap("entry table, small buffers");
     return rc;
@@ -692,7 +697,7 @@ int swin_begin(bk_ctx *c, SwinBuild &sb, const int *w, int n_levels, int words, 
     const uint64_t n_blocks = (n + (1u << kSwBlkShift) - 1) >> kSwBlkShift;
     sb.words = words;
     const uint64_t block_bytes = (uint64_t)(16 * words) << kSwBlkShift;
-    sb.t0 = StageClock::now();
+    sb.t0 = now_s();
     sb.n_levels = n_levels;
     for (int l = 0; l < n_levels; l++) sb.w[l] = w[l];
     // a run is walked whole when the copy-count check at IterCnt == 100 lets it pass: up to MaxIter + 100-odd suffixes
@@ -827,7 +832,7 @@ int swin_end(bk_ctx *c, SwinBuild &sb, hipStream_t s)
     c->swin_bytes = (uint64_t)std::max(used, sb.cap_blocks) * block_bytes + n_blocks * 4;      // (what is allocated: a sliced build's entries were sized before its coverage was known)
     c->swin_covered = (double)used / (double)n_blocks;
     publish_index(c);
-    c->swin_setup_s = StageClock::now() - sb.t0;
+    c->swin_setup_s = now_s() - sb.t0;
     return BK_OK;
 }
 
@@ -885,7 +890,7 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
     const uint64_t missing = want > have ? want - have : 0;
     const uint64_t reserve = missing * 4 / 3 + (6ULL << 30);                // (the chunk size is set from 3/4 of the free memory)
     StageClock clk;
-    const double t0 = StageClock::now();
+    const double t0 = now_s();
     if (full) {
         const uint64_t need = ((c->ix.n + 31) & ~31ULL) * 16 * (uint64_t)words;             // (whole blocks of 32 entries: sw_word_at)
         if ((uint64_t)free_b < need + reserve) { c->swin_denied = true; return BK_OK; }      // (asked once)
@@ -911,7 +916,7 @@ int maybe_build_swin(bk_ctx *c, uint32_t maxlen, uint32_t nreads, hipStream_t s)
         if (rb) { c->swin_denied = true; return BK_OK; }                   // (no room, or nothing worth covering: asked once)
     }
     publish_index(c);
-    if (full) c->swin_setup_s = StageClock::now() - t0;
+    if (full) c->swin_setup_s = now_s() - t0;
     if (clk.on) fprintf(stderr, "biokanga_amd: window array for %.1f %% of the suffix array (runs sharing %d .. %d bases, %d levels), entries of %d bytes, %.2f GB\n", 100.0 * c->swin_covered, w[0], w[n_levels - 1], n_levels, 16 * words, c->swin_bytes / 1e9);
     clk.lap("suffix-ordered windows");
     return BK_OK;
@@ -1154,14 +1159,11 @@ void bk_ctx_destroy(bk_ctx *c)
     (void)hipSetDevice(c->device);
     grow_drop(c);                         // (joins the worker: nothing writes the image from here on)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    // every device buffer, while the device is current and the stream still there: image and small fixed buffers, then everything grown on demand (bk_ctx::buf)
+    // every buffer, while the device is current and the stream still there: image and small fixed buffers, then everything grown on demand
+    // (bk_ctx::buf, the request passes' staging), then the page-locked ones
     c->release_image_buffers();
     c->release_batch_buffers();
-    if (c->h_small) (void)hipHostFree(c->h_small);
-    for (void *&t : c->sam_text) if (t) { (void)hipHostFree(t); t = nullptr; }
-    if (c->cov_host) (void)hipHostFree(c->cov_host);
-    if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    if (c->h_plan) (void)hipHostFree(c->h_plan);
+    c->release_pinned_buffers();
     if (c->ev_plan) (void)hipEventDestroy(c->ev_plan);
     if (c->ev_ctl) (void)hipEventDestroy(c->ev_ctl);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);

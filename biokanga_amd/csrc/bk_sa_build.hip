@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "bk_prim.h"
 #include "bk_env.h"
+#include "bk_devbuf.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,8 +38,7 @@ static inline unsigned grid_for(uint64_t n)
         hipError_t e__ = (expr);                                                                   \
         if (e__ != hipSuccess) {                                                                   \
             fprintf(stderr, "biokanga_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            rc = e__ == hipErrorOutOfMemory ? -95 : -1;                                            \
-            goto done;                                                                             \
+            return e__ == hipErrorOutOfMemory ? -95 : -1;                                          \
         }                                                                                          \
     } while (0)
 
@@ -245,51 +245,48 @@ __global__ void k_w_write5(const uint32_t *__restrict__ sa_lo, const uint8_t *__
 // chunk_cap: elements per stretch (0 = default 2^29); the test-suite forces small values on small inputs to run every branch
 int build_sa_device_wide(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int el_size, uint64_t chunk_cap, hipStream_t s)
 {
-    int rc = 0;
     if (n >= (1ULL << 40) || (el_size == 4 && n > 0xFFFFFFFFULL)) return -100;
     int rbits = 1;
     while ((1ULL << rbits) < n + 2) rbits++;
     const int gbits = 64 - rbits;
     uint64_t cap = chunk_cap ? chunk_cap : kWideChunkDefault;
     if (cap > (1ULL << (gbits - 1))) cap = 1ULL << (gbits - 1);         // nominal stretch; a stretch may grow to 2^gbits to end at a group boundary
-    uint32_t *sa_lo = nullptr, *rk_lo = nullptr;
-    uint8_t *sa_hi = nullptr, *rk_hi = nullptr, *sa_hi_own = nullptr;
-    unsigned long long *key[2] = {nullptr, nullptr}, *val[2] = {nullptr, nullptr}, *d_hist = nullptr, *d_small = nullptr;
-    void *tmp = nullptr;
+    uint32_t *sa_lo = nullptr;
+    uint8_t *sa_hi = nullptr;
+    DevBuf<uint32_t> rk_lo;
+    DevBuf<uint8_t> rk_hi, sa_hi_own, tmp;
+    DevBuf<unsigned long long> key[2], val[2], d_hist, d_small;
     size_t tmp_bytes = 0;
     std::vector<unsigned long long> hist(65536);
     unsigned long long h_small[4] = {0, 0, 0, 0};
-    uint64_t buf_cap = 0;
     auto ensure_bufs = [&](uint64_t m) -> hipError_t {                   // stretch buffers for m elements
-        if (m <= buf_cap) return hipSuccess;
-        for (int k = 0; k < 2; k++) { (void)hipFree(key[k]); (void)hipFree(val[k]); key[k] = val[k] = nullptr; }
-        (void)hipFree(tmp);
-        tmp = nullptr;
-        buf_cap = 0;
+        if (m <= key[0].cap()) return hipSuccess;
+        for (int k = 0; k < 2; k++) { key[k].reset(); val[k].reset(); }     // (all of them go before the first new one is made)
+        tmp.reset();
         hipError_t e = hipSuccess;
-        for (int k = 0; k < 2 && e == hipSuccess; k++) { e = hipMalloc(&key[k], m * 8); if (e == hipSuccess) e = hipMalloc(&val[k], m * 8); }
+        for (int k = 0; k < 2 && e == hipSuccess; k++) { e = key[k].ensure(m); if (e == hipSuccess) e = val[k].ensure(m); }
         size_t t1 = 0, t2 = 0, t3 = 0;
-        if (e == hipSuccess) e = bk::prim::sort_pairs(nullptr, t1, key[0], key[1], val[0], val[1], (size_t)m, 0, 64, s);
-        if (e == hipSuccess) e = bk::prim::inclusive_max(nullptr, t2, key[0], key[0], (size_t)m, s);
+        if (e == hipSuccess) e = bk::prim::sort_pairs(nullptr, t1, key[0].get(), key[1].get(), val[0].get(), val[1].get(), (size_t)m, 0, 64, s);
+        if (e == hipSuccess) e = bk::prim::inclusive_max(nullptr, t2, key[0].get(), key[0].get(), (size_t)m, s);
         if (e == hipSuccess) {
             rocprim::counting_iterator<unsigned long long> it(0ULL);
-            e = bk::prim::select_if(nullptr, t3, it, val[0], d_small, (size_t)(1ULL << 30), InBuckets{d_seq, n, 0, 0}, s);
+            e = bk::prim::select_if(nullptr, t3, it, val[0].get(), d_small.get(), (size_t)(1ULL << 30), InBuckets{d_seq, n, 0, 0}, s);
         }
         tmp_bytes = std::max(t1, std::max(t2, t3));
-        if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes);
-        if (e == hipSuccess) buf_cap = m;
+        if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
+        if (e != hipSuccess) key[0].reset();                            // (its capacity is what says the set is there)
         return e;
     };
     // sorts the m (key[0], val[0]) pairs of a stretch that starts at suffix array index j0, writes SA and ranks back
     auto sort_and_store = [&](uint64_t j0, uint64_t m, int end_bit) -> hipError_t {
         size_t tb = tmp_bytes;
-        hipError_t e = bk::prim::sort_pairs(tmp, tb, key[0], key[1], val[0], val[1], (size_t)m, 0, end_bit, s);
+        hipError_t e = bk::prim::sort_pairs(tmp.get(), tb, key[0].get(), key[1].get(), val[0].get(), val[1].get(), (size_t)m, 0, end_bit, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_w_heads, dim3(grid_for(m)), dim3(256), 0, s, key[1], m, key[0]);
+        hipLaunchKernelGGL(k_w_heads, dim3(grid_for(m)), dim3(256), 0, s, key[1].get(), m, key[0].get());
         tb = tmp_bytes;
-        e = bk::prim::inclusive_max(tmp, tb, key[0], val[0], (size_t)m, s);
+        e = bk::prim::inclusive_max(tmp.get(), tb, key[0].get(), val[0].get(), (size_t)m, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_w_store, dim3(grid_for(m)), dim3(256), 0, s, val[1], val[0], m, j0, sa_lo, sa_hi, rk_lo, rk_hi, d_small + 1);
+        hipLaunchKernelGGL(k_w_store, dim3(grid_for(m)), dim3(256), 0, s, val[1].get(), val[0].get(), m, j0, sa_lo, sa_hi, rk_lo.get(), rk_hi.get(), d_small.get() + 1);
         return hipGetLastError();
     };
 
@@ -297,15 +294,15 @@ int build_sa_device_wide(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int e
     // bytes, high bytes in the last n); the element layout the .sfx wants is produced at the end through the rank planes
     sa_lo = (uint32_t *)d_sa_out;
     if (el_size == 5) sa_hi = (uint8_t *)d_sa_out + n * 4;
-    else { SA_TRY(hipMalloc(&sa_hi_own, n)); sa_hi = sa_hi_own; }
-    SA_TRY(hipMalloc(&rk_lo, n * 4));
-    SA_TRY(hipMalloc(&rk_hi, n));
-    SA_TRY(hipMalloc(&d_hist, 65536 * 8));
-    SA_TRY(hipMalloc(&d_small, 4 * 8));
-    SA_TRY(hipMemsetAsync(d_hist, 0, 65536 * 8, s));
-    SA_TRY(hipMemsetAsync(d_small, 0, 4 * 8, s));
-    hipLaunchKernelGGL(k_w_hist, dim3(grid_for(n)), dim3(256), 0, s, d_seq, n, d_hist);
-    SA_TRY(hipMemcpyAsync(hist.data(), d_hist, 65536 * 8, hipMemcpyDeviceToHost, s));
+    else { SA_TRY(sa_hi_own.ensure(n)); sa_hi = sa_hi_own.get(); }
+    SA_TRY(rk_lo.ensure(n));
+    SA_TRY(rk_hi.ensure(n));
+    SA_TRY(d_hist.ensure(65536));
+    SA_TRY(d_small.ensure(4));
+    SA_TRY(hipMemsetAsync(d_hist.get(), 0, 65536 * 8, s));
+    SA_TRY(hipMemsetAsync(d_small.get(), 0, 4 * 8, s));
+    hipLaunchKernelGGL(k_w_hist, dim3(grid_for(n)), dim3(256), 0, s, d_seq, n, d_hist.get());
+    SA_TRY(hipMemcpyAsync(hist.data(), d_hist.get(), 65536 * 8, hipMemcpyDeviceToHost, s));
     SA_TRY(hipStreamSynchronize(s));
     {   // ---- round 0, bucket batch by bucket batch
         uint64_t biggest = 0;
@@ -323,31 +320,31 @@ int build_sa_device_wide(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int e
                     const uint64_t cnt = std::min<uint64_t>(1ULL << 30, n - at);
                     rocprim::counting_iterator<unsigned long long> it((unsigned long long)at);
                     size_t tb = tmp_bytes;
-                    SA_TRY(bk::prim::select_if(tmp, tb, it, val[0] + got, d_small, (size_t)cnt, InBuckets{d_seq, n, b0, b1}, s));
-                    SA_TRY(hipMemcpyAsync(h_small, d_small, 8, hipMemcpyDeviceToHost, s));
+                    SA_TRY(bk::prim::select_if(tmp.get(), tb, it, val[0].get() + got, d_small.get(), (size_t)cnt, InBuckets{d_seq, n, b0, b1}, s));
+                    SA_TRY(hipMemcpyAsync(h_small, d_small.get(), 8, hipMemcpyDeviceToHost, s));
                     SA_TRY(hipStreamSynchronize(s));
                     got += h_small[0];
                 }
-                if (got != m) { fprintf(stderr, "biokanga_amd: suffix sort: bucket batch holds %llu positions, %llu expected\n", (unsigned long long)got, (unsigned long long)m); rc = -1; goto done; }
-                hipLaunchKernelGGL(k_w_keys0, dim3(grid_for(m)), dim3(256), 0, s, d_seq, n, val[0], m, key[0]);
+                if (got != m) { fprintf(stderr, "biokanga_amd: suffix sort: bucket batch holds %llu positions, %llu expected\n", (unsigned long long)got, (unsigned long long)m); return -1; }
+                hipLaunchKernelGGL(k_w_keys0, dim3(grid_for(m)), dim3(256), 0, s, d_seq, n, val[0].get(), m, key[0].get());
                 SA_TRY(sort_and_store(j0, m, 64));
                 j0 += m;
             }
             b0 = b1 + 1;
         }
-        if (j0 != n) { rc = -1; goto done; }
+        if (j0 != n) return -1;
     }
     // ---- doubling rounds over stretches of the rank-sorted array
     for (uint64_t h = 16; h < (1ULL << 20); h <<= 1) {
-        SA_TRY(hipMemcpyAsync(h_small, d_small, 16, hipMemcpyDeviceToHost, s));
+        SA_TRY(hipMemcpyAsync(h_small, d_small.get(), 16, hipMemcpyDeviceToHost, s));
         SA_TRY(hipStreamSynchronize(s));
         if (h_small[1] == 0) break;                                     // every group is a single suffix
-        SA_TRY(hipMemsetAsync(d_small + 1, 0, 8, s));
+        SA_TRY(hipMemsetAsync(d_small.get() + 1, 0, 8, s));
         for (uint64_t j0 = 0; j0 < n;) {
             uint64_t j1 = n;
             if (n - j0 > cap) {
-                hipLaunchKernelGGL(k_w_next_head, dim3(1), dim3(64), 0, s, sa_lo, sa_hi, rk_lo, rk_hi, n, j0 + cap, d_small + 2);
-                SA_TRY(hipMemcpyAsync(h_small + 2, d_small + 2, 8, hipMemcpyDeviceToHost, s));
+                hipLaunchKernelGGL(k_w_next_head, dim3(1), dim3(64), 0, s, sa_lo, sa_hi, rk_lo.get(), rk_hi.get(), n, j0 + cap, d_small.get() + 2);
+                SA_TRY(hipMemcpyAsync(h_small + 2, d_small.get() + 2, 8, hipMemcpyDeviceToHost, s));
                 SA_TRY(hipStreamSynchronize(s));
                 j1 = h_small[2];
             }
@@ -361,8 +358,8 @@ int build_sa_device_wide(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int e
                 SA_TRY(hipMemcpyAsync(&hi8, sa_hi + j0 + cap, 1, hipMemcpyDeviceToHost, s));
                 SA_TRY(hipStreamSynchronize(s));
                 const uint64_t pos = (uint64_t)lo32 | ((uint64_t)hi8 << 32);
-                SA_TRY(hipMemcpyAsync(&lo32, rk_lo + pos, 4, hipMemcpyDeviceToHost, s));
-                SA_TRY(hipMemcpyAsync(&hi8, rk_hi + pos, 1, hipMemcpyDeviceToHost, s));
+                SA_TRY(hipMemcpyAsync(&lo32, rk_lo.get() + pos, 4, hipMemcpyDeviceToHost, s));
+                SA_TRY(hipMemcpyAsync(&hi8, rk_hi.get() + pos, 1, hipMemcpyDeviceToHost, s));
                 SA_TRY(hipStreamSynchronize(s));
                 const uint64_t jg = (uint64_t)lo32 | ((uint64_t)hi8 << 32);       // where the giant group starts
                 if (jg > j0) j1 = jg;
@@ -370,86 +367,78 @@ int build_sa_device_wide(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int e
             }
             const uint64_t m = j1 - j0;
             SA_TRY(ensure_bufs(m));
-            SA_TRY(hipMemsetAsync(d_small + 3, 0, 8, s));
-            hipLaunchKernelGGL(k_w_keys, dim3(grid_for(m)), dim3(256), 0, s, sa_lo, sa_hi, rk_lo, rk_hi, n, j0, m, h, rbits, single, key[0], val[0],
-                               d_small + 3);
-            SA_TRY(hipMemcpyAsync(h_small + 3, d_small + 3, 8, hipMemcpyDeviceToHost, s));
+            SA_TRY(hipMemsetAsync(d_small.get() + 3, 0, 8, s));
+            hipLaunchKernelGGL(k_w_keys, dim3(grid_for(m)), dim3(256), 0, s, sa_lo, sa_hi, rk_lo.get(), rk_hi.get(), n, j0, m, h, rbits, single, key[0].get(), val[0].get(),
+                               d_small.get() + 3);
+            SA_TRY(hipMemcpyAsync(h_small + 3, d_small.get() + 3, 8, hipMemcpyDeviceToHost, s));
             SA_TRY(hipStreamSynchronize(s));
             if (h_small[3] != 0) SA_TRY(sort_and_store(j0, m, 64));     // else: all singletons, nothing to refine here
             j0 = j1;
         }
     }
     if (el_size == 5) {
-        SA_TRY(hipMemcpyAsync(rk_lo, sa_lo, n * 4, hipMemcpyDeviceToDevice, s));
-        SA_TRY(hipMemcpyAsync(rk_hi, sa_hi, n, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_w_write5, dim3(grid_for(n)), dim3(256), 0, s, rk_lo, rk_hi, n, (uint8_t *)d_sa_out);
+        SA_TRY(hipMemcpyAsync(rk_lo.get(), sa_lo, n * 4, hipMemcpyDeviceToDevice, s));
+        SA_TRY(hipMemcpyAsync(rk_hi.get(), sa_hi, n, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_w_write5, dim3(grid_for(n)), dim3(256), 0, s, rk_lo.get(), rk_hi.get(), n, (uint8_t *)d_sa_out);
     }                                                                   // 4-byte output: the low plane is the array
     SA_TRY(hipGetLastError());
     SA_TRY(hipStreamSynchronize(s));
-done:
-    for (int k = 0; k < 2; k++) { (void)hipFree(key[k]); (void)hipFree(val[k]); }
-    (void)hipFree(tmp); (void)hipFree(sa_hi_own); (void)hipFree(rk_lo); (void)hipFree(rk_hi); (void)hipFree(d_hist); (void)hipFree(d_small);
-    return rc;
+    return 0;
 }
 
 int build_sa_device(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int el_size, hipStream_t s)
 {
-    int rc = 0;
     {
         // BK_SA_WIDE_CHUNK=<elements>: force the chunked 40-bit path (tests run it on small inputs with small stretches)
         const unsigned long long force = bk::env::sa_wide_chunk();
         if (n >= 0xFFFFFFFFULL || force > 0) return build_sa_device_wide(d_seq, n, d_sa_out, el_size, (uint64_t)force, s);
     }
-    uint64_t *key[2] = {nullptr, nullptr};
-    uint32_t *val[2] = {nullptr, nullptr};
-    uint32_t *rank = nullptr, *head = nullptr;
-    unsigned long long *d_groups = nullptr, h_groups = 0;
-    void *tmp = nullptr;
+    DevBuf<uint64_t> key[2];
+    DevBuf<uint32_t> val[2], rank;
+    DevBuf<unsigned long long> d_groups;
+    DevBuf<uint8_t> tmp;
+    uint32_t *head = nullptr;
+    unsigned long long h_groups = 0;
     size_t tmp_sort = 0, tmp_scan = 0, tmp_bytes = 0;
     int cur = 0;
     const unsigned g = grid_for(n);
 
-    SA_TRY(hipMalloc(&key[0], n * 8));
-    SA_TRY(hipMalloc(&key[1], n * 8));
-    SA_TRY(hipMalloc(&val[0], n * 4));
-    SA_TRY(hipMalloc(&val[1], n * 4));
-    SA_TRY(hipMalloc(&rank, n * 4));
-    SA_TRY(hipMalloc(&d_groups, 8));
-    head = (uint32_t *)key[0];      // key[in] is dead once sorted: its storage is reused for heads/groups
-    SA_TRY(bk::prim::sort_pairs(nullptr, tmp_sort, key[0], key[1], val[0], val[1], (size_t)n, 0, 64, s));
+    for (int k = 0; k < 2; k++) SA_TRY(key[k].ensure(n));
+    for (int k = 0; k < 2; k++) SA_TRY(val[k].ensure(n));
+    SA_TRY(rank.ensure(n));
+    SA_TRY(d_groups.ensure(1));
+    head = (uint32_t *)key[0].get();      // key[in] is dead once sorted: its storage is reused for heads/groups
+    SA_TRY(bk::prim::sort_pairs(nullptr, tmp_sort, key[0].get(), key[1].get(), val[0].get(), val[1].get(), (size_t)n, 0, 64, s));
     SA_TRY(bk::prim::inclusive_max(nullptr, tmp_scan, head, head, (size_t)n, s));
     tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
-    SA_TRY(hipMalloc(&tmp, tmp_bytes));
+    SA_TRY(tmp.ensure(tmp_bytes));
 
-    hipLaunchKernelGGL(k_sa_init, dim3(g), dim3(256), 0, s, d_seq, n, key[0], val[0]);
+    hipLaunchKernelGGL(k_sa_init, dim3(g), dim3(256), 0, s, d_seq, n, key[0].get(), val[0].get());
     for (uint64_t h = 16;; h <<= 1) {
         // sort (key[0], val[cur]) -> (key[1], val[cur^1])
         size_t tb = tmp_bytes;
-        SA_TRY(bk::prim::sort_pairs(tmp, tb, key[0], key[1], val[cur], val[cur ^ 1], (size_t)n, 0, 64, s));
+        SA_TRY(bk::prim::sort_pairs(tmp.get(), tb, key[0].get(), key[1].get(), val[cur].get(), val[cur ^ 1].get(), (size_t)n, 0, 64, s));
         cur ^= 1;
-        SA_TRY(hipMemsetAsync(d_groups, 0, 8, s));
-        head = (uint32_t *)key[0];
+        SA_TRY(hipMemsetAsync(d_groups.get(), 0, 8, s));
+        head = (uint32_t *)key[0].get();
         uint32_t *grp = head + n;   // second half of the 8n-byte key[0] buffer
-        hipLaunchKernelGGL(k_sa_heads, dim3(g), dim3(256), 0, s, key[1], n, head, d_groups);
-        SA_TRY(hipMemcpyAsync(&h_groups, d_groups, 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_sa_heads, dim3(g), dim3(256), 0, s, key[1].get(), n, head, d_groups.get());
+        SA_TRY(hipMemcpyAsync(&h_groups, d_groups.get(), 8, hipMemcpyDeviceToHost, s));
         SA_TRY(hipStreamSynchronize(s));
         if (h_groups == n || h >= (1ULL << 20)) break;
         tb = tmp_bytes;
-        SA_TRY(bk::prim::inclusive_max(tmp, tb, head, grp, (size_t)n, s));
-        hipLaunchKernelGGL(k_sa_scatter_rank, dim3(g), dim3(256), 0, s, grp, val[cur], n, rank);
-        hipLaunchKernelGGL(k_sa_make_keys, dim3(g), dim3(256), 0, s, rank, val[cur], n, h, key[0]);
+        SA_TRY(bk::prim::inclusive_max(tmp.get(), tb, head, grp, (size_t)n, s));
+        hipLaunchKernelGGL(k_sa_scatter_rank, dim3(g), dim3(256), 0, s, grp, val[cur].get(), n, rank.get());
+        hipLaunchKernelGGL(k_sa_make_keys, dim3(g), dim3(256), 0, s, rank.get(), val[cur].get(), n, h, key[0].get());
         SA_TRY(hipGetLastError());
     }
     if (el_size == 4)
-        SA_TRY(hipMemcpyAsync(d_sa_out, val[cur], n * 4, hipMemcpyDeviceToDevice, s));
+        SA_TRY(hipMemcpyAsync(d_sa_out, val[cur].get(), n * 4, hipMemcpyDeviceToDevice, s));
     else
-        hipLaunchKernelGGL(k_sa_write5, dim3(g), dim3(256), 0, s, val[cur], n, (uint8_t *)d_sa_out);
+        hipLaunchKernelGGL(k_sa_write5, dim3(g), dim3(256), 0, s, val[cur].get(), n, (uint8_t *)d_sa_out);
     SA_TRY(hipGetLastError());
     SA_TRY(hipStreamSynchronize(s));
-done:
-    (void)hipFree(key[0]); (void)hipFree(key[1]); (void)hipFree(val[0]); (void)hipFree(val[1]);
-    (void)hipFree(rank); (void)hipFree(d_groups); (void)hipFree(tmp);
-    return rc;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

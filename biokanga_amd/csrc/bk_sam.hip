@@ -15,6 +15,7 @@
 
 #include "bk_ctx_int.h"
 #include "bk_env.h"
+#include "bk_wait.h"
 #include "bk_samtags.h"
 
 namespace {
@@ -419,14 +420,10 @@ __global__ void __launch_bounds__(256) k_sam_first_exc(const bk_nbase *__restric
         if (e == 0 || exc[e - 1].read != exc[e].read) first[exc[e].read] = (uint32_t)e;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 }  // namespace
+
+using bk::DevBuf;
+using bk::PinBuf;
 
 // Records per slice.  A slice's text (150 bytes a record for 100-base reads) passes through two page-locked buffers, and page-locked memory
 // costs 0.18 s per GB to make and about as much to give back: 2 M records keep the pair at 0.6 GB and still fill the device.
@@ -434,27 +431,27 @@ constexpr uint64_t kSamSliceRecords = 2u << 20;
 
 // the read side of a job on the device: 1 byte/base reads (bases, offs) or the packed form (words, their offsets, exceptions), lengths, names
 struct SamReads {
-    DevBuf d_bases, d_offs, d_lens, d_names, d_nofs;
-    DevBuf d_words, d_wofs, d_exc, d_efirst;
+    DevBuf<uint8_t> d_bases;
+    DevBuf<uint64_t> d_offs, d_nofs;
+    DevBuf<uint32_t> d_lens;
+    DevBuf<char> d_names;
+    DevBuf<uint32_t> d_words, d_efirst;
+    DevBuf<unsigned long long> d_wofs;
+    DevBuf<bk_nbase> d_exc;
 };
 
 // what bk_sam_prepare() starts: the job's read-side arrays on their way to the device and the pinned text buffers
 struct bk_sam_prep {
     bk_ctx *ctx = nullptr;
     SamReads rd;
-    void *h_text[2] = {nullptr, nullptr};
-    uint64_t cap_text = 0;
+    PinBuf<char> h_text[2];               // (both or neither)
     uint64_t n_reads = 0, n_bases = 0, n_name_bytes = 0;
     const uint8_t *bases = nullptr;
     const uint32_t *pk_words = nullptr;
     int rc = BK_OK;
     std::thread worker;
     std::mutex join_mu;
-    ~bk_sam_prep()
-    {
-        { std::lock_guard<std::mutex> lk(join_mu); if (worker.joinable()) worker.join(); }
-        for (void *&p : h_text) if (p) { (void)hipHostFree(p); p = nullptr; }
-    }
+    ~bk_sam_prep() { std::lock_guard<std::mutex> lk(join_mu); if (worker.joinable()) worker.join(); }
 };
 
 static bool sam_job_reads_ok(const bk_sam_job *job)
@@ -467,16 +464,16 @@ static bool sam_job_reads_ok(const bk_sam_job *job)
 static int sam_upload_reads(bk_ctx *c, const bk_sam_job *job, SamReads &rd)
 {
     const uint64_t nr = job->n_reads;
-    if (rd.d_lens.alloc(nr * 4) != hipSuccess || rd.d_names.alloc(job->n_name_bytes + 16) != hipSuccess || rd.d_nofs.alloc((nr + 1) * 8) != hipSuccess) {
+    if (rd.d_lens.ensure(nr) != hipSuccess || rd.d_names.ensure(job->n_name_bytes + 16) != hipSuccess || rd.d_nofs.ensure(nr + 1) != hipSuccess) {
         (void)hipGetLastError();
         return BK_ERR_MEM;
     }
-    if (bk::upload_host(rd.d_names.p, job->names, job->n_name_bytes, c->device) || bk::upload_host(rd.d_nofs.p, job->name_ofs, nr * 8, c->device)) return BK_ERR_INTERNAL;
-    if (hipMemcpy((char *)rd.d_nofs.p + nr * 8, &job->n_name_bytes, 8, hipMemcpyHostToDevice) != hipSuccess) return BK_ERR_INTERNAL;
+    if (bk::upload_host(rd.d_names.get(), job->names, job->n_name_bytes, c->device) || bk::upload_host(rd.d_nofs.get(), job->name_ofs, nr * 8, c->device)) return BK_ERR_INTERNAL;
+    if (hipMemcpy(rd.d_nofs.get() + nr, &job->n_name_bytes, 8, hipMemcpyHostToDevice) != hipSuccess) return BK_ERR_INTERNAL;
     if (!job->pk_words) {
-        if (rd.d_bases.alloc(job->n_bases + 16) != hipSuccess || rd.d_offs.alloc(nr * 8) != hipSuccess) { (void)hipGetLastError(); return BK_ERR_MEM; }
-        if (bk::upload_host(rd.d_bases.p, job->bases, job->n_bases, c->device) || bk::upload_host(rd.d_offs.p, job->offs, nr * 8, c->device) ||
-            bk::upload_host(rd.d_lens.p, job->lens, nr * 4, c->device))
+        if (rd.d_bases.ensure(job->n_bases + 16) != hipSuccess || rd.d_offs.ensure(nr) != hipSuccess) { (void)hipGetLastError(); return BK_ERR_MEM; }
+        if (bk::upload_host(rd.d_bases.get(), job->bases, job->n_bases, c->device) || bk::upload_host(rd.d_offs.get(), job->offs, nr * 8, c->device) ||
+            bk::upload_host(rd.d_lens.get(), job->lens, nr * 4, c->device))
             return BK_ERR_INTERNAL;
         return BK_OK;
     }
@@ -488,29 +485,31 @@ static int sam_upload_reads(bk_ctx *c, const bk_sam_job *job, SamReads &rd)
     }
     // packed reads: words, 16-bit lengths and exceptions travel (page-locked buffers: plain DMA); lengths, word offsets and every read's
     // first exception are made here, on a stream of this call's own
-    DevBuf d_l16, d_nw, d_tmp;
+    DevBuf<uint16_t> d_l16;
+    DevBuf<unsigned long long> d_nw;
+    DevBuf<uint8_t> d_tmp;
     hipStream_t s = nullptr;
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return BK_ERR_INTERNAL; }
     struct Guard { hipStream_t s; ~Guard() { (void)hipStreamDestroy(s); } } guard{s};
-    if (rd.d_words.alloc((job->n_pk_words + 16) * 4) != hipSuccess || rd.d_wofs.alloc((nr + 1) * 8) != hipSuccess || d_l16.alloc(nr * 2) != hipSuccess ||
-        d_nw.alloc((nr + 1) * 8) != hipSuccess || rd.d_efirst.alloc(nr * 4) != hipSuccess || rd.d_exc.alloc((job->n_pk_exc + 1) * sizeof(bk_nbase)) != hipSuccess) {
+    if (rd.d_words.ensure(job->n_pk_words + 16) != hipSuccess || rd.d_wofs.ensure(nr + 1) != hipSuccess || d_l16.ensure(nr) != hipSuccess ||
+        d_nw.ensure(nr + 1) != hipSuccess || rd.d_efirst.ensure(nr) != hipSuccess || rd.d_exc.ensure(job->n_pk_exc + 1) != hipSuccess) {
         (void)hipGetLastError();
         return BK_ERR_MEM;
     }
-    if (bk::upload_host(rd.d_words.p, job->pk_words, job->n_pk_words * 4, c->device) || bk::upload_host(d_l16.p, job->pk_lens16, nr * 2, c->device) ||
-        (job->n_pk_exc && bk::upload_host(rd.d_exc.p, job->pk_exc, job->n_pk_exc * sizeof(bk_nbase), c->device)))
+    if (bk::upload_host(rd.d_words.get(), job->pk_words, job->n_pk_words * 4, c->device) || bk::upload_host(d_l16.get(), job->pk_lens16, nr * 2, c->device) ||
+        (job->n_pk_exc && bk::upload_host(rd.d_exc.get(), job->pk_exc, job->n_pk_exc * sizeof(bk_nbase), c->device)))
         return BK_ERR_INTERNAL;
-    hipError_t e = hipMemsetAsync((char *)d_nw.p + nr * 8, 0, 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync(rd.d_efirst.p, 0xff, nr * 4, s);
+    hipError_t e = hipMemsetAsync(d_nw.get() + nr, 0, 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(rd.d_efirst.get(), 0xff, nr * 4, s);
     if (e != hipSuccess) return BK_ERR_INTERNAL;
-    hipLaunchKernelGGL(k_sam_unpack_lens, dim3(4096), dim3(256), 0, s, d_l16.as<uint16_t>(), nr, rd.d_lens.as<uint32_t>(), d_nw.as<unsigned long long>());
-    if (job->n_pk_exc) hipLaunchKernelGGL(k_sam_first_exc, dim3(1024), dim3(256), 0, s, rd.d_exc.as<bk_nbase>(), job->n_pk_exc, rd.d_efirst.as<uint32_t>());
+    hipLaunchKernelGGL(k_sam_unpack_lens, dim3(4096), dim3(256), 0, s, d_l16.get(), nr, rd.d_lens.get(), d_nw.get());
+    if (job->n_pk_exc) hipLaunchKernelGGL(k_sam_first_exc, dim3(1024), dim3(256), 0, s, rd.d_exc.get(), job->n_pk_exc, rd.d_efirst.get());
     size_t tb = 0;
-    e = bk::prim::exclusive_sum(nullptr, tb, d_nw.as<unsigned long long>(), rd.d_wofs.as<unsigned long long>(), (size_t)nr + 1, s);
-    if (e == hipSuccess) e = d_tmp.alloc(tb + 256);
-    if (e == hipSuccess) e = bk::prim::exclusive_sum(d_tmp.p, tb, d_nw.as<unsigned long long>(), rd.d_wofs.as<unsigned long long>(), (size_t)nr + 1, s);
+    e = bk::prim::exclusive_sum(nullptr, tb, d_nw.get(), rd.d_wofs.get(), (size_t)nr + 1, s);
+    if (e == hipSuccess) e = d_tmp.ensure(tb + 256);
+    if (e == hipSuccess) e = bk::prim::exclusive_sum(d_tmp.get(), tb, d_nw.get(), rd.d_wofs.get(), (size_t)nr + 1, s);
     unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, rd.d_wofs.as<unsigned long long>() + nr, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, rd.d_wofs.get() + nr, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { (void)hipGetLastError(); return BK_ERR_INTERNAL; }
     if (total != job->n_pk_words) return BK_ERR_PARAMS;           // (the lengths do not add up to the words given)
@@ -530,10 +529,10 @@ extern "C" int bk_sam_prepare(bk_ctx *c, const bk_sam_job *job, uint32_t text_by
         if (p->rc == BK_OK && text_bytes_per_record) {
             const uint64_t slice = std::min<uint64_t>(j.n_reads, kSamSliceRecords);
             const uint64_t cap = slice * (uint64_t)text_bytes_per_record + (1u << 20);
-            bool ok = true;
-            for (int q = 0; q < 2 && ok; q++) ok = hipHostMalloc(&p->h_text[q], cap, hipHostMallocDefault) == hipSuccess;
-            if (ok) p->cap_text = cap;
-            else { (void)hipGetLastError(); for (void *&h : p->h_text) if (h) { (void)hipHostFree(h); h = nullptr; } }      // (the first slice will size them)
+            if (p->h_text[0].ensure(cap) != hipSuccess || p->h_text[1].ensure(cap) != hipSuccess) {
+                (void)hipGetLastError();
+                for (auto &h : p->h_text) h.reset();                       // (the first slice will size them)
+            }
         }
     });
     *out = p;
@@ -574,12 +573,17 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     const uint64_t nr = rj.n_reads, n_rec = job->n_reads;      // reads, records
     const uint32_t n_ent = (uint32_t)c->entries.size();
     const bool timing = bk::env::timing();
-    auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
+    auto now = bk::now_s;
     double t_mark = now(), t_dev = 0, t_settle = 0, t_pin = 0;
     auto lap = [&](const char *what) { const double t = now(); if (timing) fprintf(stderr, "bk timing: bk_sam_format %-28s %7.1f ms\n", what, 1e3 * (t - t_mark)); t_mark = t; };
     // the read store, names, records and order travel to the device once (pageable memory: staged by a few threads)
     SamReads own;
-    DevBuf d_hits, d_order, d_ent, d_bytes, d_at, d_tmp, d_cnt, d_tagnm;
+    DevBuf<bk_hit> d_hits;
+    DevBuf<uint32_t> d_order, d_cnt;
+    DevBuf<char> d_ent;
+    DevBuf<unsigned long long> d_bytes, d_at;
+    DevBuf<uint8_t> d_tmp;
+    DevBuf<uint16_t> d_tagnm;
 #define SAM_TRY(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return BK_ERR_MEM; } } while (0)
     // the read-side arrays: already on the device when bk_sam_prepare() was given these reads, else they travel now
     if (prep) {
@@ -593,61 +597,64 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     if (!prep) { int ru = sam_upload_reads(c, &rj, own); if (ru) return ru; }
     SamReads &rd = prep ? prep->rd : own;
     const bool packed = job->pk_words != nullptr;
-    SAM_TRY(d_hits.alloc(n_rec * sizeof(bk_hit)));
-    SAM_TRY(d_order.alloc(job->n_order * 4));
-    SAM_TRY(d_ent.alloc((size_t)n_ent * 81));
+    SAM_TRY(d_hits.ensure(n_rec));
+    SAM_TRY(d_order.ensure(job->n_order));
+    SAM_TRY(d_ent.ensure(std::max<size_t>((size_t)n_ent * 81, 1)));      // (a context without entries: the kernels are still handed a pointer)
     const uint32_t slice = (uint32_t)std::min<uint64_t>(job->n_order, kSamSliceRecords);
-    SAM_TRY(d_bytes.alloc(((size_t)slice + 1) * 8));
-    SAM_TRY(d_at.alloc(((size_t)slice + 1) * 8));
-    SAM_TRY(d_cnt.alloc(16));
-    if (tags) SAM_TRY(d_tagnm.alloc((size_t)slice * 2));
+    SAM_TRY(d_bytes.ensure((size_t)slice + 1));
+    SAM_TRY(d_at.ensure((size_t)slice + 1));
+    SAM_TRY(d_cnt.ensure(4));
+    if (tags) SAM_TRY(d_tagnm.ensure(slice));
     size_t tb = 0;
-    SAM_TRY(bk::prim::exclusive_sum(nullptr, tb, d_bytes.as<unsigned long long>(), d_at.as<unsigned long long>(), (size_t)slice + 1, s));
-    SAM_TRY(d_tmp.alloc(tb + 256));
-    if (bk::upload_host(d_hits.p, job->hits, n_rec * sizeof(bk_hit), c->device) || bk::upload_host(d_order.p, job->order, job->n_order * 4, c->device))
+    SAM_TRY(bk::prim::exclusive_sum(nullptr, tb, d_bytes.get(), d_at.get(), (size_t)slice + 1, s));
+    SAM_TRY(d_tmp.ensure(tb + 256));
+    if (bk::upload_host(d_hits.get(), job->hits, n_rec * sizeof(bk_hit), c->device) || bk::upload_host(d_order.get(), job->order, job->n_order * 4, c->device))
         return BK_ERR_INTERNAL;
     // what records carry besides their hits: record -> read, the reads' second segments, the records' trims
-    DevBuf d_src, d_seg2, d_tl, d_tr;
+    // (nr and n_rec are not 0 here: none of these is an empty buffer)
+    DevBuf<uint32_t> d_src;
+    DevBuf<bk_seg2> d_seg2;
+    DevBuf<uint16_t> d_tl, d_tr;
     if (job->src) {
-        SAM_TRY(d_src.alloc(n_rec * 4));
-        if (bk::upload_host(d_src.p, job->src, n_rec * 4, c->device)) return BK_ERR_INTERNAL;
+        SAM_TRY(d_src.ensure(n_rec));
+        if (bk::upload_host(d_src.get(), job->src, n_rec * 4, c->device)) return BK_ERR_INTERNAL;
     }
     if (job->seg2) {
-        SAM_TRY(d_seg2.alloc(nr * sizeof(bk_seg2)));
-        if (bk::upload_host(d_seg2.p, job->seg2, nr * sizeof(bk_seg2), c->device)) return BK_ERR_INTERNAL;
+        SAM_TRY(d_seg2.ensure(nr));
+        if (bk::upload_host(d_seg2.get(), job->seg2, nr * sizeof(bk_seg2), c->device)) return BK_ERR_INTERNAL;
     }
     if (job->trim_left) {
-        SAM_TRY(d_tl.alloc(n_rec * 2));
-        SAM_TRY(d_tr.alloc(n_rec * 2));
-        if (bk::upload_host(d_tl.p, job->trim_left, n_rec * 2, c->device) || bk::upload_host(d_tr.p, job->trim_right, n_rec * 2, c->device)) return BK_ERR_INTERNAL;
+        SAM_TRY(d_tl.ensure(n_rec));
+        SAM_TRY(d_tr.ensure(n_rec));
+        if (bk::upload_host(d_tl.get(), job->trim_left, n_rec * 2, c->device) || bk::upload_host(d_tr.get(), job->trim_right, n_rec * 2, c->device)) return BK_ERR_INTERNAL;
     }
     {
         std::vector<char> en((size_t)n_ent * 81);
         for (uint32_t e = 0; e < n_ent; e++) memcpy(&en[(size_t)e * 81], c->entries[e].name, 81);
-        HIP_TRY(hipMemcpy(d_ent.p, en.data(), en.size(), hipMemcpyHostToDevice));
+        if (!en.empty()) HIP_TRY(hipMemcpy(d_ent.get(), en.data(), en.size(), hipMemcpyHostToDevice));
     }
     lap("uploads");
     SamDev d{};
-    d.bases = packed ? nullptr : rd.d_bases.as<uint8_t>(); d.offs = rd.d_offs.as<uint64_t>(); d.lens = rd.d_lens.as<uint32_t>(); d.names = rd.d_names.as<char>();
-    d.name_ofs = rd.d_nofs.as<uint64_t>(); d.hits = d_hits.as<bk_hit>(); d.order = d_order.as<uint32_t>(); d.ent_names = d_ent.as<char>();
-    d.pk_words = rd.d_words.as<uint32_t>(); d.pk_wofs = rd.d_wofs.as<uint64_t>(); d.pk_exc = rd.d_exc.as<bk_nbase>(); d.pk_efirst = rd.d_efirst.as<uint32_t>();
+    d.bases = packed ? nullptr : rd.d_bases.get(); d.offs = rd.d_offs.get(); d.lens = rd.d_lens.get(); d.names = rd.d_names.get();
+    d.name_ofs = rd.d_nofs.get(); d.hits = d_hits.get(); d.order = d_order.get(); d.ent_names = d_ent.get();
+    d.pk_words = rd.d_words.get(); d.pk_wofs = reinterpret_cast<const uint64_t *>(rd.d_wofs.get()); d.pk_exc = rd.d_exc.get(); d.pk_efirst = rd.d_efirst.get();
     d.n_pk_exc = packed ? job->n_pk_exc : 0;
     d.n_ent = n_ent; d.fmt6 = job->report_unaligned ? 1 : 0; d.pe_mode = job->pe_mode;
-    d.src = job->src ? d_src.as<uint32_t>() : nullptr; d.seg2 = job->seg2 ? d_seg2.as<bk_seg2>() : nullptr;
-    d.trim_l = job->trim_left ? d_tl.as<uint16_t>() : nullptr; d.trim_r = job->trim_left ? d_tr.as<uint16_t>() : nullptr;
+    d.src = d_src.get(); d.seg2 = d_seg2.get();
+    d.trim_l = d_tl.get(); d.trim_r = d_tr.get();
     d.ext = (d.src || d.seg2 || d.trim_l) ? 1 : 0;
     d.tags = (int)tags;
     if (tags) {
         d.tgt4 = c->ix.tgt4; d.ent_start = c->ix.ent_start; d.ent_end = c->ix.ent_end; d.id2idx = c->ix.id2idx; d.max_id = c->ix.max_id; d.n_ix_ent = c->ix.n_ent;
-        d.tag_nm = d_tagnm.as<uint16_t>();
+        d.tag_nm = d_tagnm.get();
     }
     // does any base carry a score at all?  (one streaming pass; without scores - FASTA input, or -g3 - no record is scanned for them)
-    DevBuf d_anyq;
-    SAM_TRY(d_anyq.alloc(16));
-    SAM_TRY(hipMemsetAsync(d_anyq.p, 0, 16, s));
-    if (!packed) hipLaunchKernelGGL(k_sam_any_qual, dim3(4096), dim3(256), 0, s, d.bases, job->n_bases, d_anyq.as<uint32_t>());
+    DevBuf<uint32_t> d_anyq;
+    SAM_TRY(d_anyq.ensure(4));
+    SAM_TRY(hipMemsetAsync(d_anyq.get(), 0, 16, s));
+    if (!packed) hipLaunchKernelGGL(k_sam_any_qual, dim3(4096), dim3(256), 0, s, d.bases, job->n_bases, d_anyq.get());
     SAM_TRY(hipGetLastError());
-    d.any_qual = d_anyq.as<uint32_t>();
+    d.any_qual = d_anyq.get();
     // Everything the device indexes with is checked here first (the command line passes consistent arrays; another caller of the ABI
     // must get BK_ERR_PARAMS, not an out-of-bounds device access): chrom ids name entries 1..n, order[] names records, src[] names reads,
     // every read lies inside the bases, names are '\0'-terminated stretches in ascending order inside the name bytes.  (Trims and second
@@ -682,24 +689,20 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
         for (int b : bad) if (b) return BK_ERR_PARAMS;
     }
     lap("record check");
-    void *h_text[2] = {nullptr, nullptr};
-    DevBuf d_text[2];
-    uint64_t cap_text = 0;
-    if (prep && prep->cap_text) {                      // (the pinned text buffers came with the head start; a slice that outgrows them replaces them)
-        for (int q = 0; q < 2; q++) { h_text[q] = prep->h_text[q]; prep->h_text[q] = nullptr; }
-        cap_text = prep->cap_text;
-    } else if (c->sam_text_cap) {                      // (.. or were left by the previous call)
-        for (int q = 0; q < 2; q++) { h_text[q] = c->sam_text[q]; c->sam_text[q] = nullptr; }
-        cap_text = c->sam_text_cap;
-        c->sam_text_cap = 0;
-    }
-    if (cap_text && (d_text[0].alloc(cap_text) != hipSuccess || d_text[1].alloc(cap_text) != hipSuccess)) {
+    // the two pinned text buffers and their device twins, all four of one size (cap_text) or all empty.  The pinned pair came with the head
+    // start, or was left by the previous call; a slice that outgrows it replaces it; whatever this call holds at its end goes with it
+    // unless it is put away with the context below
+    PinBuf<char> h_text[2];
+    DevBuf<char> d_text[2];
+    auto drop_text = [&]() { for (int q = 0; q < 2; q++) { d_text[q].reset(); h_text[q].reset(); } };
+    if (prep && prep->h_text[0].cap()) for (int q = 0; q < 2; q++) h_text[q] = std::move(prep->h_text[q]);
+    else if (c->sam_text[0].cap()) for (int q = 0; q < 2; q++) h_text[q] = std::move(c->sam_text[q]);
+    uint64_t cap_text = h_text[0].cap();
+    if (cap_text && (d_text[0].ensure(cap_text) != hipSuccess || d_text[1].ensure(cap_text) != hipSuccess)) {
         (void)hipGetLastError();
-        for (int q = 0; q < 2; q++) if (d_text[q].p) { (void)hipFree(d_text[q].p); d_text[q].p = nullptr; }
-        for (void *&p : h_text) if (p) { (void)hipHostFree(p); p = nullptr; }
+        drop_text();
         cap_text = 0;
     }
-    auto free_host = [&]() { for (void *&p : h_text) if (p) { (void)hipHostFree(p); p = nullptr; } };
     int rc = BK_OK;
     uint64_t total_rep = 0, total_bytes = 0;
     // A slice's text is written into one of two device buffers, copied back by the copy stream into the pinned buffer of the same number
@@ -714,7 +717,7 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
         for (int q = 0; q < 2; q++) { if (ev_written[q]) (void)hipEventDestroy(ev_written[q]); if (ev_copied[q]) (void)hipEventDestroy(ev_copied[q]); }
         if (cs) (void)hipStreamDestroy(cs);
     };
-    if (!ev_ok) { (void)hipGetLastError(); free_events(); free_host(); return BK_ERR_INTERNAL; }
+    if (!ev_ok) { (void)hipGetLastError(); free_events(); return BK_ERR_INTERNAL; }
     std::thread sinker[2];
     int sink_rc[2] = {0, 0};
     auto settle = [&](int q) { if (sinker[q].joinable()) { sinker[q].join(); if (sink_rc[q] && rc == BK_OK) rc = sink_rc[q] < 0 ? BK_ERR_INTERNAL : BK_ERR_FILEACCESS; } };
@@ -722,16 +725,16 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     for (uint64_t k0 = 0, si = 0; k0 < job->n_order && rc == BK_OK; k0 += slice, si++) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(slice, job->n_order - k0);
         double t0 = now();
-        hipError_t e = hipMemsetAsync(d_cnt.p, 0, 16, s);
-        if (e == hipSuccess) e = hipMemsetAsync((char *)d_bytes.p + (size_t)n * 8, 0, 8, s);
-        if (tags) hipLaunchKernelGGL(k_sam_measure<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.as<unsigned long long>(), d_cnt.as<uint32_t>());
-        else hipLaunchKernelGGL(k_sam_measure<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.as<unsigned long long>(), d_cnt.as<uint32_t>());
+        hipError_t e = hipMemsetAsync(d_cnt.get(), 0, 16, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_bytes.get() + n, 0, 8, s);
+        if (tags) hipLaunchKernelGGL(k_sam_measure<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.get(), d_cnt.get());
+        else hipLaunchKernelGGL(k_sam_measure<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_bytes.get(), d_cnt.get());
         size_t t2 = tb + 256;
-        if (e == hipSuccess) e = bk::prim::exclusive_sum(d_tmp.p, t2, d_bytes.as<unsigned long long>(), d_at.as<unsigned long long>(), (size_t)n + 1, s);
+        if (e == hipSuccess) e = bk::prim::exclusive_sum(d_tmp.get(), t2, d_bytes.get(), d_at.get(), (size_t)n + 1, s);
         unsigned long long bytes = 0;
         uint32_t rep = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&bytes, d_at.as<unsigned long long>() + n, 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&rep, d_cnt.p, 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bytes, d_at.get() + n, 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&rep, d_cnt.get(), 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { rc = BK_ERR_INTERNAL; break; }
         t_dev += now() - t0;
@@ -739,12 +742,12 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
             // (the text buffers follow the largest slice seen; the first slice sizes them for the run)
             const double tp = now();
             settle(0); settle(1);
-            for (int q = 0; q < 2; q++) if (d_text[q].p) { (void)hipFree(d_text[q].p); d_text[q].p = nullptr; }
-            free_host();
+            drop_text();                                // (all four go before the first new one is made)
             cap_text = bytes + bytes / 8 + (1u << 20);
-            bool ok = d_text[0].alloc(cap_text) == hipSuccess && d_text[1].alloc(cap_text) == hipSuccess;
-            for (int q = 0; q < 2 && ok; q++) ok = hipHostMalloc(&h_text[q], cap_text, hipHostMallocDefault) == hipSuccess;
-            if (!ok) { (void)hipGetLastError(); rc = BK_ERR_MEM; break; }
+            if (d_text[0].ensure(cap_text) != hipSuccess || d_text[1].ensure(cap_text) != hipSuccess || h_text[0].ensure(cap_text) != hipSuccess ||
+                h_text[1].ensure(cap_text) != hipSuccess) {
+                (void)hipGetLastError(); rc = BK_ERR_MEM; break;
+            }
             t_pin += now() - tp;
         }
         const int q = (int)(si & 1);
@@ -753,12 +756,12 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
         t_settle += now() - t0;
         if (rc != BK_OK) break;
         t0 = now();
-        if (tags) hipLaunchKernelGGL(k_sam_write<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.as<unsigned long long>(), d_text[q].as<char>());
-        else hipLaunchKernelGGL(k_sam_write<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.as<unsigned long long>(), d_text[q].as<char>());
+        if (tags) hipLaunchKernelGGL(k_sam_write<true>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.get(), d_text[q].get());
+        else hipLaunchKernelGGL(k_sam_write<false>, dim3((n + 255) / 256), dim3(256), 0, s, d, k0, n, d_at.get(), d_text[q].get());
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ev_written[q], s);
         if (e == hipSuccess) e = hipStreamWaitEvent(cs, ev_written[q], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_text[q], d_text[q].p, bytes, hipMemcpyDeviceToHost, cs);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_text[q].get(), d_text[q].get(), bytes, hipMemcpyDeviceToHost, cs);
         if (e == hipSuccess) e = hipEventRecord(ev_copied[q], cs);
         if (e != hipSuccess) { rc = BK_ERR_INTERNAL; break; }
         t_dev += now() - t0;
@@ -766,7 +769,7 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
         const int dev = c->device;
         sinker[q] = std::thread([&, q, bytes, at, dev]() {
             if (hipSetDevice(dev) != hipSuccess || hipEventSynchronize(ev_copied[q]) != hipSuccess) { (void)hipGetLastError(); sink_rc[q] = -1; return; }
-            sink_rc[q] = bytes ? sink(user, reinterpret_cast<const char *>(h_text[q]), bytes, at) : 0;
+            sink_rc[q] = bytes ? sink(user, h_text[q].get(), bytes, at) : 0;
         });
         total_rep += rep;
         total_bytes += bytes;
@@ -775,11 +778,9 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     (void)hipStreamSynchronize(cs);
     lap("slices");
     free_events();
-    if (rc == BK_OK && h_text[0] && h_text[1] && !c->sam_text_cap) {       // kept with the context for its next call
-        for (int q = 0; q < 2; q++) { c->sam_text[q] = h_text[q]; h_text[q] = nullptr; }
-        c->sam_text_cap = cap_text;
-    }
-    free_host();
+    if (rc == BK_OK && h_text[0].cap() && h_text[1].cap() && !c->sam_text[0].cap())        // kept with the context for its next call
+        for (int q = 0; q < 2; q++) c->sam_text[q] = std::move(h_text[q]);
+    for (auto &h : h_text) h.reset();
     lap("text buffers put away");
     if (timing) fprintf(stderr, "bk timing: bk_sam_format slices: device (measure, scan, write enqueued) %.1f ms, text buffers %.1f ms, waiting for the sink %.1f ms\n",
                         1e3 * t_dev, 1e3 * t_pin, 1e3 * t_settle);

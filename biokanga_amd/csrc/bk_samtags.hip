@@ -12,6 +12,7 @@
 
 #include "bk_ctx_int.h"
 #include "bk_env.h"
+#include "bk_wait.h"
 #include "bk_samtags.h"
 
 namespace {
@@ -73,19 +74,18 @@ extern "C" int bk_samtags(bk_ctx *c, const bk_samtag_req *reqs, uint64_t n, cons
     if (!n) { if (want_md) md_ofs[0] = 0; return BK_OK; }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    bk::BatchBufs &B = c->buf;
-    const uint64_t chunk = std::min<uint64_t>(n, c->samtag_chunk);
-    HIP_TRY(B.samtag_reqs.ensure(chunk));
-    HIP_TRY(B.samtag_gofs.ensure(chunk));
-    HIP_TRY(B.samtag_nm.ensure(chunk));
-    HIP_TRY(B.samtag_len.ensure(chunk + 1));
-    HIP_TRY(B.samtag_at.ensure(chunk + 1));
+    bk::SamtagStage &B = c->samtag;
+    const uint64_t chunk = std::min<uint64_t>(n, B.chunk);
+    HIP_TRY(B.reqs.ensure(chunk));
+    HIP_TRY(B.gofs.ensure(chunk));
+    HIP_TRY(B.nm.ensure(chunk));
+    HIP_TRY(B.len.ensure(chunk + 1));
+    HIP_TRY(B.at.ensure(chunk + 1));
     size_t tb = 0;
-    HIP_TRY(bk::prim::exclusive_sum(nullptr, tb, B.samtag_len.get(), B.samtag_at.get(), (size_t)chunk + 1, s));
-    HIP_TRY(B.samtag_tmp.ensure(tb + 256));
+    HIP_TRY(bk::prim::exclusive_sum(nullptr, tb, B.len.get(), B.at.get(), (size_t)chunk + 1, s));
+    HIP_TRY(B.tmp.ensure(tb + 256));
     const bool timing = bk::env::timing();
-    auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; };
-    const double t_start = now();
+    const double t_start = bk::now_s();
     // a chunk's requests and the bases of their reads, back to back in request order, on the device
     std::vector<uint64_t> gofs(chunk);
     std::vector<uint8_t> gathered;
@@ -98,18 +98,10 @@ extern "C" int bk_samtags(bk_ctx *c, const bk_samtag_req *reqs, uint64_t n, cons
             total += q.read_len;
         }
         gathered.resize(total);
-        auto gather = [&](uint32_t lo, uint32_t hi) {
-            for (uint32_t t = lo; t < hi; t++)
-                if (gofs[t] != ~0ULL) memcpy(gathered.data() + gofs[t], bases + reqs[at + t].read_ofs, reqs[at + t].read_len);
-        };
-        const uint32_t nt = total < (8u << 20) ? 1u : 8u;
-        std::vector<std::thread> th;
-        for (uint32_t k = 1; k < nt; k++) th.emplace_back(gather, (uint32_t)((uint64_t)m * k / nt), (uint32_t)((uint64_t)m * (k + 1) / nt));
-        gather(0, (uint32_t)((uint64_t)m / nt));
-        for (auto &x : th) x.join();
-        HIP_TRY(B.samtag_bases.ensure(std::max<uint64_t>(total, 1) + 16));
-        if (bk::upload_host(B.samtag_reqs.get(), reqs + at, (size_t)m * sizeof(bk_samtag_req), c->device) ||
-            bk::upload_host(B.samtag_gofs.get(), gofs.data(), (size_t)m * 8, c->device) || (total && bk::upload_host(B.samtag_bases.get(), gathered.data(), total, c->device)))
+        bk::gather_reads(gathered.data(), gofs.data(), bases, total, m, [&](uint32_t t) { return std::make_pair(reqs[at + t].read_ofs, reqs[at + t].read_len); });
+        HIP_TRY(B.bases.ensure(std::max<uint64_t>(total, 1) + 16));
+        if (bk::upload_host(B.reqs.get(), reqs + at, (size_t)m * sizeof(bk_samtag_req), c->device) ||
+            bk::upload_host(B.gofs.get(), gofs.data(), (size_t)m * 8, c->device) || (total && bk::upload_host(B.bases.get(), gathered.data(), total, c->device)))
             return BK_ERR_INTERNAL;
         return BK_OK;
     };
@@ -121,15 +113,15 @@ extern "C" int bk_samtags(bk_ctx *c, const bk_samtag_req *reqs, uint64_t n, cons
     for (uint64_t at = 0; at < n; at += chunk) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - at);
         if (const int rc = stage(at, m)) return rc;
-        HIP_TRY(hipMemsetAsync(B.samtag_len.get() + m, 0, 8, s));
-        hipLaunchKernelGGL(k_samtags_measure, dim3((m + 255) / 256), dim3(256), 0, s, c->ix, reinterpret_cast<const uint4 *>(B.samtag_reqs.get()), m, B.samtag_bases.get(),
-                           B.samtag_gofs.get(), B.samtag_nm.get(), B.samtag_len.get());
+        HIP_TRY(hipMemsetAsync(B.len.get() + m, 0, 8, s));
+        hipLaunchKernelGGL(k_samtags_measure, dim3((m + 255) / 256), dim3(256), 0, s, c->ix, reinterpret_cast<const uint4 *>(B.reqs.get()), m, B.bases.get(),
+                           B.gofs.get(), B.nm.get(), B.len.get());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync((want_md ? nm_tmp.data() : nm_out) + at, B.samtag_nm.get(), (size_t)m * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync((want_md ? nm_tmp.data() : nm_out) + at, B.nm.get(), (size_t)m * 2, hipMemcpyDeviceToHost, s));
         if (want_md) {
             size_t t2 = tb + 256;
-            HIP_TRY(bk::prim::exclusive_sum(B.samtag_tmp.get(), t2, B.samtag_len.get(), B.samtag_at.get(), (size_t)m + 1, s));
-            HIP_TRY(hipMemcpyAsync(ofs_tmp.data() + at, B.samtag_at.get(), ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(bk::prim::exclusive_sum(B.tmp.get(), t2, B.len.get(), B.at.get(), (size_t)m + 1, s));
+            HIP_TRY(hipMemcpyAsync(ofs_tmp.data() + at, B.at.get(), ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));
         if (want_md) {
@@ -148,16 +140,16 @@ extern "C" int bk_samtags(bk_ctx *c, const bk_samtag_req *reqs, uint64_t n, cons
         const uint64_t bytes = md_ofs[at + m] - md_ofs[at];
         if (!bytes) continue;
         if (n > chunk) { if (const int rc = stage(at, m)) return rc; }
-        HIP_TRY(B.samtag_text.ensure(bytes));
-        HIP_TRY(hipMemcpyAsync(B.samtag_nm.get(), nm_out + at, (size_t)m * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(B.samtag_at.get(), md_ofs + at, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_samtags_write, dim3((m + 255) / 256), dim3(256), 0, s, c->ix, reinterpret_cast<const uint4 *>(B.samtag_reqs.get()), m, B.samtag_bases.get(),
-                           B.samtag_gofs.get(), B.samtag_nm.get(), reinterpret_cast<const uint64_t *>(B.samtag_at.get()), md_ofs[at], B.samtag_text.get());
+        HIP_TRY(B.text.ensure(bytes));
+        HIP_TRY(hipMemcpyAsync(B.nm.get(), nm_out + at, (size_t)m * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(B.at.get(), md_ofs + at, ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_samtags_write, dim3((m + 255) / 256), dim3(256), 0, s, c->ix, reinterpret_cast<const uint4 *>(B.reqs.get()), m, B.bases.get(),
+                           B.gofs.get(), B.nm.get(), reinterpret_cast<const uint64_t *>(B.at.get()), md_ofs[at], B.text.get());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(md_text + md_ofs[at], B.samtag_text.get(), bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(md_text + md_ofs[at], B.text.get(), bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     if (timing) fprintf(stderr, "bk timing: SAM tags: %llu requests in %llu chunks, %llu bytes of MD text, %.1f ms\n", (unsigned long long)n, (unsigned long long)((n + chunk - 1) / chunk),
-                        (unsigned long long)total, 1e3 * (now() - t_start));
+                        (unsigned long long)total, 1e3 * (bk::now_s() - t_start));
     return BK_OK;
 }

@@ -1,6 +1,5 @@
 // bk_snp_host.cpp - SNP pile-up and screening entry points (include/biokanga_amd.h: bk_snp_*; CAligner::ProcessSNPs, Aligner.cpp:7609-8071);
-// the kernels are in bk_snp.hip.  Beside them the other step over finished alignments: the start-site octamer gather (bk_site_*; bk_sites.hip)
-// and the 5' primer artefact correction (bk_primer_*; bk_primer.hip).
+// the kernels are in bk_snp.hip.
 #include "bk_engine_int.h"
 
 using namespace bk;
@@ -110,7 +109,7 @@ int bk_snp_sites(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, double min_non
     if (!ent) return BK_ERR_PARAMS;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    DevBuf<bk_snp_site> &d_sites = c->buf.snp_sites;
+    DevBuf<bk_snp_site> &d_sites = c->snp.d_sites;
     if (!d_sites.cap()) HIP_TRY(d_sites.ensure(1u << 20));
     unsigned long long h_tot[4] = {0, 0, 0, 0};
     uint32_t n = 0;
@@ -126,120 +125,13 @@ int bk_snp_sites(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, double min_non
         if (n <= d_sites.cap()) break;
         HIP_TRY(d_sites.ensure(n));
     }
-    c->snp_sites.resize(n);
-    if (n) HIP_TRY(hipMemcpy(c->snp_sites.data(), d_sites.get(), (size_t)n * sizeof(bk_snp_site), hipMemcpyDeviceToHost));
-    std::sort(c->snp_sites.begin(), c->snp_sites.end(), [](const bk_snp_site &a, const bk_snp_site &b) { return a.loci < b.loci; });
-    *sites = n ? c->snp_sites.data() : nullptr;
+    c->snp.sites.resize(n);
+    if (n) HIP_TRY(hipMemcpy(c->snp.sites.data(), d_sites.get(), (size_t)n * sizeof(bk_snp_site), hipMemcpyDeviceToHost));
+    std::sort(c->snp.sites.begin(), c->snp.sites.end(), [](const bk_snp_site &a, const bk_snp_site &b) { return a.loci < b.loci; });
+    *sites = n ? c->snp.sites.data() : nullptr;
     *n_sites = n;
     totals->tot_match = h_tot[0]; totals->tot_mismatch = h_tot[1]; totals->loci_covered = h_tot[2]; totals->bases_coverage = h_tot[3];
     return BK_OK;
 }
-
-// ---- start-site octamers (see include/biokanga_amd.h) ------------------------------------------
-int bk_site_octamers(bk_ctx *c, const bk_site_req *reqs, uint64_t n, int32_t rel_ofs, bk_site_res *out)
-{
-    if (!c || rel_ofs < -BK_SITE_MAX_OFS || rel_ofs > BK_SITE_MAX_OFS || (n && (!reqs || !out))) return BK_ERR_PARAMS;
-    if (!n) return BK_OK;
-    std::vector<uint8_t> known;                                              // by sequence id
-    for (const auto &e : c->entries) { if (e.entry_id >= known.size()) known.resize((size_t)e.entry_id + 1, 0); known[e.entry_id] = 1; }
-    for (uint64_t i = 0; i < n; i++) {
-        const bk_site_req &r = reqs[i];
-        if (r.chrom_id >= known.size() || !known[r.chrom_id] || (r.strand != '+' && r.strand != '-')) return BK_ERR_PARAMS;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const uint64_t chunk = std::min<uint64_t>(n, c->site_chunk);
-    HIP_TRY(c->buf.site_reqs.ensure(chunk));
-    HIP_TRY(c->buf.site_res.ensure(chunk));
-    // (BK_TIMING=1: the kernel's own time, between two events, beside the staging copies' - on stderr like the other stage clocks)
-    const bool timing = bk::env::timing();
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (timing) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); }
-    float ms_kernel = 0.f;
-    int rc = BK_OK;
-    auto one = [&](uint64_t at, uint64_t m) -> int {
-        HIP_TRY(hipMemcpyAsync(c->buf.site_reqs.get(), reqs + at, m * sizeof(bk_site_req), hipMemcpyHostToDevice, s));
-        if (timing) HIP_TRY(hipEventRecord(ev[0], s));
-        launch_site_octamers(c->ix, c->buf.site_reqs.get(), m, rel_ofs, c->buf.site_res.get(), s);
-        HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipMemcpyAsync(out + at, c->buf.site_res.get(), m * sizeof(bk_site_res), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (timing) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); ms_kernel += ms; }
-        return BK_OK;
-    };
-    for (uint64_t at = 0; at < n && !rc; at += chunk) rc = one(at, std::min(chunk, n - at));
-    if (timing) {
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-        if (!rc) fprintf(stderr, "bk timing: site octamers: %llu alignments, k_site_octamers %.3f ms in %llu launches\n", (unsigned long long)n, ms_kernel, (unsigned long long)((n + chunk - 1) / chunk));
-    }
-    return rc;
-}
-
-int bk_site_octamers_device(bk_ctx *c, const void *d_reqs, uint64_t n, int32_t rel_ofs, void *d_out, int sync)
-{
-    if (!c || rel_ofs < -BK_SITE_MAX_OFS || rel_ofs > BK_SITE_MAX_OFS || (n && (!d_reqs || !d_out)) || ((uintptr_t)d_out & 7)) return BK_ERR_PARAMS;
-    if (!n) return BK_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    launch_site_octamers(c->ix, (const bk_site_req *)d_reqs, n, rel_ofs, (bk_site_res *)d_out, c->stream);
-    HIP_TRY(hipGetLastError());
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return BK_OK;
-}
-
-// ---- 5' primer artefact correction (see include/biokanga_amd.h) ---------------------------------
-int bk_primer_correct(bk_ctx *c, const bk_primer_req *reqs, uint64_t n, bk_primer_res *out)
-{
-    if (!c || (n && (!reqs || !out))) return BK_ERR_PARAMS;
-    if (!n) return BK_OK;
-    std::vector<uint32_t> len_of;                                            // by sequence id; 0: no such sequence
-    for (const auto &e : c->entries) { if (e.entry_id >= len_of.size()) len_of.resize((size_t)e.entry_id + 1, 0); len_of[e.entry_id] = e.seq_len; }
-    for (uint64_t i = 0; i < n; i++) {
-        const bk_primer_req &r = reqs[i];
-        if (r.chrom_id >= len_of.size() || !len_of[r.chrom_id] || (r.strand != '+' && r.strand != '-') || r.match_len < BK_PRIMER_KLEN ||
-            (uint64_t)r.match_loci + r.match_len > len_of[r.chrom_id])
-            return BK_ERR_PARAMS;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const uint64_t chunk = std::min<uint64_t>(n, c->primer_chunk);
-    HIP_TRY(c->buf.primer_reqs.ensure(chunk));
-    HIP_TRY(c->buf.primer_res.ensure(chunk));
-    // (BK_TIMING=1: the kernel's own time, between two events, beside the staging copies' - on stderr like the other stage clocks)
-    const bool timing = bk::env::timing();
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (timing) { HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1])); }
-    float ms_kernel = 0.f;
-    int rc = BK_OK;
-    auto one = [&](uint64_t at, uint64_t m) -> int {
-        HIP_TRY(hipMemcpyAsync(c->buf.primer_reqs.get(), reqs + at, m * sizeof(bk_primer_req), hipMemcpyHostToDevice, s));
-        if (timing) HIP_TRY(hipEventRecord(ev[0], s));
-        launch_primer_correct(c->ix, c->buf.primer_reqs.get(), m, c->buf.primer_res.get(), s);
-        HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipMemcpyAsync(out + at, c->buf.primer_res.get(), m * sizeof(bk_primer_res), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (timing) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); ms_kernel += ms; }
-        return BK_OK;
-    };
-    for (uint64_t at = 0; at < n && !rc; at += chunk) rc = one(at, std::min(chunk, n - at));
-    if (timing) {
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-        if (!rc) fprintf(stderr, "bk timing: primer correction: %llu requests, k_primer_correct %.3f ms in %llu launches\n", (unsigned long long)n, ms_kernel, (unsigned long long)((n + chunk - 1) / chunk));
-    }
-    return rc;
-}
-
-int bk_primer_correct_device(bk_ctx *c, const void *d_reqs, uint64_t n, void *d_out, int sync)
-{
-    if (!c || (n && (!d_reqs || !d_out)) || ((uintptr_t)d_reqs & 7) || ((uintptr_t)d_out & 15)) return BK_ERR_PARAMS;
-    if (!n) return BK_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    launch_primer_correct(c->ix, (const bk_primer_req *)d_reqs, n, (bk_primer_res *)d_out, c->stream);
-    HIP_TRY(hipGetLastError());
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return BK_OK;
-}
-
 
 }  // extern "C"

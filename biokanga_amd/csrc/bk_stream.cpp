@@ -99,22 +99,16 @@ struct Job {
 };
 
 struct Slot {
-    uint8_t *d_bases = nullptr;           // 1 byte/base reads, or the words of a packed batch
-    uint16_t *d_lens16 = nullptr;
-    bk_nbase *d_exc = nullptr;            // grown on demand
-    uint64_t cap_exc = 0;
-    uint64_t *d_offs = nullptr;
-    uint32_t *d_lens = nullptr;
-    bk_hit *d_out = nullptr;
+    bk::DevBuf<uint8_t> d_bases;          // 1 byte/base reads, or the words of a packed batch
+    bk::DevBuf<uint16_t> d_lens16;
+    bk::DevBuf<bk_nbase> d_exc;           // grown on demand
+    bk::DevBuf<uint64_t> d_offs;
+    bk::DevBuf<uint32_t> d_lens;
+    bk::DevBuf<bk_hit> d_out;
     hipEvent_t ev_up = nullptr, ev_al = nullptr;
 };
 
-double now_s()
-{
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
+using bk::now_s;
 
 }  // namespace
 
@@ -126,9 +120,10 @@ struct bk_stream {
     uint64_t max_words = 0;            // != 0: packed batches only, of at most this many words
     std::vector<Slot> slots;
     hipStream_t s_up = nullptr, s_al = nullptr, s_dn = nullptr;
-    void *d_scan_tmp = nullptr;
+    bk::DevBuf<uint8_t> d_scan_tmp;
     size_t scan_tmp_bytes = 0;
-    unsigned long long *d_ext = nullptr, *h_ext = nullptr;     // [0] max read end [1] max read length [2] ~(min read length), 32 bits
+    bk::DevBuf<unsigned long long> d_ext;
+    bk::PinBuf<unsigned long long> h_ext;     // [0] max read end [1] max read length [2] ~(min read length), 32 bits
     std::thread t_up, t_al, t_dn;
     hipEvent_t ev_w_al = nullptr, ev_w_dn = nullptr;       // what the aligner and the download thread sleep on (bk_wait.h)
     std::mutex mu;
@@ -170,25 +165,18 @@ struct bk_stream {
                 // packed batch: 2 bit/base words, 16-bit lengths, the few bases that are not a,c,g,t
                 const size_t wb = (size_t)j->n_words * 4;
                 if (wb) {
-                    if (bk::host_is_pinned(j->words)) e = hipMemcpyAsync(sl.d_bases, j->words, wb, hipMemcpyHostToDevice, s_up);
-                    else if (bk::upload_host(sl.d_bases, j->words, wb, ctx->device) != BK_OK) e = hipErrorUnknown;
+                    if (bk::host_is_pinned(j->words)) e = hipMemcpyAsync(sl.d_bases.get(), j->words, wb, hipMemcpyHostToDevice, s_up);
+                    else if (bk::upload_host(sl.d_bases.get(), j->words, wb, ctx->device) != BK_OK) e = hipErrorUnknown;
                 }
-                if (e == hipSuccess) e = hipMemcpyAsync(sl.d_lens16, j->lens16, (size_t)j->n * 2, hipMemcpyHostToDevice, s_up);
-                if (e == hipSuccess && j->n_exc > sl.cap_exc) {
-                    // (the slot is idle: its previous batch has been waited for)
-                    if (sl.d_exc) (void)hipFree(sl.d_exc);
-                    sl.d_exc = nullptr;
-                    sl.cap_exc = 0;
-                    e = bk::dev_malloc(&sl.d_exc, (size_t)(j->n_exc + j->n_exc / 4 + 1024) * sizeof(bk_nbase));
-                    if (e == hipSuccess) sl.cap_exc = j->n_exc + j->n_exc / 4 + 1024;
-                }
-                if (e == hipSuccess && j->n_exc) e = hipMemcpyAsync(sl.d_exc, j->exc, (size_t)j->n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s_up);
+                if (e == hipSuccess) e = hipMemcpyAsync(sl.d_lens16.get(), j->lens16, (size_t)j->n * 2, hipMemcpyHostToDevice, s_up);
+                if (e == hipSuccess && j->n_exc > sl.d_exc.cap()) e = sl.d_exc.ensure(j->n_exc + j->n_exc / 4 + 1024);      // (the slot is idle: its previous batch has been waited for)
+                if (e == hipSuccess && j->n_exc) e = hipMemcpyAsync(sl.d_exc.get(), j->exc, (size_t)j->n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s_up);
             } else if (j->n) {
                 // the bases are the bulk: pageable buffers are staged by several threads (bk::upload_host), pinned ones DMA'd as they are
-                if (bk::host_is_pinned(j->bases)) e = hipMemcpyAsync(sl.d_bases, j->bases, j->nbases, hipMemcpyHostToDevice, s_up);
-                else if (bk::upload_host(sl.d_bases, j->bases, j->nbases, ctx->device) != BK_OK) e = hipErrorUnknown;
-                if (e == hipSuccess && j->offs) e = hipMemcpyAsync(sl.d_offs, j->offs, (size_t)j->n * 8, hipMemcpyHostToDevice, s_up);
-                if (e == hipSuccess) e = hipMemcpyAsync(sl.d_lens, j->lens, (size_t)j->n * 4, hipMemcpyHostToDevice, s_up);
+                if (bk::host_is_pinned(j->bases)) e = hipMemcpyAsync(sl.d_bases.get(), j->bases, j->nbases, hipMemcpyHostToDevice, s_up);
+                else if (bk::upload_host(sl.d_bases.get(), j->bases, j->nbases, ctx->device) != BK_OK) e = hipErrorUnknown;
+                if (e == hipSuccess && j->offs) e = hipMemcpyAsync(sl.d_offs.get(), j->offs, (size_t)j->n * 8, hipMemcpyHostToDevice, s_up);
+                if (e == hipSuccess) e = hipMemcpyAsync(sl.d_lens.get(), j->lens, (size_t)j->n * 4, hipMemcpyHostToDevice, s_up);
             }
             if (e == hipSuccess) e = hipEventRecord(sl.ev_up, s_up);
             if (e != hipSuccess) fail(j, rc_of(e));
@@ -232,13 +220,13 @@ struct bk_stream {
             if (j->rc == BK_OK && j->n && j->lens16) {
                 hipError_t e = hipStreamWaitEvent(s_al, sl.ev_up, 0);
                 uint32_t maxlen = 0, minlen = 0;
-                int rc = e == hipSuccess ? bk::engine_prepare_packed(ctx, sl.d_lens16, j->n, j->n_words, sl.d_exc, j->n_exc, sl.d_lens, sl.d_offs, &maxlen, &minlen, s_al)
+                int rc = e == hipSuccess ? bk::engine_prepare_packed(ctx, sl.d_lens16.get(), j->n, j->n_words, sl.d_exc.get(), j->n_exc, sl.d_lens.get(), sl.d_offs.get(), &maxlen, &minlen, s_al)
                                          : rc_of(e);
                 t_prep = now_s();
                 bk::DevReads in;
-                in.offs = sl.d_offs; in.lens = sl.d_lens; in.words = reinterpret_cast<const uint32_t *>(sl.d_bases); in.exc = sl.d_exc; in.n_exc = j->n_exc;
-                if (rc == BK_OK) rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen, minlen);
-                if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out, maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
+                in.offs = sl.d_offs.get(); in.lens = sl.d_lens.get(); in.words = reinterpret_cast<const uint32_t *>(sl.d_bases.get()); in.exc = sl.d_exc.get(); in.n_exc = j->n_exc;
+                if (rc == BK_OK) rc = bk::engine_align_device(ctx, in, j->n, sl.d_out.get(), s_al, maxlen, minlen);
+                if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out.get(), maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
                 if (rc) fail(j, rc);
                 else if (list_modes) {
                     j->loci_offs.swap(ctx->loci_offs);
@@ -254,26 +242,26 @@ struct bk_stream {
                 hipError_t e = hipStreamWaitEvent(s_al, sl.ev_up, 0);
                 if (e == hipSuccess && !j->offs) {          // contiguous reads: offsets = exclusive prefix sum of the lengths
                     size_t tb = scan_tmp_bytes;
-                    rocprim::transform_iterator<const uint32_t *, CastU64, unsigned long long> in(sl.d_lens, CastU64());
-                    e = bk::prim::exclusive_sum(d_scan_tmp, tb, in, (unsigned long long *)sl.d_offs, (size_t)j->n, s_al);
+                    rocprim::transform_iterator<const uint32_t *, CastU64, unsigned long long> in(sl.d_lens.get(), CastU64());
+                    e = bk::prim::exclusive_sum(d_scan_tmp.get(), tb, in, (unsigned long long *)sl.d_offs.get(), (size_t)j->n, s_al);
                 }
-                if (e == hipSuccess) e = hipMemsetAsync(d_ext, 0, 24, s_al);
+                if (e == hipSuccess) e = hipMemsetAsync(d_ext.get(), 0, 24, s_al);
                 if (e == hipSuccess) {
                     unsigned blocks = (j->n + 255) / 256;
                     if (blocks > 2048) blocks = 2048;
-                    hipLaunchKernelGGL(k_extent, dim3(blocks), dim3(256), 0, s_al, sl.d_offs, sl.d_lens, j->n, (unsigned long long)j->nbases, d_ext);
+                    hipLaunchKernelGGL(k_extent, dim3(blocks), dim3(256), 0, s_al, sl.d_offs.get(), sl.d_lens.get(), j->n, (unsigned long long)j->nbases, d_ext.get());
                     e = hipGetLastError();
                 }
-                if (e == hipSuccess) e = hipMemcpyAsync(h_ext, d_ext, 24, hipMemcpyDeviceToHost, s_al);
+                if (e == hipSuccess) e = hipMemcpyAsync(h_ext.get(), d_ext.get(), 24, hipMemcpyDeviceToHost, s_al);
                 if (e == hipSuccess) e = bk::wait_stream(s_al, ev_w_al);
                 if (e != hipSuccess) fail(j, rc_of(e));
-                else if (h_ext[0] > j->nbases || h_ext[1] > (unsigned long long)bk::kMaxReadLenAbs) fail(j, BK_ERR_PARAMS);
-                const uint32_t maxlen = (uint32_t)h_ext[1], minlen = bk::min_len_of((uint32_t)h_ext[2]);
+                else if (h_ext.get()[0] > j->nbases || h_ext.get()[1] > (unsigned long long)bk::kMaxReadLenAbs) fail(j, BK_ERR_PARAMS);
+                const uint32_t maxlen = (uint32_t)h_ext.get()[1], minlen = bk::min_len_of((uint32_t)h_ext.get()[2]);
                 if (j->rc == BK_OK) {
                     bk::DevReads in;
-                    in.bases = sl.d_bases; in.offs = sl.d_offs; in.lens = sl.d_lens;
-                    int rc = bk::engine_align_device(ctx, in, j->n, sl.d_out, s_al, maxlen, minlen);
-                    if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out, maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
+                    in.bases = sl.d_bases.get(); in.offs = sl.d_offs.get(); in.lens = sl.d_lens.get();
+                    int rc = bk::engine_align_device(ctx, in, j->n, sl.d_out.get(), s_al, maxlen, minlen);
+                    if (rc == BK_OK && has_pe) rc = bk::engine_pair_device(ctx, in, j->n / 2, sl.d_out.get(), maxlen, &pe, s_al, ctx->seg2.empty() ? nullptr : ctx->seg2.data());
                     if (rc) fail(j, rc);
                     else if (list_modes) {
                         j->loci_offs.swap(ctx->loci_offs);
@@ -310,7 +298,7 @@ struct bk_stream {
                 // results were written where the caller said and the aligner thread has waited for its last kernel
             } else if (j->n) {
                 hipError_t e = hipStreamWaitEvent(s_dn, sl.ev_al, 0);
-                if (e == hipSuccess) e = hipMemcpyAsync(j->out, sl.d_out, (size_t)j->n * sizeof(bk_hit), hipMemcpyDeviceToHost, s_dn);
+                if (e == hipSuccess) e = hipMemcpyAsync(j->out, sl.d_out.get(), (size_t)j->n * sizeof(bk_hit), hipMemcpyDeviceToHost, s_dn);
                 if (e == hipSuccess) e = bk::wait_stream(s_dn, ev_w_dn);         // (asleep until the records are back)
                 if (e != hipSuccess) fail(j, rc_of(e));
             }
@@ -371,25 +359,16 @@ void bk_stream_destroy(bk_stream *s)
     if (s->t_dn.joinable()) s->t_dn.join();
     (void)hipSetDevice(s->ctx->device);
     for (Slot &sl : s->slots) {
-        if (sl.d_bases) (void)hipFree(sl.d_bases);
-        if (sl.d_lens16) (void)hipFree(sl.d_lens16);
-        if (sl.d_exc) (void)hipFree(sl.d_exc);
-        if (sl.d_offs) (void)hipFree(sl.d_offs);
-        if (sl.d_lens) (void)hipFree(sl.d_lens);
-        if (sl.d_out) (void)hipFree(sl.d_out);
         if (sl.ev_up) (void)hipEventDestroy(sl.ev_up);
         if (sl.ev_al) (void)hipEventDestroy(sl.ev_al);
     }
-    if (s->d_scan_tmp) (void)hipFree(s->d_scan_tmp);
-    if (s->d_ext) (void)hipFree(s->d_ext);
-    if (s->h_ext) (void)hipHostFree(s->h_ext);
     if (s->s_up) (void)hipStreamDestroy(s->s_up);
     if (s->s_al) (void)hipStreamDestroy(s->s_al);
     if (s->s_dn) (void)hipStreamDestroy(s->s_dn);
     if (s->ev_w_al) (void)hipEventDestroy(s->ev_w_al);
     if (s->ev_w_dn) (void)hipEventDestroy(s->ev_w_dn);
     for (auto &kv : s->jobs) delete kv.second;
-    delete s;
+    delete s;                             // (the buffers go with their owners, while the device is current)
 }
 
 static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads, uint64_t max_batch_bases, uint64_t max_batch_words, int depth, const bk_pe_params *pe);
@@ -434,11 +413,11 @@ static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads,
             // (either form of a batch: max_batch_bases bytes, or one word per 16 bases and at most one more per read)
             //  + the words the read preparation may load behind the last read of a packed batch, bk::kPackedPadWords)
             const uint64_t bytes = packed_only ? 4ULL * max_batch_words : std::max<uint64_t>(max_batch_bases, max_batch_bases / 4 + 4ULL * max_batch_reads);
-            if (e2 == hipSuccess) e2 = bk::dev_malloc(&sl.d_bases, bytes + 64 + 4ULL * bk::kPackedPadWords);
-            if (e2 == hipSuccess) e2 = bk::dev_malloc(&sl.d_lens16, (size_t)max_batch_reads * 2);
-            if (e2 == hipSuccess) e2 = bk::dev_malloc(&sl.d_offs, (size_t)max_batch_reads * 8);
-            if (e2 == hipSuccess) e2 = bk::dev_malloc(&sl.d_lens, (size_t)max_batch_reads * 4);
-            if (e2 == hipSuccess) e2 = bk::dev_malloc(&sl.d_out, (size_t)max_batch_reads * sizeof(bk_hit));
+            if (e2 == hipSuccess) e2 = sl.d_bases.ensure(bytes + 64 + 4ULL * bk::kPackedPadWords);
+            if (e2 == hipSuccess) e2 = sl.d_lens16.ensure(max_batch_reads);
+            if (e2 == hipSuccess) e2 = sl.d_offs.ensure(max_batch_reads);
+            if (e2 == hipSuccess) e2 = sl.d_lens.ensure(max_batch_reads);
+            if (e2 == hipSuccess) e2 = sl.d_out.ensure(max_batch_reads);
         }
         return e2;
     };
@@ -447,10 +426,7 @@ static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads,
         if (e == hipErrorOutOfMemory && ctx->image.swin.get()) {
             // the context's window array (half of the HBM) goes before the pipeline is refused its buffers
             (void)hipGetLastError();
-            for (Slot &sl : s->slots) {
-                for (void **pp : {(void **)&sl.d_bases, (void **)&sl.d_lens16, (void **)&sl.d_offs, (void **)&sl.d_lens, (void **)&sl.d_out})
-                    if (*pp) { (void)hipFree(*pp); *pp = nullptr; }
-            }
+            for (Slot &sl : s->slots) sl = Slot{};         // (what the first attempt got; the events are made below)
             bk::release_swin(ctx);
             e = alloc_slots();
         }
@@ -463,9 +439,9 @@ static int stream_create(bk_stream **out, bk_ctx *ctx, uint32_t max_batch_reads,
         rocprim::transform_iterator<const uint32_t *, CastU64, unsigned long long> in(nullptr, CastU64());
         e = bk::prim::exclusive_sum(nullptr, s->scan_tmp_bytes, in, (unsigned long long *)nullptr, (size_t)max_batch_reads, s->s_al);
     }
-    if (e == hipSuccess) e = bk::dev_malloc(&s->d_scan_tmp, s->scan_tmp_bytes ? s->scan_tmp_bytes : 16);
-    if (e == hipSuccess) e = bk::dev_malloc(&s->d_ext, 24);
-    if (e == hipSuccess) e = hipHostMalloc(&s->h_ext, 24, hipHostMallocDefault);
+    if (e == hipSuccess) e = s->d_scan_tmp.ensure(s->scan_tmp_bytes ? s->scan_tmp_bytes : 16);
+    if (e == hipSuccess) e = s->d_ext.ensure(3);
+    if (e == hipSuccess) e = s->h_ext.ensure(3);
     if (e != hipSuccess) {
         fprintf(stderr, "biokanga_amd: bk_stream_create: %s\n", hipGetErrorString(e));
         s->next_ticket = 1;

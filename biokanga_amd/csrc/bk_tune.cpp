@@ -71,65 +71,30 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->cfg.heavy_thresh = (int)value;     // 0 routes every call with a non-empty interval to k_heavy
         return old;
     }
-    if (n == "chunk_reads") {
-        int64_t old = c->chunk_reads;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->chunk_reads = (uint32_t)value;
+    // the chunk knobs: a plain number within bounds, no side effect; the old value comes back
+    const struct { const char *name; uint32_t *p32; uint64_t *p64; int64_t lo, hi; } chunk_knobs[] = {
+        {"chunk_reads", &c->chunk_reads, nullptr, 1, 1LL << 30},                  // reads per pass over the phases
+        {"site_chunk", nullptr, &c->site.chunk, 1, 1LL << 30},                    // requests bk_site_octamers stages at a time
+        {"primer_chunk", nullptr, &c->primer.chunk, 1, 1LL << 30},                // .. bk_primer_correct
+        {"constraint_chunk", nullptr, &c->constraint_chunk, 1, 1LL << 30},        // .. bk_constraints_check
+        {"samtag_chunk", nullptr, &c->samtag.chunk, 1, 1LL << 30},                // .. bk_samtags
+        {"coverage_req_chunk", nullptr, &c->cov.req_chunk, 1, 1LL << 30},         // .. bk_coverage_*
+        {"coverage_slice_bases", nullptr, &c->cov.slice_bases, 0, INT64_MAX},     // target bases per slice; 0 (the default): the next call derives it from the free memory
+        {"coverage_run_chunk", nullptr, &c->cov.run_chunk, 1, 1LL << 26},         // runs per sink call
+        {"wave_waves", &c->wave_waves, nullptr, 64, 65536},                       // resident waves the wave kernel is launched with
+    };
+    for (const auto &k : chunk_knobs) {
+        if (n != k.name) continue;
+        const int64_t old = k.p32 ? (int64_t)*k.p32 : (int64_t)*k.p64;
+        if (value < k.lo || value > k.hi) return BK_ERR_PARAMS;
+        if (k.p32) *k.p32 = (uint32_t)value;
+        else *k.p64 = (uint64_t)value;
         return old;
     }
-    if (n == "site_chunk") {               // requests bk_site_octamers stages at a time
-        int64_t old = (int64_t)c->site_chunk;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->site_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "primer_chunk") {             // requests bk_primer_correct stages at a time
-        int64_t old = (int64_t)c->primer_chunk;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->primer_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "constraint_chunk") {         // requests bk_constraints_check stages at a time
-        int64_t old = (int64_t)c->constraint_chunk;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->constraint_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "samtag_chunk") {             // requests bk_samtags stages at a time
-        int64_t old = (int64_t)c->samtag_chunk;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->samtag_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "samtag_buf_bytes")           // (read only) what bk_samtags' staging holds now: 0 until its first call
-        return (int64_t)(c->buf.samtag_reqs.cap() * sizeof(bk_samtag_req) + c->buf.samtag_bases.cap() + c->buf.samtag_tmp.cap() + c->buf.samtag_gofs.cap() * 8 +
-                         c->buf.samtag_nm.cap() * 2 + (c->buf.samtag_len.cap() + c->buf.samtag_at.cap()) * 8 + c->buf.samtag_text.cap());
-    if (n == "coverage_req_chunk") {       // requests bk_coverage_* stages at a time
-        int64_t old = (int64_t)c->cov_req_chunk;
-        if (value < 1 || value > (1LL << 30)) return BK_ERR_PARAMS;
-        c->cov_req_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "coverage_slice_bases") {     // target bases per slice; 0 (the default): the next call derives it from the free memory
-        int64_t old = (int64_t)c->cov_slice_bases;
-        if (value < 0) return BK_ERR_PARAMS;
-        c->cov_slice_bases = (uint64_t)value;
-        return old;
-    }
-    if (n == "coverage_run_chunk") {       // runs per sink call
-        int64_t old = (int64_t)c->cov_run_chunk;
-        if (value < 1 || value > (1LL << 26)) return BK_ERR_PARAMS;
-        c->cov_run_chunk = (uint64_t)value;
-        return old;
-    }
-    if (n == "coverage_buf_bytes") {       // (read only) what bk_coverage_*'s staging holds now, device and page-locked: 0 until its first call
-        const bk::BatchBufs &B = c->buf;
-        return (int64_t)(B.cov_reqs.cap() * sizeof(bk_cov_req) + B.cov_flags.cap() + B.cov_tmp.cap() + B.cov_depth.cap() * 4 + B.cov_ent_ofs.cap() * 8 + B.cov_names.cap() +
-                         (B.cov_tile_n[0].cap() + B.cov_tile_n[1].cap()) * 4 + (B.cov_tile_at[0].cap() + B.cov_tile_at[1].cap() + B.cov_tot.cap() + B.cov_len.cap() + B.cov_at.cap()) * 8 +
-                         B.cov_runs.cap() * sizeof(bk_cov_run) + B.cov_text.cap() + c->cov_host_cap);
-    }
-    if (n == "primer_buf_bytes")          // (read only) what bk_primer_correct's staging holds now: 0 until its first call
-        return (int64_t)(c->buf.primer_reqs.cap() * sizeof(bk_primer_req) + c->buf.primer_res.cap() * sizeof(bk_primer_res));
+    // (read only) what a request pass's staging holds now, device and page-locked: 0 until its first call
+    if (n == "samtag_buf_bytes") return (int64_t)c->samtag.bytes();
+    if (n == "coverage_buf_bytes") return (int64_t)c->cov.bytes();
+    if (n == "primer_buf_bytes") return (int64_t)c->primer.bytes();
     if (n == "kmer_bits" || n == "use_ktab") {
         int64_t old = n == "use_ktab" ? c->use_ktab : c->ix.k;
         if (n == "use_ktab") c->use_ktab = value ? 1 : 0;
@@ -191,12 +156,6 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         c->use_tgt2 = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
         int rc = build_tgt2(c);
         return rc ? rc : old;
-    }
-    if (n == "wave_waves") {
-        int64_t old = c->wave_waves;
-        if (value < 64 || value > 65536) return BK_ERR_PARAMS;
-        c->wave_waves = (uint32_t)value;
-        return old;
     }
     if (n == "wave_len_spec") {            // host only: which form of the wave kernel is launched, never what it computes
         int64_t old = c->wave_len_spec;

@@ -1,7 +1,8 @@
-// bk_wait.h - how host threads wait for the GPU.
+// bk_wait.h - how host threads wait for the GPU, and the clock they read.
 #pragma once
 #include <atomic>
 #include <stdlib.h>
+#include <time.h>
 
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,9 @@
 #include "bk_env.h"
 
 namespace bk {
+
+// the library's one monotonic clock, in seconds (BK_TIMING's stage clocks, the pipelines' busy times)
+inline double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 // hipStreamSynchronize spins on the CPU until the GPU is done: the shortest wait there is, and what a pipeline's three threads do when
 // the process has CPUs to spare.  When it has not, the threads sleep on events made with hipEventBlockingSync instead, so that they do
