@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = [
     "bk_contam_create", "bk_contam_destroy", "bk_contam_match",
     "bk_samtags", "bk_sam_format_tags",
     "bk_coverage_runs", "bk_coverage_text",
+    "bk_mark_duplicates",
 ]
 
 
@@ -89,6 +90,11 @@ COV_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("pos", "<u4"), ("m", "<u2"), ("m
 COV_RUN_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])
 assert COV_REQ_DTYPE.itemsize == 16 and COV_RUN_DTYPE.itemsize == 16
 COV_TOTALS = ("runs", "covered", "depth_sum", "max_depth", "flagged")
+# bk_dup_req: one TEMPLATE of bk_mark_duplicates - the unclipped 5' position(s) and strand(s) of a fragment (strand_mate 0) or a pair, and its score
+DUP_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("pos5", "<i4"), ("pos5_mate", "<i4"), ("strand", "u1"), ("strand_mate", "u1"), ("score", "<u2")])
+assert DUP_REQ_DTYPE.itemsize == 16
+DUP_TOTALS = ("templates", "groups", "duplicates", "max_group", "flagged")
+DUP_KEPT, DUP_DUPLICATE, DUP_FLAGGED = 0, 1, 2
 MAX_CONSTRAINED_SEQS, MAX_CONSTRAINTS, CONSTRAINT_R = 64, 6400, 0x10
 CONSTRAINT_UNTOUCHED, CONSTRAINT_TOUCHED, CONSTRAINT_VIOLATED, CONSTRAINT_BAD = 0, 1, 2, 0x80
 CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("mask", "u1"), ("_r", "u1", (3,))])
@@ -140,7 +146,7 @@ class _SamJob(ctypes.Structure):
                 ("pk_words", ctypes.c_void_p), ("n_pk_words", ctypes.c_uint64), ("pk_lens16", ctypes.c_void_p),
                 ("pk_exc", ctypes.c_void_p), ("n_pk_exc", ctypes.c_uint64),
                 ("src", ctypes.c_void_p), ("n_src_reads", ctypes.c_uint64), ("seg2", ctypes.c_void_p),
-                ("trim_left", ctypes.c_void_p), ("trim_right", ctypes.c_void_p)]
+                ("trim_left", ctypes.c_void_p), ("trim_right", ctypes.c_void_p), ("dup", ctypes.c_void_p)]
 
 
 _SAM_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
@@ -316,6 +322,8 @@ def load_library():
     lib.bk_coverage_runs.restype = i32
     lib.bk_coverage_text.argtypes = [vp, vp, u64, _SAM_SINK, vp, ctypes.POINTER(u64 * 5)]
     lib.bk_coverage_text.restype = i32
+    lib.bk_mark_duplicates.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64 * 5)]
+    lib.bk_mark_duplicates.restype = i32
     lib.bk_contam_create.argtypes = [ctypes.POINTER(vp), i32, vp, u32]
     lib.bk_contam_create.restype = i32
     lib.bk_contam_destroy.argtypes = [vp]
@@ -815,12 +823,24 @@ class Aligner:
             raise BkError(rc, "bk_coverage_text")
         return b"".join(parts), dict(zip(COV_TOTALS, (int(v) for v in tot))), [len(p) for p in parts]
 
+    def mark_duplicates(self, reqs):
+        """bk_mark_duplicates: DUP_REQ_DTYPE templates -> (one byte per request: DUP_KEPT, DUP_DUPLICATE or DUP_FLAGGED, totals as a
+        dict of DUP_TOTALS).  Among equal keys the highest score is kept, the earlier request among equal scores."""
+        reqs = np.ascontiguousarray(reqs, dtype=DUP_REQ_DTYPE)
+        out = np.zeros(len(reqs), dtype=np.uint8)
+        tot = (ctypes.c_uint64 * 5)()
+        rc = self.lib.bk_mark_duplicates(self.h, reqs.ctypes.data if len(reqs) else None, len(reqs), out.ctypes.data if len(reqs) else None, ctypes.byref(tot))
+        if rc:
+            raise BkError(rc, "bk_mark_duplicates")
+        return out, dict(zip(DUP_TOTALS, (int(v) for v in tot)))
+
     def sam_format(self, bases, offs, lens, names, hits, order, report_unaligned=True, pe_mode=0, *, src=None, seg2=None,
-                   trim_left=None, trim_right=None, tags=None, packed=False):
+                   trim_left=None, trim_right=None, tags=None, packed=False, dup=None):
         """bk_sam_format: the SAM body of `hits` in the order given, as bytes.  `names`: a list of bytes, one per read.  Without `src`
         hits go by read; with it (record -> read) hits, order and the trims go by record, the read store and seg2 by read.
         tags: None, or the mask of bk_sam_format_tags (SAMTAG_NM | SAMTAG_MD; 0 is allowed).  packed: the reads travel in the packed
-        form of pack_reads (they must lie back to back in `bases`, in read order)."""
+        form of pack_reads (they must lie back to back in `bases`, in read order).  dup: None, or a byte per record - non-zero adds 0x400
+        to the FLAG of an accepted record."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
@@ -835,7 +855,8 @@ class Aligner:
                       order=order.ctypes.data, n_order=len(order), report_unaligned=1 if report_unaligned else 0, pe_mode=pe_mode)
         keep = []
         for field, arr, dt, n in (("src", src, np.uint32, len(hits)), ("seg2", seg2, SEG2_DTYPE, len(lens)),
-                                  ("trim_left", trim_left, np.uint16, len(hits)), ("trim_right", trim_right, np.uint16, len(hits))):
+                                  ("trim_left", trim_left, np.uint16, len(hits)), ("trim_right", trim_right, np.uint16, len(hits)),
+                                  ("dup", dup, np.uint8, len(hits))):
             if arr is None:
                 continue
             arr = np.ascontiguousarray(arr, dtype=dt)

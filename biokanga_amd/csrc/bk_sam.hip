@@ -45,6 +45,7 @@ struct SamDev {
     const bk_seg2 *seg2;
     const uint16_t *trim_l, *trim_r;
     int ext;                         // any of the four is there: the kernels ask this first, so plain jobs never look at a record for them
+    const uint8_t *dup;              // null, or by record: non-zero = a duplicate (bk_mark_duplicates): an accepted record's FLAG gets 0x400
     // bk_sam_format_tags (tags = 0: none of this is looked at): the mask, the indexed target with its entry table, and per record of the
     // slice the NM the measuring pass found (bk::kTagNone: the record gets no tags), which the writing pass places the MD text by
     int tags;
@@ -181,6 +182,7 @@ __device__ __forceinline__ SamRec sam_rec(const SamDev &d, uint64_t k)
         } else
             r.flag |= 0x8;
     }
+    if (d.dup && r.acc && d.dup[r.i]) r.flag |= 0x400;         // (before either pass measures or writes the flag)
     return r;
 }
 
@@ -615,6 +617,11 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     DevBuf<uint32_t> d_src;
     DevBuf<bk_seg2> d_seg2;
     DevBuf<uint16_t> d_tl, d_tr;
+    DevBuf<uint8_t> d_dup;
+    if (job->dup) {
+        SAM_TRY(d_dup.ensure(n_rec));
+        if (bk::upload_host(d_dup.get(), job->dup, n_rec, c->device)) return BK_ERR_INTERNAL;
+    }
     if (job->src) {
         SAM_TRY(d_src.ensure(n_rec));
         if (bk::upload_host(d_src.get(), job->src, n_rec * 4, c->device)) return BK_ERR_INTERNAL;
@@ -643,6 +650,7 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     d.src = d_src.get(); d.seg2 = d_seg2.get();
     d.trim_l = d_tl.get(); d.trim_r = d_tr.get();
     d.ext = (d.src || d.seg2 || d.trim_l) ? 1 : 0;
+    d.dup = d_dup.get();
     d.tags = (int)tags;
     if (tags) {
         d.tgt4 = c->ix.tgt4; d.ent_start = c->ix.ent_start; d.ent_end = c->ix.ent_end; d.id2idx = c->ix.id2idx; d.max_id = c->ix.max_id; d.n_ix_ent = c->ix.n_ent;

@@ -63,4 +63,18 @@ struct CovStage {
                tile_at[1].bytes() + tot.bytes() + runs.bytes() + len.bytes() + at.bytes() + text.bytes() + host.bytes();
     }
 };
+// bk_mark_duplicates: all requests of a call and their answers, the grouping table, the totals
+struct alignas(16) DupSlot {
+    unsigned long long best;              // score << 32 | (0xFFFFFFFF - request index) of the group's keeper so far (cleared to 0)
+    uint32_t owner;                       // the request that claimed the slot: its key is the slot's (cleared to 0xFFFFFFFF)
+    uint32_t count;                       // templates of the group
+};
+struct DupStage {
+    uint64_t table_slots = 0;             // "dup_table_slots": 0 - derived per call - or a power of two >= the call's requests
+    DevBuf<bk_dup_req> reqs;
+    DevBuf<uint8_t> out;
+    DevBuf<DupSlot> table;
+    DevBuf<unsigned long long> tot;       // groups, largest group, flagged, the error word
+    size_t bytes() const { return reqs.bytes() + out.bytes() + table.bytes() + tot.bytes(); }
+};
 }  // namespace bk

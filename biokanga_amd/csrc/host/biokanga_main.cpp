@@ -9,7 +9,7 @@
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
 //                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-5 lociconstraints.csv] [-T host threads] [-F logfile] [--device n | --devices 0-7]
-//                  [--sam-tags NM,MD] [--coverage depth.bedgraph]
+//                  [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -34,6 +34,7 @@
 #include <memory>
 #include <ctime>
 #include <map>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -56,12 +57,14 @@
 #include "contaminants.h"
 #include "report.h"
 #include "coverage.h"
+#include "duplicates.h"
 
 namespace {
 using namespace bkcli;
 
+// long_no_val: keys of long-only options that take no value (every other key of more than one character takes one)
 bool parse_args(int argc, char **argv, int first, const std::map<std::string, std::string> &longnames,
-                const std::string &flags_with_val, const std::string &flags_no_val, Args &out, std::string &err)
+                const std::string &flags_with_val, const std::string &flags_no_val, Args &out, std::string &err, const std::set<std::string> &long_no_val = {})
 {
     for (int i = first; i < argc; i++) {
         std::string a = argv[i];
@@ -75,6 +78,10 @@ bool parse_args(int argc, char **argv, int first, const std::map<std::string, st
             std::string key = it->second;
             bool wants = flags_with_val.find(key) != std::string::npos || key.size() > 1;
             if (flags_no_val.find(key) != std::string::npos && key.size() == 1) wants = false;
+            if (long_no_val.count(key)) {
+                if (hasval) { err = "option --" + name + " takes no value"; return false; }
+                wants = false;
+            }
             if (wants && !hasval) {
                 if (i + 1 >= argc) { err = "option --" + name + " needs a value"; return false; }
                 val = argv[++i];
@@ -227,6 +234,7 @@ struct AlignOpts {
     int sam_tags = 0;                      // --sam-tags: mask of BK_SAMTAG_NM | BK_SAMTAG_MD written behind QUAL of accepted records (0: none, the reference's lines)
     uint64_t sam_tag_bytes() const { return ((sam_tags & BK_SAMTAG_NM) ? 8u : 0u) + ((sam_tags & BK_SAMTAG_MD) ? 16u : 0u); }      // .. about what they add to a line
     std::string coverage_path;             // --coverage: per-base depth of the accepted records into this bedGraph (empty: none; made on the first device)
+    bool mark_dups = false;                // --mark-duplicates: FLAG 0x400 on the records of duplicate templates (grouped on the first device)
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
 
@@ -391,6 +399,18 @@ int read_align_opts(Args &a, AlignOpts &o)
         o.coverage_path = a.str("coverage");
         if (o.coverage_path.empty()) { diag("Error: coverage file '--coverage' needs a file name"); return 1; }
         if (o.coverage_path == a.str("o")) { diag("Error: coverage file '--coverage %s' is the output file '-o' itself", o.coverage_path.c_str()); return 1; }
+    }
+    // --mark-duplicates (ours: the reference's -k removes single-end reads by start, strand and length)
+    if (a.has("mark-duplicates")) {
+        o.mark_dups = true;
+        if (o.fmt >= 0 && o.fmt <= 4) {
+            diag("Error: duplicate marking '--mark-duplicates' is only available with SAM / BAM output formats '-M5' and '-M6'");
+            return 1;
+        }
+        if (o.ml_mode == 5) {
+            diag("Error: duplicate marking '--mark-duplicates' is not available when reporting all multiloci alignments '-r5'");
+            return 1;
+        }
     }
     if (a.has("O") && o.fmt == 6) {                 // kanga.cpp:1015-1021
         diag("Error: Output induced substitution mode '-O<file>' not available in '-M6' output mode\n");
@@ -976,14 +996,14 @@ int parse_align_args(int argc, char **argv, int first, Args &a)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}, {"coverage", "coverage"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err)) {
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}, {"coverage", "coverage"}, {"mark-duplicates", "mark-duplicates"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err, {"mark-duplicates"})) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
     if (!a.has("i") || !a.has("I") || !a.has("o")) {
         fprintf(stderr, "usage: %s align -i <reads> -I <genome.sfx> -o <out.sam> [-s subs] [-e delta] [-Q strand] [-m mode] [-n maxNs] "
-                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD] [--coverage depth.bedgraph]\n", g_proc.c_str());
+                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates]\n", g_proc.c_str());
         return 1;
     }
     return 0;
@@ -1592,6 +1612,34 @@ int gather_site_prefs(AlignRun &r)
     return 0;
 }
 
+// --mark-duplicates: the templates of the final record set in load order go to the first device (bk_mark_duplicates), the records of
+// the duplicates among them get their byte in rec.dup, which every writer turns into FLAG 0x400; nothing else of a record changes
+int mark_duplicates(AlignRun &r)
+{
+    bk::RecordSet &rec = r.rec;
+    if (r.ctx == nullptr) { diag("Fatal: '--mark-duplicates' needs a device context"); return 1; }
+    diag("Processing to mark duplicate templates...");
+    HostClock clk;
+    std::vector<bk_dup_req> reqs;
+    std::vector<uint32_t> first;
+    duplicate_templates(rec, r.o.pe_mode != 0, reqs, first);
+    size_t n_pairs = 0;
+    for (const bk_dup_req &q : reqs) n_pairs += q.strand_mate != 0;
+    clk.lap("duplicate requests made");
+    std::vector<uint8_t> answers(reqs.size());
+    bk_dup_totals tot{};
+    const int rc = bk_mark_duplicates(r.ctx, reqs.data(), reqs.size(), answers.data(), &tot);
+    if (rc != BK_OK) { diag("Fatal: the duplicates could not be marked on the device: %s", bk_strerror(rc)); return 1; }
+    clk.lap("duplicates grouped (device)");
+    if (tot.flagged) { diag("Fatal: the duplicate marking pass turned %llu of %zu requests down", (unsigned long long)tot.flagged, reqs.size()); return 1; }
+    const long n_marked = duplicate_apply(rec, reqs, first, answers);
+    if (n_marked < 0) { diag("Fatal: the duplicate marking pass left a request unanswered"); return 1; }
+    clk.lap("duplicate records marked");
+    diag("Duplicates: %zu templates (%zu fragments, %zu pairs) in %llu groups, %llu templates (%ld records) marked as duplicates, largest group %llu", reqs.size(),
+         reqs.size() - n_pairs, n_pairs, (unsigned long long)tot.groups, (unsigned long long)tot.duplicates, n_marked, (unsigned long long)tot.max_group);
+    return 0;
+}
+
 // the writers, then the files that come behind them: the site preferences of -8, the SNPs of -p.  0, or the failed writer's code.
 int write_reports(AlignRun &r)
 {
@@ -1675,6 +1723,7 @@ int cmd_align(int argc, char **argv, int first)
     remove_orphan_junctions(r);
     if (!o.re_excl.empty() || !o.re_incl.empty()) filter_by_chroms(r);
     if (report_align_stats(r)) return 1;
+    if (o.mark_dups && mark_duplicates(r)) return 1;
 
     r.with_site_prefs = !o.site_prefs_path.empty() && r.nar[1] > 0;
     if (r.with_site_prefs && gather_site_prefs(r)) return 1;

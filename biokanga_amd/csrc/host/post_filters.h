@@ -32,6 +32,7 @@ struct RecordSet {
     std::vector<uint32_t> src;                     // -r5: record -> read it came from (records replace the reads)
     FlankTrims trims;                              // per record, empty until a step makes them
     std::vector<bk_loci_trims> rec_trims;          // -c with -r: per record (after -r5's expansion) the trims of the placement it took
+    std::vector<uint8_t> dup;                      // --mark-duplicates: per record, non-zero = a duplicate (FLAG 0x400); empty: not asked for
 
     size_t size() const { return hits.size(); }
     size_t RD(size_t i) const { return src.empty() ? i : (size_t)src[i]; }
@@ -41,6 +42,7 @@ struct RecordSet {
         if (!rec_trims.empty()) return rec_trims[i].chimeric != 0;
         return !seg2.empty() && (seg2[RD(i)].flags & 8);
     }
+    bool is_dup(size_t i) const { return !dup.empty() && dup[i] != 0; }
     uint32_t TL(size_t i) const { return trims.empty() ? 0u : trims.left[i]; }
     uint32_t TR(size_t i) const { return trims.empty() ? 0u : trims.right[i]; }
     uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci

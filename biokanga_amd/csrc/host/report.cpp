@@ -353,6 +353,7 @@ int report_bam(Report &R, const std::string &opath)
                 } else
                     flag |= 0x8;
             }
+            if (acc && recs.is_dup(i)) flag |= 0x400;          // --mark-duplicates
             const char *qn = rs.name(recs.RD(i));
             const uint32_t l_qn = (uint32_t)strlen(qn) + 1;
             const char *tag = acc ? nullptr : kNarTag[h.nar < 20 ? h.nar : 0];
@@ -563,6 +564,7 @@ int report_text(Report &R)
                 } else
                     flag |= 0x8;
             }
+            if (acc && recs.is_dup(i)) flag |= 0x400;          // --mark-duplicates
             *w++ = '\t';
             w = put_num(w, flag);
             if (acc) {
@@ -691,6 +693,7 @@ int report_text(Report &R)
             if (!recs.src.empty()) { job.src = recs.src.data(); job.n_src_reads = n_rd; }
             if (!recs.seg2.empty()) { job.seg2 = recs.seg2.data(); job_ok = job_ok && recs.seg2.size() == n_rd; }
             if (!recs.trims.empty()) { job.trim_left = recs.trims.left.data(); job.trim_right = recs.trims.right.data(); job_ok = job_ok && recs.trims.left.size() == nr && recs.trims.right.size() == nr; }
+            if (!recs.dup.empty()) { job.dup = recs.dup.data(); job_ok = job_ok && recs.dup.size() == nr; }
             job.report_unaligned = fmt == 6 ? 1 : 0; job.pe_mode = pe_mode;
             job.pk_words = R.pk_words; job.n_pk_words = R.n_pk_words; job.pk_lens16 = R.pk_lens16; job.pk_exc = R.pk_exc; job.n_pk_exc = R.n_pk_exc;
             job.prep = R.sam_prep;

@@ -82,7 +82,7 @@ typedef struct bk_hit {
     int8_t   nxt_low_mm;         /* tsReadHit.NxtLowMMCnt                                        */
     uint8_t  num_hits;           /* tsReadHit.NumHits                                            */
     uint8_t  mismatches;         /* Seg[0].Mismatches (Hamming score of the accepted hit)        */
-    uint8_t  flags;              /* reserved                                                     */
+    uint8_t  flags;              /* bit 7: FlgPEAligned (bk_pair_batch); bits 0-6: the engine's, no meaning outside it */
 } bk_hit;
 
 /* counters behind the "algorithmic bytes" figure of SURVEY.md §8(d); all are counts of what the
@@ -245,6 +245,8 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "coverage_slice_bases" (target bases bk_coverage_* takes per slice, one int32 each; 0 - the default - until the first call
  *   derives it from the free memory), "coverage_run_chunk" (runs per sink call), "coverage_req_chunk" (requests staged at a time),
  *   "coverage_buf_bytes" (what its staging holds now, device and page-locked; read only)
+ *   "dup_table_slots" (slots of bk_mark_duplicates' table; 0 - the default - derives them per call: the smallest power of two
+ *   >= 2 n, at least 1024; any other value is checked by the call), "dup_buf_bytes" (what its staging and table hold now; read only)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -633,8 +635,9 @@ int  bk_constraints_check(bk_constraints *set, const bk_constraint_req *reqs, ui
  * record i is read i, and n_reads counts both.  With `src` (-r5: a read owns a record per reported locus) n_reads counts the
  * RECORDS and n_src_reads the reads; record i belongs to read src[i].
  *   by read:   bases / offs / lens, names / name_ofs, pk_*, seg2 and the head start (`prep`, given the reads alone)
- *   by record: hits, the entries of order, trim_left / trim_right, src
+ *   by record: hits, the entries of order, trim_left / trim_right, src, dup
  * What a record may carry besides its bk_hit:
+ *   dup                    - the verdict of bk_mark_duplicates (below): FLAG |= 0x400 on an accepted record, nothing else moves;
  *   trim_left / trim_right - end trims in read orientation (-x, -A, -c: tsSegLoci.TrimLeft / TrimRight): POS moves to AdjStartLoci,
  *                            the M run shrinks to AdjHitLen and the trimmed ends are written as soft clips, swapped on the '-' strand;
  *   seg2 of its read       - a second segment (flags & 5: microInDel or splice junction) adds <gap>N, <n>I or <gap>D and <len2>M
@@ -672,6 +675,7 @@ typedef struct bk_sam_job {
     const bk_seg2  *seg2;         /* NULL, or one per READ, as bk_batch_seg2() returns them                                */
     const uint16_t *trim_left;    /* NULL (both), or one per RECORD, read orientation                                      */
     const uint16_t *trim_right;
+    const uint8_t  *dup;          /* NULL, or one per RECORD (--mark-duplicates): non-zero adds 0x400 to the FLAG of an accepted record */
 } bk_sam_job;
 /* Optional head start: everything of a job that is known once the reads are aligned - the read store, the names, the buffers the
  * text leaves the device through - can travel while the host still sorts.  bk_sam_prepare() returns at once (a thread of the library
@@ -772,6 +776,62 @@ typedef int (*bk_cov_run_sink)(void *user, const bk_cov_run *runs, uint64_t n_ru
  * Both calls share every kernel but the formatter's. */
 int  bk_coverage_runs(bk_ctx *ctx, const bk_cov_req *reqs, uint64_t n, bk_cov_run_sink sink, void *user, bk_cov_totals *totals);
 int  bk_coverage_text(bk_ctx *ctx, const bk_cov_req *reqs, uint64_t n, bk_sam_sink sink, void *user, bk_cov_totals *totals);
+
+/* ---- duplicate marking: FLAG 0x400 (--mark-duplicates) ---------------------------------------------------------------
+ * Ours, as --sam-tags and --coverage are: the reference's -k removes reads, keys on start + strand + length and runs for single
+ * ends only.  THE RULE.
+ * Templates.  The participants are the accepted records (nar == BK_NAR_ACCEPTED, strand '+' or '-') of the FINAL record set, the
+ * one the writers see.  A PAIR is one template of two records: under -U, both mates accepted and both carrying bk_hit.flags & 0x80
+ * (on the lines as written: FLAG & 1 set, FLAG & 4 and FLAG & 8 clear).  Every other accepted record is a FRAGMENT: single-end
+ * runs, orphan ends, ends "treated as SE" under -U3 / -U4.
+ * Unclipped 5' position of a record, from the numbers put_cigar writes - the walk of --sam-tags and --coverage: the line is
+ * [cL S] m M [cR S] [gap N|I|D m2 M] from POS; p = POS - 1 is the 0-based position of the first M base;
+ * span = m + (N or D ? gap : 0) + (second segment ? m2 : 0); strand '+': pos5 = p - cL; strand '-': pos5 = p + span - 1 + cR.
+ * pos5 is signed: it may be negative or lie beyond its sequence.
+ * Key.  Fragment: (chrom, pos5, strand).  Pair: (chrom, pos5_a, strand_a, pos5_b, strand_b) with the two ends ordered so that
+ * (pos5_a, strand_a) <= (pos5_b, strand_b), '+' < '-'; which end is PE1 is no part of the key (F1R2 and F2R1 at the same ends are
+ * one molecule).  Pairs and fragments never share a group: Picard's "a fragment at a pair's end is a duplicate" is not part of
+ * this version.
+ * Keeper.  Within a group of equal keys exactly one template is kept: the one with the highest score - the M bases of its line(s)
+ * as written, m + m2, summed over both mates of a pair - ties going to the template whose (first) read was loaded first.  Every
+ * other template of the group is a duplicate.  Base qualities are not looked at; the score is the caller's number.
+ * Effect.  Every record of a duplicate template gets 0x400 added to FLAG, in SAM and in BAM, and nothing else changes: duplicates
+ * stay accepted, keep their place in the sort order, their --sam-tags, and their count in --coverage, the -O statistics, the SNP
+ * calls and -8 (depth and SNPs still include duplicates).  Lines of unaccepted reads under -M6 never carry the bit.
+ * The verdict reaches the writers as one byte per record (bk_sam_job.dup), not as a bit of bk_hit.flags: the low seven bits of
+ * that field are not free - the engine leaves (AlignReads phase << 1) | 1 there, and the phase reaches 32 and more. */
+typedef struct bk_dup_req {      /* one per TEMPLATE */
+    uint32_t chrom_id;           /* EntryID                                                                   */
+    int32_t  pos5;               /* unclipped 5' position of the (first) end                                  */
+    int32_t  pos5_mate;          /* pairs: the other end's; ignored for a fragment                            */
+    uint8_t  strand;             /* '+' | '-'                                                                 */
+    uint8_t  strand_mate;        /* 0: fragment; '+' | '-': pair                                              */
+    uint16_t score;
+} bk_dup_req;                    /* 16 bytes */
+typedef struct bk_dup_totals {
+    uint64_t templates;          /* n                                                                         */
+    uint64_t groups;             /* distinct keys among the requests that are not flagged                     */
+    uint64_t duplicates;         /* templates - flagged - groups                                              */
+    uint64_t max_group;          /* templates of the largest group                                            */
+    uint64_t flagged;
+} bk_dup_totals;
+/* Host arrays, blocking, on the context's stream.  out[i]: 0 request i is kept, 1 it is a duplicate, 2 it is flagged.  The library
+ * puts a pair's ends into canonical order itself (the caller hands them PE1 first); among equal scores the EARLIER REQUEST wins,
+ * so a caller that submits its templates in load order gets the rule's tie-break.  The answer does not depend on how the device
+ * schedules the requests.
+ * A request is FLAGGED when its sequence does not exist, its strand is not '+' / '-' or its strand_mate is none of 0, '+', '-':
+ * it takes part in no group, is counted in totals->flagged and harms no other request.
+ * On the device: an open-addressing table of "dup_table_slots" slots of 16 bytes (owner, best, count), linear probing.  A lane per
+ * request claims the first empty slot of its probe sequence with a compare-and-swap of its own index, or joins the slot whose
+ * owner's FULL key equals its own (never a fingerprint), and there raises best = score << 32 | (0xFFFFFFFF - index) by an atomic
+ * maximum; a second pass finds the slot again and keeps the request best names.  The grouping is global: all requests and the
+ * table are resident at once - 100 M templates with the derived table take 1.6 GB of requests and 4.3 GB of table - and
+ * BK_ERR_MEM says they do not fit.  Staging and table belong to the context and are made by the first call (a run without the
+ * option allocates nothing; "dup_buf_bytes", read only, says what is held).
+ * BK_ERR_PARAMS, before anything is launched: a NULL array with n > 0, n >= 2^32 - 1, a "dup_table_slots" that is set and is no
+ * power of two or is smaller than n.  n == 0 does nothing (totals may be NULL).  The probe loops are bounded by the table's size:
+ * a lane that finds neither its group nor an empty slot - which cannot happen - ends the call with BK_ERR_INTERNAL. */
+int  bk_mark_duplicates(bk_ctx *ctx, const bk_dup_req *reqs, uint64_t n, uint8_t *out, bk_dup_totals *totals);
 
 /* ---- test hook: the search stage on its own ------------------------------------------------------------------------
  * LocateFirstExact / LocateLastExact (SfxArrayV2.cpp:7765-7876, :7914-8027) are two kernels here (k-mer table + key arrays, bk_search.hip); to
