@@ -23,6 +23,7 @@ EXPORTED_SYMBOLS = [
     "bk_samtags", "bk_sam_format_tags",
     "bk_coverage_runs", "bk_coverage_text",
     "bk_mark_duplicates",
+    "bk_junctions",
 ]
 
 
@@ -95,6 +96,11 @@ DUP_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("pos5", "<i4"), ("pos5_mate", "<
 assert DUP_REQ_DTYPE.itemsize == 16
 DUP_TOTALS = ("templates", "groups", "duplicates", "max_group", "flagged")
 DUP_KEPT, DUP_DUPLICATE, DUP_FLAGGED = 0, 1, 2
+# bk_junction_req: one spliced record of bk_junctions - the intron [start, end) of its line and min(m, m2); bk_junction: one line of the table
+JUNCTION_REQ_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("overhang", "<u2"), ("reserved", "<u2")])
+JUNCTION_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reads", "<u4"), ("max_overhang", "<u2"), ("motif", "u1"), ("strand", "u1")])
+assert JUNCTION_REQ_DTYPE.itemsize == 16 and JUNCTION_DTYPE.itemsize == 20
+JUNCTION_TOTALS = ("requests", "junctions", "flagged", "max_reads", "by_motif")
 MAX_CONSTRAINED_SEQS, MAX_CONSTRAINTS, CONSTRAINT_R = 64, 6400, 0x10
 CONSTRAINT_UNTOUCHED, CONSTRAINT_TOUCHED, CONSTRAINT_VIOLATED, CONSTRAINT_BAD = 0, 1, 2, 0x80
 CONSTRAINT_DTYPE = np.dtype([("chrom_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("mask", "u1"), ("_r", "u1", (3,))])
@@ -146,7 +152,7 @@ class _SamJob(ctypes.Structure):
                 ("pk_words", ctypes.c_void_p), ("n_pk_words", ctypes.c_uint64), ("pk_lens16", ctypes.c_void_p),
                 ("pk_exc", ctypes.c_void_p), ("n_pk_exc", ctypes.c_uint64),
                 ("src", ctypes.c_void_p), ("n_src_reads", ctypes.c_uint64), ("seg2", ctypes.c_void_p),
-                ("trim_left", ctypes.c_void_p), ("trim_right", ctypes.c_void_p), ("dup", ctypes.c_void_p)]
+                ("trim_left", ctypes.c_void_p), ("trim_right", ctypes.c_void_p), ("dup", ctypes.c_void_p), ("xs", ctypes.c_void_p)]
 
 
 _SAM_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
@@ -324,6 +330,8 @@ def load_library():
     lib.bk_coverage_text.restype = i32
     lib.bk_mark_duplicates.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64 * 5)]
     lib.bk_mark_duplicates.restype = i32
+    lib.bk_junctions.argtypes = [vp, vp, u64, vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64 * 11)]
+    lib.bk_junctions.restype = i32
     lib.bk_contam_create.argtypes = [ctypes.POINTER(vp), i32, vp, u32]
     lib.bk_contam_create.restype = i32
     lib.bk_contam_destroy.argtypes = [vp]
@@ -834,13 +842,30 @@ class Aligner:
             raise BkError(rc, "bk_mark_duplicates")
         return out, dict(zip(DUP_TOTALS, (int(v) for v in tot)))
 
+    def junctions(self, reqs):
+        """bk_junctions: JUNCTION_REQ_DTYPE requests -> (the table as JUNCTION_DTYPE, sorted by (sequence in index order, start, end),
+        one byte per request: ord('+'), ord('-') or 0, totals as a dict of JUNCTION_TOTALS - by_motif a list of seven)"""
+        reqs = np.ascontiguousarray(reqs, dtype=JUNCTION_REQ_DTYPE)
+        n = len(reqs)
+        strands = np.zeros(n, dtype=np.uint8)
+        out = np.zeros(n, dtype=JUNCTION_DTYPE)
+        nj = ctypes.c_uint64(0)
+        tot = (ctypes.c_uint64 * 11)()
+        rc = self.lib.bk_junctions(self.h, reqs.ctypes.data if n else None, n, strands.ctypes.data if n else None, out.ctypes.data if n else None, n,
+                                   ctypes.byref(nj), ctypes.byref(tot))
+        if rc:
+            raise BkError(rc, "bk_junctions")
+        t = [int(v) for v in tot]
+        return out[:nj.value].copy(), strands, dict(zip(JUNCTION_TOTALS, t[:4] + [t[4:]]))
+
     def sam_format(self, bases, offs, lens, names, hits, order, report_unaligned=True, pe_mode=0, *, src=None, seg2=None,
-                   trim_left=None, trim_right=None, tags=None, packed=False, dup=None):
+                   trim_left=None, trim_right=None, tags=None, packed=False, dup=None, xs=None):
         """bk_sam_format: the SAM body of `hits` in the order given, as bytes.  `names`: a list of bytes, one per read.  Without `src`
         hits go by read; with it (record -> read) hits, order and the trims go by record, the read store and seg2 by read.
         tags: None, or the mask of bk_sam_format_tags (SAMTAG_NM | SAMTAG_MD; 0 is allowed).  packed: the reads travel in the packed
         form of pack_reads (they must lie back to back in `bases`, in read order).  dup: None, or a byte per record - non-zero adds 0x400
-        to the FLAG of an accepted record."""
+        to the FLAG of an accepted record.  xs: None, or a byte per record - ord('+') / ord('-') adds XS:A:<c> at the end of an accepted
+        record's line."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
@@ -856,7 +881,7 @@ class Aligner:
         keep = []
         for field, arr, dt, n in (("src", src, np.uint32, len(hits)), ("seg2", seg2, SEG2_DTYPE, len(lens)),
                                   ("trim_left", trim_left, np.uint16, len(hits)), ("trim_right", trim_right, np.uint16, len(hits)),
-                                  ("dup", dup, np.uint8, len(hits))):
+                                  ("dup", dup, np.uint8, len(hits)), ("xs", xs, np.uint8, len(hits))):
             if arr is None:
                 continue
             arr = np.ascontiguousarray(arr, dtype=dt)

@@ -4,7 +4,7 @@
 // buffer's own size (bk_devbuf.h).  The index image and the grow worker's tables are bk_ctx::image (ImageBufs, filled by bk_image.cpp), the
 // small fixed buffers (counters, phase control, the SNP planes) bk_ctx::fixed (FixedBufs), the engine's scratch and what the batch entry
 // points grow on demand bk_ctx::buf (BatchBufs); each request pass over finished alignments keeps its own staging (bk_stage.h: bk_ctx::snp,
-// site, primer, samtag, cov, dup).  bk_ctx_destroy frees nothing by name: release_image_buffers(), release_batch_buffers() and
+// site, primer, samtag, cov, dup, jct).  bk_ctx_destroy frees nothing by name: release_image_buffers(), release_batch_buffers() and
 // release_pinned_buffers() give the lot back.  POD structs that travel to kernels (DevIndex - set from the image by publish_index alone -
 // HeavyScratch, DevBatch) carry raw pointers into them.
 #pragma once
@@ -146,10 +146,11 @@ struct bk_ctx {
     bk::SamtagStage samtag;
     bk::CovStage cov;
     bk::DupStage dup;
+    bk::JunctionStage jct;
     void release_batch_buffers()
     {
         buf = bk::BatchBufs{}; snp = bk::SnpStage{}; site = bk::SiteStage{}; primer = bk::PrimerStage{}; samtag = bk::SamtagStage{}; cov = bk::CovStage{};
-        dup = bk::DupStage{};
+        dup = bk::DupStage{}; jct = bk::JunctionStage{};
     }
     // what the batch scratch was sized for (scratch_bytes_per_read, maybe_build_swin)
     uint32_t cap_reads = 0, cap_wpr = 0, cap_iv_cores = 0;

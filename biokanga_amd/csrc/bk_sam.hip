@@ -46,6 +46,7 @@ struct SamDev {
     const uint16_t *trim_l, *trim_r;
     int ext;                         // any of the four is there: the kernels ask this first, so plain jobs never look at a record for them
     const uint8_t *dup;              // null, or by record: non-zero = a duplicate (bk_mark_duplicates): an accepted record's FLAG gets 0x400
+    const uint8_t *xs;               // null, or by record: '+' / '-' = the transcript strand (bk_junctions): an accepted record's line ends with \tXS:A:<c>
     // bk_sam_format_tags (tags = 0: none of this is looked at): the mask, the indexed target with its entry table, and per record of the
     // slice the NM the measuring pass found (bk::kTagNone: the record gets no tags), which the writing pass places the MD text by
     int tags;
@@ -186,6 +187,15 @@ __device__ __forceinline__ SamRec sam_rec(const SamDev &d, uint64_t k)
     return r;
 }
 
+// XS:A:<c> closes the line of an accepted record whose byte is '+' or '-': seven bytes, counted by the measuring pass and written by the
+// writing pass in front of the line's '\n'
+__device__ __forceinline__ char sam_xs(const SamDev &d, const SamRec &r)
+{
+    if (!d.xs || !r.acc) return 0;
+    const uint8_t c = d.xs[r.i];
+    return c == '+' || c == '-' ? (char)c : (char)0;
+}
+
 // the walk of an accepted record's line for its NM / MD (bk_samtags.h): the numbers put_cigar writes, against the record's sequence
 __device__ __forceinline__ void sam_tag_walk(const SamDev &d, const SamRec &r, bk::TagWalk &w)
 {
@@ -265,6 +275,7 @@ __global__ void __launch_bounds__(256) k_sam_measure(SamDev d, uint64_t k0, uint
                 // \t RNAME \t POS \t255\t CIGAR \t [*=] \t PNEXT \t TLEN \t SEQ \t QUAL \n
                 b += 1 + cl + 1 + n_digits((unsigned long)r.pos + 1) + 5 + (d.ext ? cigar_chars(r) : n_digits(r.mlen) + 1) + 1 + 1 + 1 +
                      n_digits((unsigned long)(r.pnext < 0 ? 0 : r.pnext + 1)) + 1 + n_chars((long)r.tlen) + 1 + r.len + 1 + qual + 1;
+                if (sam_xs(d, r)) b += 7;
             } else
                 // \t*\t0\t255\t <len>M\t*\t0\t0\t SEQ \t QUAL \t\tYU:Z:xx \n
                 b += 9 + n_digits(r.len) + 8 + r.len + 1 + qual + 7 + 2 + 1;
@@ -364,8 +375,13 @@ __global__ void __launch_bounds__(256) k_sam_write(SamDev d, uint64_t k0, uint32
                 if (d.tags & BK_SAMTAG_NM) { w = put_str(w, "\tNM:i:"); w = put_num(w, (long)nm); }
                 if (d.tags & BK_SAMTAG_MD) { w = put_str(w, "\tMD:Z:"); w_md = w; }       // (the text itself: the wave, below)
                 out[at[j + 1] - 1] = '\n';
-            } else
+            } else if (!sam_xs(d, r))
                 *w++ = '\n';
+            if (const char xs = sam_xs(d, r)) {                                           // the line's last field, wherever the tags end
+                char *x = put_str(out + at[j + 1] - 8, "\tXS:A:");
+                *x++ = xs;
+                *x = '\n';
+            }
         } else {
             w = put_str(w, "\t*\t0\t255\t");
             w = put_num(w, r.len);
@@ -617,7 +633,11 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     DevBuf<uint32_t> d_src;
     DevBuf<bk_seg2> d_seg2;
     DevBuf<uint16_t> d_tl, d_tr;
-    DevBuf<uint8_t> d_dup;
+    DevBuf<uint8_t> d_dup, d_xs;
+    if (job->xs) {
+        SAM_TRY(d_xs.ensure(n_rec));
+        if (bk::upload_host(d_xs.get(), job->xs, n_rec, c->device)) return BK_ERR_INTERNAL;
+    }
     if (job->dup) {
         SAM_TRY(d_dup.ensure(n_rec));
         if (bk::upload_host(d_dup.get(), job->dup, n_rec, c->device)) return BK_ERR_INTERNAL;
@@ -651,6 +671,7 @@ extern "C" int bk_sam_format_tags(bk_ctx *c, const bk_sam_job *job, uint32_t tag
     d.trim_l = d_tl.get(); d.trim_r = d_tr.get();
     d.ext = (d.src || d.seg2 || d.trim_l) ? 1 : 0;
     d.dup = d_dup.get();
+    d.xs = d_xs.get();
     d.tags = (int)tags;
     if (tags) {
         d.tgt4 = c->ix.tgt4; d.ent_start = c->ix.ent_start; d.ent_end = c->ix.ent_end; d.id2idx = c->ix.id2idx; d.max_id = c->ix.max_id; d.n_ix_ent = c->ix.n_ent;

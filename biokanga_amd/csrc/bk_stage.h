@@ -77,4 +77,26 @@ struct DupStage {
     DevBuf<unsigned long long> tot;       // groups, largest group, flagged, the error word
     size_t bytes() const { return reqs.bytes() + out.bytes() + table.bytes() + tot.bytes(); }
 };
+// bk_junctions: all requests of a call and their strands, the grouping table, the emitted junctions with their sort keys, the totals
+struct alignas(16) JctSlot {
+    uint32_t owner;                       // the request that claimed the slot: its key is the slot's (cleared to 0xFFFFFFFF)
+    uint32_t count;                       // requests of the junction
+    uint32_t overhang;                    // the largest overhang among them
+    uint32_t motif;                       // motif | strand << 8, written by the owner once the grouping is done
+};
+struct JunctionStage {
+    uint64_t table_slots = 0;             // "junction_table_slots": 0 - derived per call - or a power of two >= the call's requests
+    DevBuf<bk_junction_req> reqs;
+    DevBuf<uint8_t> strand, tmp;          // (tmp: the sorts' temporary)
+    DevBuf<JctSlot> table;
+    DevBuf<unsigned long long> tot;       // junctions, largest count, flagged, the error word, the emit counter, junctions by motif
+    DevBuf<bk_junction> jct, sorted;      // as emitted; in their final order
+    DevBuf<uint32_t> key_end[2], place[3];        // first sort: `end` in and out; the places in, between the sorts, out
+    DevBuf<unsigned long long> key_hi[3]; // entry index << 32 | start: as emitted; second sort in and out
+    size_t bytes() const
+    {
+        return reqs.bytes() + strand.bytes() + tmp.bytes() + table.bytes() + tot.bytes() + jct.bytes() + sorted.bytes() + key_end[0].bytes() + key_end[1].bytes() +
+               place[0].bytes() + place[1].bytes() + place[2].bytes() + key_hi[0].bytes() + key_hi[1].bytes() + key_hi[2].bytes();
+    }
+};
 }  // namespace bk

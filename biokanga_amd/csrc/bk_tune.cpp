@@ -82,7 +82,8 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
         {"coverage_slice_bases", nullptr, &c->cov.slice_bases, 0, INT64_MAX},     // target bases per slice; 0 (the default): the next call derives it from the free memory
         {"coverage_run_chunk", nullptr, &c->cov.run_chunk, 1, 1LL << 26},         // runs per sink call
         {"dup_table_slots", nullptr, &c->dup.table_slots, 0, 1LL << 40},          // slots of bk_mark_duplicates' table; 0 (the default): derived per call.  The call checks a set value against its requests
-        {"wave_waves", &c->wave_waves, nullptr, 64, 65536},                       // resident waves the wave kernel is launched with
+        {"junction_table_slots", nullptr, &c->jct.table_slots, 0, 1LL << 40},     // .. of bk_junctions' table, the same way
+        {"wave_waves", &c->wave_waves, nullptr, 64, 65536},                     // resident waves the wave kernel is launched with
     };
     for (const auto &k : chunk_knobs) {
         if (n != k.name) continue;
@@ -96,6 +97,7 @@ int64_t bk_ctx_tune(bk_ctx *c, const char *name, int64_t value)
     if (n == "samtag_buf_bytes") return (int64_t)c->samtag.bytes();
     if (n == "coverage_buf_bytes") return (int64_t)c->cov.bytes();
     if (n == "dup_buf_bytes") return (int64_t)c->dup.bytes();
+    if (n == "junction_buf_bytes") return (int64_t)c->jct.bytes();
     if (n == "primer_buf_bytes") return (int64_t)c->primer.bytes();
     if (n == "kmer_bits" || n == "use_ktab") {
         int64_t old = n == "use_ktab" ? c->use_ktab : c->ix.k;

@@ -9,7 +9,7 @@
 //   biokanga align -i reads.fa[.gz] -I genome.sfx -o out.sam [-s subs] [-e 1|2] [-Q 0|1|2] [-m 0..3]
 //                  [-n maxNs] [-l minlen] [-L maxlen] [-y trim5] [-Y trim3] [-H contaminants.fa] [-M 0|5|6] [-O stats.csv]
 //                  [-U 1..4 -u mates.fa -d minins -D maxins [-E]] [-8 siteprefs.csv [-9 ofs]] [-6 0..5] [-5 lociconstraints.csv] [-T host threads] [-F logfile] [--device n | --devices 0-7]
-//                  [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates]
+//                  [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates] [--junctions sj.tab] [--splice-strand]
 //   (reads: FASTA / FASTQ, plain, gzip'd or bgzip'd, also through a FIFO; -o: a file, a name ending in .gz or .bam, or a FIFO)
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -58,6 +58,7 @@
 #include "report.h"
 #include "coverage.h"
 #include "duplicates.h"
+#include "junctions.h"
 
 namespace {
 using namespace bkcli;
@@ -235,6 +236,8 @@ struct AlignOpts {
     uint64_t sam_tag_bytes() const { return ((sam_tags & BK_SAMTAG_NM) ? 8u : 0u) + ((sam_tags & BK_SAMTAG_MD) ? 16u : 0u); }      // .. about what they add to a line
     std::string coverage_path;             // --coverage: per-base depth of the accepted records into this bedGraph (empty: none; made on the first device)
     bool mark_dups = false;                // --mark-duplicates: FLAG 0x400 on the records of duplicate templates (grouped on the first device)
+    std::string junctions_path;            // --junctions: the junction table of the spliced records into this file (empty: none; made on the first device)
+    bool splice_strand = false;            // --splice-strand: XS:A:+ / XS:A:- on spliced records whose junction has a stranded motif
     std::vector<int> devices;              // --device n | --devices a,b,c | a-b: one context (+ upload / align / download pipeline) per entry
 };
 
@@ -411,6 +414,27 @@ int read_align_opts(Args &a, AlignOpts &o)
             diag("Error: duplicate marking '--mark-duplicates' is not available when reporting all multiloci alignments '-r5'");
             return 1;
         }
+    }
+    // --junctions <file>, --splice-strand (ours: the reference writes a BED line per spliced read, with the read's strand)
+    if (a.has("junctions")) {
+        o.junctions_path = a.str("junctions");
+        std::string jp = a.str("o");
+        if (is_gz_name(jp)) jp.resize(jp.size() - 3);
+        if (o.junctions_path.empty()) { diag("Error: junction table '--junctions' needs a file name"); return 1; }
+        if (o.junctions_path == a.str("o")) { diag("Error: junction table '--junctions %s' is the output file '-o' itself", o.junctions_path.c_str()); return 1; }
+        if (o.junctions_path == a.str("o") + ".jct" || o.junctions_path == jp + ".jct") {
+            diag("Error: junction table '--junctions %s' is the junction BED file of '-o' itself", o.junctions_path.c_str());
+            return 1;
+        }
+        if (!o.splice_len) { diag("Error: junction table '--junctions' needs RNAseq splice junction processing '-A<len>'"); return 1; }
+    }
+    if (a.has("splice-strand")) {
+        o.splice_strand = true;
+        if (o.fmt >= 0 && o.fmt <= 4) {
+            diag("Error: transcript strand tags '--splice-strand' are only available with SAM / BAM output formats '-M5' and '-M6'");
+            return 1;
+        }
+        if (!o.splice_len) { diag("Error: transcript strand tags '--splice-strand' need RNAseq splice junction processing '-A<len>'"); return 1; }
     }
     if (a.has("O") && o.fmt == 6) {                 // kanga.cpp:1015-1021
         diag("Error: Output induced substitution mode '-O<file>' not available in '-M6' output mode\n");
@@ -996,14 +1020,15 @@ int parse_align_args(int argc, char **argv, int first, Args &a)
         {"pairstrand", "E"}, {"nonealign", "j"}, {"multialign", "J"}, {"title", "t"}, {"maxmulti", "R"}, {"clampmaxmulti", "X"},
         {"bestmatches", "N"}, {"microindellen", "a"}, {"minflankexacts", "x"}, {"splicejunctlen", "A"}, {"minchimeric", "c"}, {"pcrwin", "k"}, {"samplenthrawread", "#"}, {"chromexclude", "Z"}, {"chromeinclude", "z"},
         {"contaminants", "H"}, {"minsnpreads", "p"}, {"qvalue", "P"}, {"snpnonrefpcnt", "1"}, {"snpfile", "S"}, {"markerlen", "K"}, {"markerpolythres", "G"}, {"snpcentroid", "7"},
-        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}, {"coverage", "coverage"}, {"mark-duplicates", "mark-duplicates"}};
-    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err, {"mark-duplicates"})) {
+        {"siteprefs", "8"}, {"siteprefsofs", "9"}, {"pcrprimersubs", "6"}, {"lociconstraints", "5"}, {"sam-tags", "sam-tags"}, {"coverage", "coverage"}, {"mark-duplicates", "mark-duplicates"},
+        {"junctions", "junctions"}, {"splice-strand", "splice-strand"}};
+    if (!parse_args(argc, argv, first, ln, "mQesnyYlLMiIoOTFfUrg4udDjJtRaxAck#ZzpP1SKG7H8965", "EXN", a, err, {"mark-duplicates", "splice-strand"})) {
         fprintf(stderr, "%s align: %s\n", g_proc.c_str(), err.c_str());
         return 1;
     }
     if (!a.has("i") || !a.has("I") || !a.has("o")) {
         fprintf(stderr, "usage: %s align -i <reads> -I <genome.sfx> -o <out.sam> [-s subs] [-e delta] [-Q strand] [-m mode] [-n maxNs] "
-                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates]\n", g_proc.c_str());
+                        "[-l minlen] [-L maxlen] [-M 0|5|6] [-O stats] [--device n | --devices a-b] [--window-array on|off] [--index-image lean|full] [--sam-tags NM,MD] [--coverage depth.bedgraph] [--mark-duplicates] [--junctions sj.tab] [--splice-strand]\n", g_proc.c_str());
         return 1;
     }
     return 0;
@@ -1640,6 +1665,51 @@ int mark_duplicates(AlignRun &r)
     return 0;
 }
 
+// --junctions / --splice-strand: one request per accepted record of the final record set whose line has an N goes to the first device
+// (bk_junctions); the table is written here, the strands go into rec.xs, which every SAM / BAM writer turns into XS:A:<c>; nothing else of a
+// record changes
+int splice_junctions(AlignRun &r)
+{
+    bk::RecordSet &rec = r.rec;
+    const AlignOpts &o = r.o;
+    if (r.ctx == nullptr) { diag("Fatal: '--junctions' / '--splice-strand' need a device context"); return 1; }
+    diag("Processing splice junctions of the accepted alignments...");
+    HostClock clk;
+    std::vector<bk_junction_req> reqs;
+    std::vector<uint32_t> rec_of;
+    junction_requests(rec, reqs, rec_of);
+    clk.lap("junction requests made");
+    const bool table = !o.junctions_path.empty();
+    std::vector<uint8_t> strands(reqs.size());
+    std::vector<bk_junction> jcts(table ? reqs.size() : 0);
+    uint64_t nj = 0;
+    bk_junction_totals tot{};
+    const int rc = bk_junctions(r.ctx, reqs.data(), reqs.size(), o.splice_strand ? strands.data() : nullptr, table ? jcts.data() : nullptr, jcts.size(), &nj, &tot);
+    if (rc != BK_OK) { diag("Fatal: the splice junctions could not be made on the device: %s", bk_strerror(rc)); return 1; }
+    clk.lap("junctions grouped (device)");
+    if (tot.flagged) diag("Warning: the junction pass turned %llu of %zu requests down", (unsigned long long)tot.flagged, reqs.size());
+    if (o.splice_strand) junction_apply_strands(rec, rec_of, strands);
+    if (table) {
+        std::string text;
+        for (uint64_t k = 0; k < nj; k++) {
+            const bk_junction &j = jcts[k];
+            if (j.chrom_id < 1 || j.chrom_id > r.n_ent) { diag("Fatal: the junction pass returned a sequence that is none of the index"); return 1; }
+            junction_line(j, r.ents[j.chrom_id - 1].name, text);
+        }
+        OutBuf out;
+        out.open(o.junctions_path.c_str());
+        if (out.fd < 0) { diag("Fatal: unable to create '%s'", o.junctions_path.c_str()); return 1; }
+        out.put(text);
+        out.close();
+        if (out.failed) { diag("Fatal error: unable to write the junction table to '%s'", o.junctions_path.c_str()); return 1; }
+        clk.lap("junction table written");
+    }
+    diag("Junctions: %zu spliced records, %llu junctions (%llu GT/AG, %llu other canonical, %llu non-canonical), most reads at one junction %llu", reqs.size(),
+         (unsigned long long)tot.junctions, (unsigned long long)(tot.by_motif[1] + tot.by_motif[2]),
+         (unsigned long long)(tot.by_motif[3] + tot.by_motif[4] + tot.by_motif[5] + tot.by_motif[6]), (unsigned long long)tot.by_motif[0], (unsigned long long)tot.max_reads);
+    return 0;
+}
+
 // the writers, then the files that come behind them: the site preferences of -8, the SNPs of -p.  0, or the failed writer's code.
 int write_reports(AlignRun &r)
 {
@@ -1724,6 +1794,7 @@ int cmd_align(int argc, char **argv, int first)
     if (!o.re_excl.empty() || !o.re_incl.empty()) filter_by_chroms(r);
     if (report_align_stats(r)) return 1;
     if (o.mark_dups && mark_duplicates(r)) return 1;
+    if ((!o.junctions_path.empty() || o.splice_strand) && splice_junctions(r)) return 1;
 
     r.with_site_prefs = !o.site_prefs_path.empty() && r.nar[1] > 0;
     if (r.with_site_prefs && gather_site_prefs(r)) return 1;

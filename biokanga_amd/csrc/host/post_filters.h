@@ -33,6 +33,7 @@ struct RecordSet {
     FlankTrims trims;                              // per record, empty until a step makes them
     std::vector<bk_loci_trims> rec_trims;          // -c with -r: per record (after -r5's expansion) the trims of the placement it took
     std::vector<uint8_t> dup;                      // --mark-duplicates: per record, non-zero = a duplicate (FLAG 0x400); empty: not asked for
+    std::vector<uint8_t> xs;                       // --splice-strand: per record, '+' / '-' = the transcript strand (XS:A), else 0; empty: not asked for
 
     size_t size() const { return hits.size(); }
     size_t RD(size_t i) const { return src.empty() ? i : (size_t)src[i]; }
@@ -43,6 +44,7 @@ struct RecordSet {
         return !seg2.empty() && (seg2[RD(i)].flags & 8);
     }
     bool is_dup(size_t i) const { return !dup.empty() && dup[i] != 0; }
+    char xs_of(size_t i) const { return !xs.empty() && (xs[i] == '+' || xs[i] == '-') ? (char)xs[i] : (char)0; }
     uint32_t TL(size_t i) const { return trims.empty() ? 0u : trims.left[i]; }
     uint32_t TR(size_t i) const { return trims.empty() ? 0u : trims.right[i]; }
     uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci

@@ -362,6 +362,8 @@ int report_bam(Report &R, const std::string &opath)
             const uint32_t tq = R.sam_tags ? tags.of(i) : HostSamTags::kNone;
             if (tq != HostSamTags::kNone)
                 aux += ((R.sam_tags & BK_SAMTAG_NM) ? (tags.nm[tq] <= 255 ? 4u : 5u) : 0u) + ((R.sam_tags & BK_SAMTAG_MD) ? 3u + (uint32_t)tags.md_len(tq) + 1u : 0u);
+            const char xs = acc ? recs.xs_of(i) : (char)0;          // --splice-strand: XS as A, behind NM / MD
+            if (xs) aux += 4u;
             const bool two = acc && recs.has_seg2(i);
             // soft clips in target order: read orientation for '+', swapped for '-' (Aligner.cpp:5961-5984)
             const uint32_t clip5 = acc ? (h.strand == '+' ? recs.TL(i) : recs.TR(i)) : 0u, clip3 = acc ? (h.strand == '+' ? recs.TR(i) : recs.TL(i)) : 0u;
@@ -427,6 +429,7 @@ int report_bam(Report &R, const std::string &opath)
                     *q++ = 0;
                 }
             }
+            if (xs) { *q++ = 'X'; *q++ = 'S'; *q++ = 'A'; *q++ = (uint8_t)xs; }
             if (acc) S.al.push_back({(uint64_t)at, (uint64_t)(at + 4 + block), ref, (int32_t)pos0, (int32_t)(pos0 + hit_len - 1)});
             S.n++;
         }
@@ -602,6 +605,7 @@ int report_text(Report &R)
                     if (R.sam_tags & BK_SAMTAG_NM) { w = put_str(w, "\tNM:i:"); w = put_num(w, (long)tags.nm[tq]); }
                     if (R.sam_tags & BK_SAMTAG_MD) { w = put_str(w, "\tMD:Z:"); const size_t ml = tags.md_len(tq); memcpy(w, tags.text.data() + tags.ofs[tq], ml); w += ml; }
                 }
+                if (const char xs = recs.xs_of(i)) { w = put_str(w, "\tXS:A:"); *w++ = xs; }          // --splice-strand
                 *w++ = '\n';
             } else {
                 w = put_str(w, "\t*\t0\t255\t");
@@ -694,6 +698,7 @@ int report_text(Report &R)
             if (!recs.seg2.empty()) { job.seg2 = recs.seg2.data(); job_ok = job_ok && recs.seg2.size() == n_rd; }
             if (!recs.trims.empty()) { job.trim_left = recs.trims.left.data(); job.trim_right = recs.trims.right.data(); job_ok = job_ok && recs.trims.left.size() == nr && recs.trims.right.size() == nr; }
             if (!recs.dup.empty()) { job.dup = recs.dup.data(); job_ok = job_ok && recs.dup.size() == nr; }
+            if (!recs.xs.empty()) { job.xs = recs.xs.data(); job_ok = job_ok && recs.xs.size() == nr; }
             job.report_unaligned = fmt == 6 ? 1 : 0; job.pe_mode = pe_mode;
             job.pk_words = R.pk_words; job.n_pk_words = R.n_pk_words; job.pk_lens16 = R.pk_lens16; job.pk_exc = R.pk_exc; job.n_pk_exc = R.n_pk_exc;
             job.prep = R.sam_prep;

@@ -247,6 +247,7 @@ int  bk_ctx_set_params(bk_ctx *ctx, const bk_align_params *p);
  *   "coverage_buf_bytes" (what its staging holds now, device and page-locked; read only)
  *   "dup_table_slots" (slots of bk_mark_duplicates' table; 0 - the default - derives them per call: the smallest power of two
  *   >= 2 n, at least 1024; any other value is checked by the call), "dup_buf_bytes" (what its staging and table hold now; read only)
+ *   "junction_table_slots", "junction_buf_bytes" (the same two for bk_junctions)
  * returns the old value or <0 */
 int64_t bk_ctx_tune(bk_ctx *ctx, const char *name, int64_t value);
 
@@ -635,9 +636,11 @@ int  bk_constraints_check(bk_constraints *set, const bk_constraint_req *reqs, ui
  * record i is read i, and n_reads counts both.  With `src` (-r5: a read owns a record per reported locus) n_reads counts the
  * RECORDS and n_src_reads the reads; record i belongs to read src[i].
  *   by read:   bases / offs / lens, names / name_ofs, pk_*, seg2 and the head start (`prep`, given the reads alone)
- *   by record: hits, the entries of order, trim_left / trim_right, src, dup
+ *   by record: hits, the entries of order, trim_left / trim_right, src, dup, xs
  * What a record may carry besides its bk_hit:
  *   dup                    - the verdict of bk_mark_duplicates (below): FLAG |= 0x400 on an accepted record, nothing else moves;
+ *   xs                     - the strand answer of bk_junctions (below): '+' or '-' appends XS:A:<c> to an accepted record's line, behind
+ *                            NM / MD where bk_sam_format_tags writes those; any other byte, and every unaccepted line: nothing;
  *   trim_left / trim_right - end trims in read orientation (-x, -A, -c: tsSegLoci.TrimLeft / TrimRight): POS moves to AdjStartLoci,
  *                            the M run shrinks to AdjHitLen and the trimmed ends are written as soft clips, swapped on the '-' strand;
  *   seg2 of its read       - a second segment (flags & 5: microInDel or splice junction) adds <gap>N, <n>I or <gap>D and <len2>M
@@ -676,6 +679,7 @@ typedef struct bk_sam_job {
     const uint16_t *trim_left;    /* NULL (both), or one per RECORD, read orientation                                      */
     const uint16_t *trim_right;
     const uint8_t  *dup;          /* NULL, or one per RECORD (--mark-duplicates): non-zero adds 0x400 to the FLAG of an accepted record */
+    const uint8_t  *xs;           /* NULL, or one per RECORD (--splice-strand): '+' or '-' adds \tXS:A:<c> at the end of an accepted record's line */
 } bk_sam_job;
 /* Optional head start: everything of a job that is known once the reads are aligned - the read store, the names, the buffers the
  * text leaves the device through - can travel while the host still sorts.  bk_sam_prepare() returns at once (a thread of the library
@@ -832,6 +836,62 @@ typedef struct bk_dup_totals {
  * power of two or is smaller than n.  n == 0 does nothing (totals may be NULL).  The probe loops are bounded by the table's size:
  * a lane that finds neither its group nor an empty slot - which cannot happen - ends the call with BK_ERR_INTERNAL. */
 int  bk_mark_duplicates(bk_ctx *ctx, const bk_dup_req *reqs, uint64_t n, uint8_t *out, bk_dup_totals *totals);
+
+/* ---- splice junctions: the junction table and XS:A (--junctions, --splice-strand) ---------------------------------
+ * Ours: the reference writes a BED line per spliced read ("<out>.jct") with the READ's strand and no optional field.  THE RULE.
+ * Requests.  A junction request comes from an accepted record of the FINAL record set whose line as written has an N: the line is
+ * [c5 S] m M [c3 S] gap N m2 M from POS.  start = POS - 1 + m, 0-based, the first intron base; end = start + gap, one past the
+ * last intron base; overhang = min(m, m2); chrom_id = the EntryID of RNAME.
+ * Motif of (sequence, start, end), from the sequence AS INDEXED (the codes a c g t n of the 4-bit target, nibble & 7, case gone),
+ * d = the bases at start and start + 1, a = the bases at end - 2 and end - 1:
+ *     1  GT..AG  +        2  CT..AC  -        3  GC..AG  +        4  CT..GC  -        5  AT..AC  +        6  GT..AT  -
+ *     0  anything else, any n, or end - start < 4: no strand
+ * The read's own strand plays no part.
+ * Junction table.  Requests with equal (chrom_id, start, end) are one junction; it carries `reads`, the number of its requests,
+ * `max_overhang`, the largest overhang among them, its motif and its strand ('+', '-' or '.').  Junctions leave the library sorted by
+ * (sequence in INDEX order, start, end): the keys are unique, so the order is total and depends neither on how the device schedules
+ * the requests nor on their order.
+ * Flagged requests.  A request whose sequence does not exist, whose start is 0, whose end is <= start or >= the sequence's length, or
+ * whose overhang is 0 is FLAGGED: its strand answer is 0, it counts in no junction and changes nothing for the other requests. */
+typedef struct bk_junction_req {
+    uint32_t chrom_id;           /* EntryID                                                                   */
+    uint32_t start;              /* first intron base, 0-based                                                */
+    uint32_t end;                /* one past the last intron base                                             */
+    uint16_t overhang;           /* min(m, m2) of the line                                                    */
+    uint16_t reserved;
+} bk_junction_req;               /* 16 bytes */
+typedef struct bk_junction {
+    uint32_t chrom_id, start, end;
+    uint32_t reads;              /* requests of this junction                                                 */
+    uint16_t max_overhang;
+    uint8_t  motif;              /* 0..6                                                                      */
+    uint8_t  strand;             /* '+', '-' or '.'                                                           */
+} bk_junction;                   /* 20 bytes */
+typedef struct bk_junction_totals {
+    uint64_t requests;           /* n                                                                         */
+    uint64_t junctions;          /* distinct keys among the requests that are not flagged                     */
+    uint64_t flagged;
+    uint64_t max_reads;          /* requests of the junction that has most                                    */
+    uint64_t by_motif[7];        /* junctions of motif 0..6                                                   */
+} bk_junction_totals;
+/* Host arrays, blocking, on the context's stream.  strand_out (n bytes, may be NULL): '+' or '-', the strand of request i's junction,
+ * or 0 - its motif is 0, or the request is flagged.  out / cap: room for the table; *n_junctions (may be NULL) is the number of
+ * junctions.  out == NULL with cap == 0 asks for strands and totals alone.  When cap is smaller than the junction count the call returns
+ * BK_ERR_MEM with *n_junctions set and nothing else written, to be repeated with a larger array (n always suffices).
+ * On the device: an open-addressing table of "junction_table_slots" slots of 16 bytes (owner, count, overhang, motif), linear probing.
+ * A lane per request claims the first empty slot of its probe sequence with a compare-and-swap of its own index, or joins the slot
+ * whose owner's FULL key equals its own, and there adds itself and raises the overhang by an atomic maximum.  Behind the kernel
+ * boundary only the owner of a slot reads the target - two dinucleotides per junction, not per read - writes the motif into the slot
+ * and emits the junction; a third pass hands every request its slot's strand.  The emitted junctions are ordered by two stable radix
+ * sorts (on end, then on entry index << 32 | start) and gathered; the requests are never sorted.  All requests, the table and the
+ * emitted junctions are resident at once: 53 bytes per request, 16 per slot and 48 per junction for the sorts.  Staging and table belong to the context and are made
+ * by the first call (a run without the options allocates nothing; "junction_buf_bytes", read only, says what is held).
+ * BK_ERR_PARAMS, before anything is launched: a NULL context, NULL reqs with n > 0, n >= 2^32 - 1, out == NULL with cap > 0, a
+ * "junction_table_slots" that is set and is no power of two or is smaller than n.  n == 0 does nothing (totals, when given, are
+ * zeroed).  The probe loops are bounded by the table's size: a lane that finds neither its junction nor an empty slot - which cannot
+ * happen - ends the call with BK_ERR_INTERNAL. */
+int  bk_junctions(bk_ctx *ctx, const bk_junction_req *reqs, uint64_t n, uint8_t *strand_out, bk_junction *out, uint64_t cap, uint64_t *n_junctions,
+                  bk_junction_totals *totals);
 
 /* ---- test hook: the search stage on its own ------------------------------------------------------------------------
  * LocateFirstExact / LocateLastExact (SfxArrayV2.cpp:7765-7876, :7914-8027) are two kernels here (k-mer table + key arrays, bk_search.hip); to
