@@ -1,30 +1,23 @@
 // bk_dups.hip - duplicate marking (bk_mark_duplicates of include/biokanga_amd.h, where THE RULE is stated: templates with equal keys -
 // sequence, unclipped 5' position(s), strand(s) - form a group, the template with the highest score stays, the earlier request among equal
-// scores, every other one is a duplicate).  No sort: an open-addressing table of bk::DupSlot (owner, best, count) in HBM, linear probing,
-// a lane per request, two kernels.  k_dup_group: the lane walks its probe sequence; an empty slot is claimed by a compare-and-swap of the
-// lane's own request index into `owner`, an occupied one is the lane's group when the FULL key of reqs[owner] equals its own (reqs is not
-// written during the call, so the owner's request may be read as soon as its index has been seen); on its slot the lane raises `best` to
-// score << 32 | (0xFFFFFFFF - index) by an atomic maximum and counts itself.  Slots only ever go from empty to owned, and all lanes of a
-// group walk the same sequence: the first slot of it that is not another group's is claimed by exactly one of them and joined by the rest,
-// so a group has one slot whatever the scheduling, and the maximum makes the keeper independent of it too.  k_dup_verdict, behind the
-// kernel boundary: the lane finds its slot again; it is kept iff the low word of `best` names it.  Groups (= owners), the largest count
-// and the flagged requests are reduced over the block before they reach the totals.  Both probe loops end after `slots` steps: with
-// slots >= n an empty slot or the group is always met before that, so running out is a bug - it raises the error word and the call
-// returns BK_ERR_INTERNAL instead of hanging.
+// scores, every other one is a duplicate).  No sort: the grouping table of bk_dev_group.h with bk::DupSlot (owner, best, count), a lane per
+// request, two kernels.  k_dup_group: the lane finds or claims its group's slot; on it the lane raises `best` to
+// score << 32 | (0xFFFFFFFF - index) by an atomic maximum and counts itself: a group has one slot whatever the scheduling, and the maximum
+// makes the keeper independent of it too.  k_dup_verdict, behind the kernel boundary: the lane finds its slot again; it is kept iff the
+// low word of `best` names it.  Groups (= owners), the largest count and the flagged requests are reduced over the block before they
+// reach the totals.  A lane that runs out of slots raises the error word (bk_dev_group.h says why that is a bug).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "bk_ctx_int.h"
+#include "bk_dev_group.h"
 #include "bk_env.h"
-#include "bk_wait.h"
 
 namespace {
 using namespace bk;
 
 constexpr int kDupBlock = 256;                                       // threads per block of every kernel here
 constexpr uint32_t kDupWaves = kDupBlock / 64;
-constexpr uint32_t kDupEmpty = 0xFFFFFFFFu;                          // DupSlot::owner of a slot nobody has claimed (no request has this index: n < 2^32 - 1)
 enum { kDupGroups = 0, kDupMaxGroup = 1, kDupFlagged = 2, kDupError = 3, kDupTotWords = 4 };
 
 // a template's key with the ends of a pair in canonical order: (a, strand bit 0) <= (b, strand bit 1), '+' < '-'; bit 2: a pair
@@ -52,26 +45,13 @@ __device__ __forceinline__ DupKey dup_key(const uint4 q)
 
 __device__ __forceinline__ bool dup_same(const DupKey &x, const DupKey &y) { return x.chrom == y.chrom && x.a == y.a && x.b == y.b && x.s == y.s; }
 
-__device__ __forceinline__ uint64_t dup_hash(const DupKey &k)
-{
-    uint64_t h = ((uint64_t)k.chrom << 32 | (uint32_t)k.a) * 0x9E3779B97F4A7C15ULL;
-    h ^= ((uint64_t)k.s << 32 | (uint32_t)k.b) + 0xD6E8FEB86659FD93ULL + (h << 6) + (h >> 2);
-    h ^= h >> 33; h *= 0xFF51AFD7ED558CCDULL;
-    h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ULL;
-    h ^= h >> 33;
-    return h;
-}
+__device__ __forceinline__ uint64_t dup_hash(const DupKey &k) { return group_hash((uint64_t)k.chrom << 32 | (uint32_t)k.a, (uint64_t)k.s << 32 | (uint32_t)k.b); }
 
 __device__ __forceinline__ bool dup_valid(const DevIndex &ix, const uint4 q)
 {
     const uint32_t e = q.x <= ix.max_id ? ix.id2idx[q.x] : 0xffffffffu;
     const uint32_t st = q.w & 0xffu, sm = (q.w >> 8) & 0xffu;
     return e < ix.n_ent && (st == '+' || st == '-') && (sm == 0 || sm == '+' || sm == '-');
-}
-
-__global__ void __launch_bounds__(kDupBlock) k_dup_clear(DupSlot *__restrict__ table, uint64_t slots)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) table[i] = DupSlot{0ULL, kDupEmpty, 0u};
 }
 
 // pass 1: request j finds or claims its group's slot, offers itself as the keeper and is counted (mask = slots - 1)
@@ -82,23 +62,10 @@ __global__ void __launch_bounds__(kDupBlock) k_dup_group(DevIndex ix, const uint
     const uint4 q = reqs[j];
     if (!dup_valid(ix, q)) return;
     const DupKey k = dup_key(q);
-    const unsigned long long offer = (unsigned long long)(q.w >> 16) << 32 | (kDupEmpty - (uint32_t)j);
-    uint64_t slot = dup_hash(k) & mask;
-    for (uint64_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
-        uint32_t *ow = &table[slot].owner;
-        // (relaxed: a stale "empty" only sends the lane into the compare-and-swap, which answers with the owner there is)
-        uint32_t o = __hip_atomic_load(ow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (o == kDupEmpty) {
-            o = atomicCAS(ow, kDupEmpty, (uint32_t)j);
-            if (o == kDupEmpty) o = (uint32_t)j;
-        }
-        if (o == (uint32_t)j || dup_same(k, dup_key(reqs[o]))) {          // (o < n: only requests of this call claim slots)
-            atomicMax(&table[slot].best, offer);
-            atomicAdd(&table[slot].count, 1u);
-            return;
-        }
-    }
-    atomicOr(&tot[kDupError], 1ULL);
+    const uint64_t slot = group_claim(table, mask, dup_hash(k), (uint32_t)j, [&](uint32_t o) { return dup_same(k, dup_key(reqs[o])); });
+    if (slot == ~0ULL) { atomicOr(&tot[kDupError], 1ULL); return; }
+    atomicMax(&table[slot].best, (unsigned long long)(q.w >> 16) << 32 | (kGroupEmpty - (uint32_t)j));
+    atomicAdd(&table[slot].count, 1u);
 }
 
 // pass 2: out[j] = 0 kept, 1 duplicate, 2 flagged; tot: groups, largest group, flagged
@@ -116,18 +83,12 @@ __global__ void __launch_bounds__(kDupBlock) k_dup_verdict(DevIndex ix, const ui
         uint8_t answer = 2;
         if (!flagged) {
             const DupKey k = dup_key(q);
-            uint64_t slot = dup_hash(k) & mask;
-            lost = true;
-            for (uint64_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
-                const DupSlot t = table[slot];
-                if (t.owner == kDupEmpty) break;                        // (pass 1 left this request in no slot)
-                if (t.owner == (uint32_t)j || dup_same(k, dup_key(reqs[t.owner]))) {
-                    answer = (uint32_t)t.best == kDupEmpty - (uint32_t)j ? 0 : 1;
-                    owner = t.owner == (uint32_t)j;
-                    cnt = owner ? t.count : 0u;
-                    lost = false;
-                    break;
-                }
+            DupSlot t;
+            lost = group_find(table, mask, dup_hash(k), (uint32_t)j, [&](uint32_t o) { return dup_same(k, dup_key(reqs[o])); }, t) == ~0ULL;       // (pass 1 left this request in no slot)
+            if (!lost) {
+                answer = (uint32_t)t.best == kGroupEmpty - (uint32_t)j ? 0 : 1;
+                owner = t.owner == (uint32_t)j;
+                cnt = owner ? t.count : 0u;
             }
         }
         out[j] = answer;
@@ -150,34 +111,16 @@ __global__ void __launch_bounds__(kDupBlock) k_dup_verdict(DevIndex ix, const ui
 
 extern "C" int bk_mark_duplicates(bk_ctx *c, const bk_dup_req *reqs, uint64_t n, uint8_t *out, bk_dup_totals *totals)
 {
-    if (!c || (n && (!reqs || !out)) || n >= 0xFFFFFFFFULL) return BK_ERR_PARAMS;
+    if (!c || (n && (!reqs || !out)) || n >= bk::kGroupEmpty) return BK_ERR_PARAMS;
     if (totals) *totals = bk_dup_totals{};
     if (!n) return BK_OK;
     if (c->entries.empty() || !c->ix.id2idx) return BK_ERR_PARAMS;
     bk::DupStage &B = c->dup;
-    uint64_t slots = B.table_slots;
-    if (slots) {
-        if ((slots & (slots - 1)) || slots < n) return BK_ERR_PARAMS;
-    } else {
-        slots = 1024;
-        while (slots < 2 * n) slots <<= 1;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    bk::GroupCall g;
+    if (const int rc = bk::group_begin(c, B.table_slots, reqs, n, B.reqs, B.table, B.tot, kDupTotWords, bk::DupSlot{0ULL, bk::kGroupEmpty, 0u}, [&]() -> int { HIP_TRY(B.out.ensure(n)); return BK_OK; }, g)) return rc;
+    const uint64_t slots = g.slots;
     hipStream_t s = c->stream;
     const bool timing = bk::env::timing();
-    const double t_start = bk::now_s();
-    HIP_TRY(B.reqs.ensure(n));
-    HIP_TRY(B.out.ensure(n));
-    HIP_TRY(B.table.ensure(slots));
-    HIP_TRY(B.tot.ensure(kDupTotWords));
-    const double t_alloc = bk::now_s();
-    HIP_TRY(hipMemsetAsync(B.tot.get(), 0, kDupTotWords * 8, s));
-    const uint32_t clear_blocks = (uint32_t)std::min<uint64_t>((slots + kDupBlock - 1) / kDupBlock, 1u << 16);
-    hipLaunchKernelGGL(k_dup_clear, dim3(clear_blocks), dim3(kDupBlock), 0, s, B.table.get(), slots);
-    HIP_TRY(hipGetLastError());
-    if (bk::upload_host(B.reqs.get(), reqs, (size_t)n * sizeof(bk_dup_req), c->device)) return BK_ERR_INTERNAL;
-    HIP_TRY(hipStreamSynchronize(s));
-    const double t_up = bk::now_s();
     const uint32_t blocks = (uint32_t)((n + kDupBlock - 1) / kDupBlock);
     const uint4 *d_reqs = reinterpret_cast<const uint4 *>(B.reqs.get());
     hipLaunchKernelGGL(k_dup_group, dim3(blocks), dim3(kDupBlock), 0, s, c->ix, d_reqs, n, B.table.get(), slots - 1, B.tot.get());
@@ -203,7 +146,7 @@ extern "C" int bk_mark_duplicates(bk_ctx *c, const bk_dup_req *reqs, uint64_t n,
     if (timing)
         fprintf(stderr, "bk timing: mark duplicates: %llu requests, %llu slots (%.1f MB of requests and answers, %.1f MB of table): buffers %.2f, clear + upload %.2f, k_dup_group %.2f, k_dup_verdict %.2f, "
                         "answers back %.2f, whole call %.1f ms\n",
-                (unsigned long long)n, (unsigned long long)slots, 1e-6 * (double)(n * 17), 1e-6 * (double)(slots * sizeof(bk::DupSlot)), 1e3 * (t_alloc - t_start), 1e3 * (t_up - t_alloc), 1e3 * (t_group - t_up),
-                1e3 * (t_verdict - t_group), 1e3 * (bk::now_s() - t_verdict), 1e3 * (bk::now_s() - t_start));
+                (unsigned long long)n, (unsigned long long)slots, 1e-6 * (double)(n * 17), 1e-6 * (double)(slots * sizeof(bk::DupSlot)), 1e3 * (g.t_alloc - g.t_start), 1e3 * (g.t_up - g.t_alloc), 1e3 * (t_group - g.t_up),
+                1e3 * (t_verdict - t_group), 1e3 * (bk::now_s() - t_verdict), 1e3 * (bk::now_s() - g.t_start));
     return BK_OK;
 }

@@ -1,31 +1,27 @@
 // bk_junctions.hip - the junction table and the transcript strand of spliced records (bk_junctions of include/biokanga_amd.h, where THE RULE
 // is stated: requests with equal (sequence, start, end) are one junction; its motif - and with it its strand - is read from the two target
-// bases at each end of the gap, in the sequence as indexed).  The grouping is that of bk_dups.hip: an open-addressing table of bk::JctSlot
-// (owner, count, overhang, motif) in HBM, linear probing, a lane per request, the request one 16-byte load.  k_jct_group: the lane claims
-// the first empty slot of its probe sequence by a compare-and-swap of its own request index into `owner`, or joins the slot whose owner's
-// FULL key equals its own; there it counts itself and raises the overhang by an atomic maximum.  k_jct_classify, behind the kernel boundary:
+// bases at each end of the gap, in the sequence as indexed).  The grouping table is that of bk_dev_group.h with bk::JctSlot (owner, count,
+// overhang, motif), a lane per request, the request one 16-byte load.  k_jct_group: the lane finds or claims its junction's slot; there
+// it counts itself and raises the overhang by an atomic maximum.  k_jct_classify, behind the kernel boundary:
 // the lane finds its slot again, and only the owner goes on - the target is gathered once per junction, not once per read: two dinucleotides
 // out of DevIndex::tgt4 (one may lie across two of its 64-bit words), the motif into the slot, the bk_junction and its two sort keys into the
 // emit arrays at a place taken from one counter per wave.  k_jct_answer: every request reads its slot's strand; junctions, the largest
 // count, the motifs and the flagged requests are reduced over the block before they reach the totals.  The emitted junctions are then
 // ordered by two stable radix sorts of (key, place) - on `end`, then on entry index << 32 | start - and gathered; the requests are never
-// sorted.  Every probe loop ends after `slots` steps: with slots >= n an empty slot or the group is always met before that, so running out is
-// a bug - it raises the error word and the call returns BK_ERR_INTERNAL instead of hanging.
+// sorted.  A lane that runs out of slots raises the error word (bk_dev_group.h says why that is a bug).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "bk_ctx_int.h"
+#include "bk_dev_group.h"
 #include "bk_env.h"
 #include "bk_prim.h"
-#include "bk_wait.h"
 
 namespace {
 using namespace bk;
 
 constexpr int kJctBlock = 256;                                       // threads per block of every kernel here
 constexpr uint32_t kJctWaves = kJctBlock / 64;
-constexpr uint32_t kJctEmpty = 0xFFFFFFFFu;                          // JctSlot::owner of a slot nobody has claimed (no request has this index: n < 2^32 - 1)
 constexpr uint32_t kJctNoEntry = 0xFFFFFFFFu;
 enum { kJctJunctions = 0, kJctMaxReads = 1, kJctFlagged = 2, kJctError = 3, kJctEmitted = 4, kJctMotif0 = 5, kJctTotWords = 12 };
 static_assert(sizeof(bk_junction_req) == 16 && sizeof(bk_junction) == 20 && sizeof(JctSlot) == 16, "record layout");
@@ -33,15 +29,7 @@ static_assert(sizeof(bk_junction_req) == 16 && sizeof(bk_junction) == 20 && size
 // q: a bk_junction_req as one 16-byte load - chrom_id, start, end, overhang | reserved << 16
 __device__ __forceinline__ bool jct_same(const uint4 a, const uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
 
-__device__ __forceinline__ uint64_t jct_hash(const uint4 q)
-{
-    uint64_t h = ((uint64_t)q.x << 32 | q.y) * 0x9E3779B97F4A7C15ULL;
-    h ^= (uint64_t)q.z + 0xD6E8FEB86659FD93ULL + (h << 6) + (h >> 2);
-    h ^= h >> 33; h *= 0xFF51AFD7ED558CCDULL;
-    h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ULL;
-    h ^= h >> 33;
-    return h;
-}
+__device__ __forceinline__ uint64_t jct_hash(const uint4 q) { return group_hash((uint64_t)q.x << 32 | q.y, (uint64_t)q.z); }
 
 // the entry index of the request's sequence, or kJctNoEntry for a request that is flagged
 __device__ __forceinline__ uint32_t jct_entry(const DevIndex &ix, const uint4 q)
@@ -77,11 +65,6 @@ __device__ __forceinline__ uint32_t jct_motif(uint32_t d, uint32_t a)
     return 0;
 }
 
-__global__ void __launch_bounds__(kJctBlock) k_jct_clear(JctSlot *__restrict__ table, uint64_t slots)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x) table[i] = JctSlot{kJctEmpty, 0u, 0u, 0u};
-}
-
 // pass 1: request j finds or claims its junction's slot, is counted there and offers its overhang (mask = slots - 1)
 __global__ void __launch_bounds__(kJctBlock) k_jct_group(DevIndex ix, const uint4 *__restrict__ reqs, uint64_t n, JctSlot *table, uint64_t mask, unsigned long long *tot)
 {
@@ -89,34 +72,16 @@ __global__ void __launch_bounds__(kJctBlock) k_jct_group(DevIndex ix, const uint
     if (j >= n) return;
     const uint4 q = reqs[j];
     if (jct_entry(ix, q) == kJctNoEntry) return;
-    uint64_t slot = jct_hash(q) & mask;
-    for (uint64_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
-        uint32_t *ow = &table[slot].owner;
-        // (relaxed: a stale "empty" only sends the lane into the compare-and-swap, which answers with the owner there is)
-        uint32_t o = __hip_atomic_load(ow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (o == kJctEmpty) {
-            o = atomicCAS(ow, kJctEmpty, (uint32_t)j);
-            if (o == kJctEmpty) o = (uint32_t)j;
-        }
-        if (o == (uint32_t)j || jct_same(q, reqs[o])) {                   // (o < n: only requests of this call claim slots)
-            atomicAdd(&table[slot].count, 1u);
-            atomicMax(&table[slot].overhang, q.w & 0xffffu);
-            return;
-        }
-    }
-    atomicOr(&tot[kJctError], 1ULL);
+    const uint64_t slot = group_claim(table, mask, jct_hash(q), (uint32_t)j, [&](uint32_t o) { return jct_same(q, reqs[o]); });
+    if (slot == ~0ULL) { atomicOr(&tot[kJctError], 1ULL); return; }
+    atomicAdd(&table[slot].count, 1u);
+    atomicMax(&table[slot].overhang, q.w & 0xffffu);
 }
 
-// the slot of request j's junction as pass 1 left it, or ~0 when there is none (which pass 1 rules out)
-__device__ __forceinline__ uint64_t jct_find(const uint4 *__restrict__ reqs, const JctSlot *table, uint64_t mask, uint64_t j, const uint4 q)
+// the slot of request j's junction as pass 1 left it and what it holds, or ~0 when there is none (which pass 1 rules out)
+__device__ __forceinline__ uint64_t jct_find(const uint4 *__restrict__ reqs, const JctSlot *table, uint64_t mask, uint64_t j, const uint4 q, JctSlot &t)
 {
-    uint64_t slot = jct_hash(q) & mask;
-    for (uint64_t step = 0; step <= mask; step++, slot = (slot + 1) & mask) {
-        const uint32_t o = table[slot].owner;
-        if (o == kJctEmpty) break;
-        if (o == (uint32_t)j || jct_same(q, reqs[o])) return slot;
-    }
-    return ~0ULL;
+    return group_find(table, mask, jct_hash(q), (uint32_t)j, [&](uint32_t o) { return jct_same(q, reqs[o]); }, t);
 }
 
 // pass 2: the owner of every slot reads its junction's motif from the target, writes it into the slot and emits the junction: jct[p],
@@ -134,9 +99,10 @@ __global__ void __launch_bounds__(kJctBlock) k_jct_classify(DevIndex ix, const u
         q = reqs[j];
         e = jct_entry(ix, q);
         if (e != kJctNoEntry) {
-            const uint64_t slot = jct_find(reqs, table, mask, j, q);
+            JctSlot t;
+            const uint64_t slot = jct_find(reqs, table, mask, j, q, t);
             lost = slot == ~0ULL;
-            if (!lost && table[slot].owner == (uint32_t)j) {
+            if (!lost && t.owner == (uint32_t)j) {
                 owner = true;
                 const uint64_t g0 = ix.ent_start[e];
                 uint32_t motif = 0;
@@ -144,8 +110,8 @@ __global__ void __launch_bounds__(kJctBlock) k_jct_classify(DevIndex ix, const u
                 const uint32_t strand = motif == 0 ? (uint32_t)'.' : ((motif & 1u) ? (uint32_t)'+' : (uint32_t)'-');
                 word = motif | strand << 8;
                 table[slot].motif = word;
-                count = table[slot].count;
-                overhang = table[slot].overhang;
+                count = t.count;
+                overhang = t.overhang;
             }
         }
     }
@@ -181,10 +147,9 @@ __global__ void __launch_bounds__(kJctBlock) k_jct_answer(DevIndex ix, const uin
         flagged = jct_entry(ix, q) == kJctNoEntry;
         uint8_t answer = 0;
         if (!flagged) {
-            const uint64_t slot = jct_find(reqs, table, mask, j, q);
-            lost = slot == ~0ULL;
+            JctSlot t;
+            lost = jct_find(reqs, table, mask, j, q, t) == ~0ULL;
             if (!lost) {
-                const JctSlot t = table[slot];
                 motif = t.motif & 0xffu;
                 const uint32_t s = t.motif >> 8 & 0xffu;
                 answer = s == '.' ? (uint8_t)0 : (uint8_t)s;
@@ -242,7 +207,7 @@ __global__ void __launch_bounds__(kJctBlock) k_jct_gather(const uint32_t *__rest
 extern "C" int bk_junctions(bk_ctx *c, const bk_junction_req *reqs, uint64_t n, uint8_t *strand_out, bk_junction *out, uint64_t cap, uint64_t *n_junctions,
                             bk_junction_totals *totals)
 {
-    if (!c || (n && !reqs) || n >= 0xFFFFFFFFULL || (!out && cap)) return BK_ERR_PARAMS;
+    if (!c || (n && !reqs) || n >= bk::kGroupEmpty || (!out && cap)) return BK_ERR_PARAMS;
     if (!n) {
         if (n_junctions) *n_junctions = 0;
         if (totals) *totals = bk_junction_totals{};
@@ -250,33 +215,15 @@ extern "C" int bk_junctions(bk_ctx *c, const bk_junction_req *reqs, uint64_t n, 
     }
     if (c->entries.empty() || !c->ix.id2idx || !c->ix.tgt4) return BK_ERR_PARAMS;
     bk::JunctionStage &B = c->jct;
-    uint64_t slots = B.table_slots;
-    if (slots) {
-        if ((slots & (slots - 1)) || slots < n) return BK_ERR_PARAMS;
-    } else {
-        slots = 1024;
-        while (slots < 2 * n) slots <<= 1;
-    }
-    HIP_TRY(hipSetDevice(c->device));
+    auto more_buffers = [&]() -> int {
+        HIP_TRY(B.strand.ensure(n)); HIP_TRY(B.jct.ensure(n)); HIP_TRY(B.key_end[0].ensure(n)); HIP_TRY(B.key_hi[0].ensure(n)); HIP_TRY(B.place[0].ensure(n));
+        return BK_OK;
+    };
+    bk::GroupCall g;
+    if (const int rc = bk::group_begin(c, B.table_slots, reqs, n, B.reqs, B.table, B.tot, kJctTotWords, bk::JctSlot{bk::kGroupEmpty, 0u, 0u, 0u}, more_buffers, g)) return rc;
+    const uint64_t slots = g.slots;
     hipStream_t s = c->stream;
     const bool timing = bk::env::timing();
-    const double t_start = bk::now_s();
-    HIP_TRY(B.reqs.ensure(n));
-    HIP_TRY(B.strand.ensure(n));
-    HIP_TRY(B.table.ensure(slots));
-    HIP_TRY(B.tot.ensure(kJctTotWords));
-    HIP_TRY(B.jct.ensure(n));
-    HIP_TRY(B.key_end[0].ensure(n));
-    HIP_TRY(B.key_hi[0].ensure(n));
-    HIP_TRY(B.place[0].ensure(n));
-    const double t_alloc = bk::now_s();
-    HIP_TRY(hipMemsetAsync(B.tot.get(), 0, kJctTotWords * 8, s));
-    const uint32_t clear_blocks = (uint32_t)std::min<uint64_t>((slots + kJctBlock - 1) / kJctBlock, 1u << 16);
-    hipLaunchKernelGGL(k_jct_clear, dim3(clear_blocks), dim3(kJctBlock), 0, s, B.table.get(), slots);
-    HIP_TRY(hipGetLastError());
-    if (bk::upload_host(B.reqs.get(), reqs, (size_t)n * sizeof(bk_junction_req), c->device)) return BK_ERR_INTERNAL;
-    HIP_TRY(hipStreamSynchronize(s));
-    const double t_up = bk::now_s();
     const uint32_t blocks = (uint32_t)((n + kJctBlock - 1) / kJctBlock);
     const uint4 *d_reqs = reinterpret_cast<const uint4 *>(B.reqs.get());
     uint32_t *d_jct = reinterpret_cast<uint32_t *>(B.jct.get());
@@ -338,7 +285,7 @@ extern "C" int bk_junctions(bk_ctx *c, const bk_junction_req *reqs, uint64_t n, 
         fprintf(stderr, "bk timing: junctions: %llu requests, %llu slots, %llu junctions (%.1f MB of requests, answers and emitted junctions, %.1f MB of table): buffers %.2f, "
                         "clear + upload %.2f, k_jct_group %.2f, k_jct_classify %.2f, k_jct_answer + totals back %.2f, sort + answers back %.2f, whole call %.1f ms\n",
                 (unsigned long long)n, (unsigned long long)slots, (unsigned long long)nj, 1e-6 * (double)(n * (16 + 1 + 20 + 4 + 8 + 4)), 1e-6 * (double)(slots * sizeof(bk::JctSlot)),
-                1e3 * (t_alloc - t_start), 1e3 * (t_up - t_alloc), 1e3 * (t_group - t_up), 1e3 * (t_classify - t_group), 1e3 * (t_answer - t_classify),
-                1e3 * (bk::now_s() - t_answer), 1e3 * (bk::now_s() - t_start));
+                1e3 * (g.t_alloc - g.t_start), 1e3 * (g.t_up - g.t_alloc), 1e3 * (t_group - g.t_up), 1e3 * (t_classify - t_group), 1e3 * (t_answer - t_classify),
+                1e3 * (bk::now_s() - t_answer), 1e3 * (bk::now_s() - g.t_start));
     return BK_OK;
 }

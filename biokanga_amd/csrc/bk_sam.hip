@@ -15,6 +15,7 @@
 
 #include "bk_ctx_int.h"
 #include "bk_env.h"
+#include "bk_line.h"
 #include "bk_wait.h"
 #include "bk_samtags.h"
 
@@ -99,27 +100,13 @@ struct SamRec {
     char gop;
 };
 
-// trims and second segment of an accepted record (format_rec of host/report.cpp; CAligner::ReportBAMread, Aligner.cpp:5960-6033)
+// trims and second segment of an accepted record: the line as written (bk_line.h), as format_rec of host/report.cpp takes it
 __device__ __forceinline__ void sam_rec_ext(const SamDev &d, const bk_hit &h, SamRec &r)
 {
-    if (d.trim_l) {
-        const uint32_t tl = d.trim_l[r.i], tr = d.trim_r[r.i];
-        const bool plus = h.strand == '+';
-        r.pos = h.match_loci + (plus ? tl : tr);
-        r.mlen = (uint32_t)h.match_len - tl - tr;
-        r.clip5 = plus ? tl : tr;
-        r.clip3 = plus ? tr : tl;
-    }
-    if (d.seg2) {
-        const bk_seg2 g = d.seg2[r.rd];
-        if (g.flags & 5) {                                  // FlgInDel or FlgSplice
-            const long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len);
-            if (g.flags & 4) { r.gop = 'N'; r.gap = gap; }
-            else if (g.flags & 2) { r.gop = 'I'; r.gap = (long)r.len - ((long)h.match_len + g.match_len); }
-            else { r.gop = 'D'; r.gap = gap < 0 ? -gap : gap; }
-            r.len2 = g.match_len;
-        }
-    }
+    const uint32_t tl = d.trim_l ? d.trim_l[r.i] : 0u, tr = d.trim_l ? d.trim_r[r.i] : 0u;
+    const bk::Line L = bk::line_of(h, tl, tr, d.seg2 ? d.seg2[r.rd] : bk_seg2{});
+    r.pos = L.pos; r.mlen = L.m; r.clip5 = L.c5; r.clip3 = L.c3;
+    r.gop = L.gop; r.len2 = L.m2; r.gap = L.gap_written(r.len);
 }
 
 // [clip5 S] len M [clip3 S] [gap N|I|D len2 M]: the second segment follows the 3' clip, which is what the reference writes

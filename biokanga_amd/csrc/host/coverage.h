@@ -1,7 +1,6 @@
 // coverage.h - `align --coverage <file>`: the per-base depth of the accepted records as a bedGraph, made on the first device
-// (bk_coverage_text of include/biokanga_amd.h, where the rule is stated).  The requests are the M runs of the lines as written - the
-// numbers host_sam_tags (report.cpp) hands to bk_samtags: AdjStartLoci, AdjHitLen, the second segment and its N / I / D decision - of the
-// final record set in output order, whatever the output format.
+// (bk_coverage_text of include/biokanga_amd.h, where the rule is stated).  The requests are the M runs of the lines as written
+// (bk::RecordSet::line, bk_line.h) of the final record set in output order, whatever the output format.
 #pragma once
 #include <string>
 #include <vector>
@@ -13,20 +12,9 @@ namespace bkcli {
 // the request of accepted record i; false: its numbers are no walk the request can carry
 inline bool coverage_request(const bk::RecordSet &recs, size_t i, bk_cov_req &q)
 {
-    const bk_hit &h = recs.hits[i];
-    const uint32_t m = recs.a_len(h, i);
-    long gap = 0;
-    uint32_t m2 = 0;
-    if (recs.has_seg2(i)) {
-        const bk_seg2 &g = recs.seg2[recs.RD(i)];
-        const long d = (long)g.match_loci - ((long)h.match_loci + h.match_len);
-        if (g.flags & 4) gap = d;                              // N
-        else if (g.flags & 2) gap = 0;                         // I: the second M run starts where the first ended
-        else gap = d < 0 ? -d : d;                             // D
-        m2 = g.match_len;
-    }
-    if (m > 0xffffu || m2 > 0xffffu || gap > 0x7fffffffL || gap < -0x7fffffffL) return false;
-    q = bk_cov_req{h.chrom_id, recs.a_start(h, i), (uint16_t)m, (uint16_t)m2, (int32_t)gap};
+    const bk::Line L = recs.line(i);                           // (an I's second M run starts where the first ended: gap 0)
+    if (L.m > 0xffffu || L.m2 > 0xffffu || L.gap > 0x7fffffffL || L.gap < -0x7fffffffL) return false;
+    q = bk_cov_req{recs.hits[i].chrom_id, L.pos, (uint16_t)L.m, (uint16_t)L.m2, (int32_t)L.gap};
     return true;
 }
 

@@ -1,7 +1,6 @@
 // duplicates.h - `align --mark-duplicates`: FLAG 0x400 on the records of duplicate templates, grouped on the first device
-// (bk_mark_duplicates of include/biokanga_amd.h, where the rule is stated).  The requests are made of the numbers the writers print -
-// AdjStartLoci, AdjHitLen, the end trims as soft clips, the second segment and its N / I / D decision, as coverage_request and
-// host_sam_tags take them - of the final record set, one per template, in load order: the library's tie-break (the earlier request
+// (bk_mark_duplicates of include/biokanga_amd.h, where the rule is stated).  The requests are made of the lines as written
+// (bk::RecordSet::line, bk_line.h) of the final record set, one per template, in load order: the library's tie-break (the earlier request
 // among equal scores) is then the rule's (the read loaded first).
 #pragma once
 #include <algorithm>
@@ -19,20 +18,9 @@ struct DupEnd {
 
 inline DupEnd duplicate_end(const bk::RecordSet &recs, size_t i)
 {
-    const bk_hit &h = recs.hits[i];
-    const bool plus = h.strand == '+';
-    const long p = (long)recs.a_start(h, i), m = (long)recs.a_len(h, i);
-    const long c_left = plus ? recs.TL(i) : recs.TR(i), c_right = plus ? recs.TR(i) : recs.TL(i);        // soft clips in target order
-    long span = m, m2 = 0;
-    if (recs.has_seg2(i)) {
-        const bk_seg2 &g = recs.seg2[recs.RD(i)];
-        const long d = (long)g.match_loci - ((long)h.match_loci + h.match_len);
-        m2 = g.match_len;
-        if (g.flags & 4) span += d;                            // N
-        else if (!(g.flags & 2)) span += d < 0 ? -d : d;       // D (an I takes no target base)
-        span += m2;
-    }
-    return DupEnd{(int32_t)(plus ? p - c_left : p + span - 1 + c_right), (uint32_t)(m + m2)};
+    const bk::Line L = recs.line(i);
+    const long span = (long)L.m + L.gap + (long)L.m2;          // target bases of the line (an I takes none)
+    return DupEnd{(int32_t)(recs.hits[i].strand == '+' ? (long)L.pos - (long)L.c5 : (long)L.pos + span - 1 + (long)L.c3), L.m + L.m2};
 }
 
 // the request of the template of record i - a fragment - or of records i and mate - a pair, i the end that is handed over first

@@ -1,7 +1,6 @@
 // junctions.h - `align --junctions <file>` / `--splice-strand`: the junction table of the spliced records and their transcript strand
 // (XS:A), both from one call of bk_junctions on the first device (include/biokanga_amd.h, where the rule is stated).  The requests are made
-// of the numbers the writers print - AdjStartLoci, AdjHitLen, the second segment and its gap, as coverage_request and duplicate_end take
-// them - of the final record set: one per accepted record whose line as written has an N.
+// of the lines as written (bk::RecordSet::line, bk_line.h) of the final record set: one per accepted record whose line has an N.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -15,15 +14,12 @@ namespace bkcli {
 // the request of accepted record i when its line is [c5 S] m M [c3 S] gap N m2 M; false: the line has no N, or no gap a request can carry
 inline bool junction_request(const bk::RecordSet &recs, size_t i, bk_junction_req &q)
 {
-    const bk_hit &h = recs.hits[i];
-    if (!recs.has_seg2(i)) return false;
-    const bk_seg2 &g = recs.seg2[recs.RD(i)];
-    if (!(g.flags & 4)) return false;                          // I or D
-    const long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len);
-    const uint64_t m = recs.a_len(h, i), m2 = g.match_len;
-    const uint64_t start = (uint64_t)recs.a_start(h, i) + m;  // POS - 1 + m
-    if (gap <= 0 || start + (uint64_t)gap > 0xFFFFFFFFull) return false;
-    q = bk_junction_req{h.chrom_id, (uint32_t)start, (uint32_t)(start + (uint64_t)gap), (uint16_t)std::min<uint64_t>(std::min(m, m2), 0xffffu), 0};
+    const bk::Line L = recs.line(i);
+    if (L.gop != 'N') return false;                            // one segment, I or D
+    const uint64_t m = L.m, m2 = L.m2;
+    const uint64_t start = (uint64_t)L.pos + m;               // POS - 1 + m
+    if (L.gap <= 0 || start + (uint64_t)L.gap > 0xFFFFFFFFull) return false;
+    q = bk_junction_req{recs.hits[i].chrom_id, (uint32_t)start, (uint32_t)(start + (uint64_t)L.gap), (uint16_t)std::min<uint64_t>(std::min(m, m2), 0xffffu), 0};
     return true;
 }
 

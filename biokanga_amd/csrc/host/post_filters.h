@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../../include/biokanga_amd.h"
+#include "../bk_line.h"
 
 namespace bk {
 
@@ -50,6 +51,8 @@ struct RecordSet {
     uint32_t a_start(const bk_hit &h, size_t i) const { return h.match_loci + (h.strand == '+' ? TL(i) : TR(i)); }       // AdjStartLoci
     uint32_t a_len(const bk_hit &h, size_t i) const { return (uint32_t)h.match_len - TL(i) - TR(i); }                      // AdjHitLen
     uint32_t a_mm(const bk_hit &h, size_t i) const { return trims.empty() ? h.mismatches : trims.mismatches[i]; }         // TrimMismatches
+    // the line of accepted record i as written: POS, the CIGAR's numbers and what its gap takes of the target (bk_line.h)
+    Line line(size_t i) const { return line_of(hits[i], TL(i), TR(i), has_seg2(i) ? seg2[RD(i)] : bk_seg2{}); }
     // no trims yet: none at either end, the mismatches those of the records as they stand
     void ensure_trims()
     {

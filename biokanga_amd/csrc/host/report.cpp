@@ -181,7 +181,7 @@ void report_jct_for_sam(Report &R)
     for (size_t k = 0; k < nr; k++) {
         const uint32_t i = order[k];
         const bk_hit &h = hits[i];
-        if (h.nar != BK_NAR_ACCEPTED || !recs.has_seg2(i) || !(seg2[recs.RD(i)].flags & 4)) continue;
+        if (h.nar != BK_NAR_ACCEPTED || !recs.has_seg2(i) || bk::seg2_op(seg2[recs.RD(i)]) != 'N') continue;
         const bk_seg2 &g = seg2[recs.RD(i)];
         const uint32_t end1 = g.match_loci + g.match_len;
         m = snprintf(ln, sizeof(ln), "%s\t%u\t%u\tarj\t0\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1, (char)h.strand,
@@ -232,22 +232,12 @@ static int host_sam_tags(Report &R, HostSamTags &T)
         if (h.nar != BK_NAR_ACCEPTED || (h.strand != '+' && h.strand != '-')) continue;
         const size_t rd = recs.RD(i);
         const uint32_t len = R.rs.lens[rd];
-        const uint32_t clip5 = h.strand == '+' ? recs.TL(i) : recs.TR(i), clip3 = h.strand == '+' ? recs.TR(i) : recs.TL(i), m = recs.a_len(h, i);
-        long gap = 0;
-        uint32_t m2 = 0;
-        uint8_t gop = 0;
-        if (recs.has_seg2(i)) {
-            const bk_seg2 &g = recs.seg2[rd];
-            const long d = (long)g.match_loci - ((long)h.match_loci + h.match_len);
-            if (g.flags & 4) { gop = 'N'; gap = d; }
-            else if (g.flags & 2) { gop = 'I'; gap = (long)len - ((long)h.match_len + g.match_len); }
-            else { gop = 'D'; gap = d < 0 ? -d : d; }
-            m2 = g.match_len;
-        }
-        if (len > 0xffffu || clip5 > 0xffffu || clip3 > 0xffffu || m > 0xffffu || m2 > 0xffffu || gap > 0x7fffffffL || gap < -0x7fffffffL) continue;      // (no such walk: no tags)
+        const bk::Line L = recs.line(i);
+        const long gap = L.gap_written(len);
+        if (len > 0xffffu || L.c5 > 0xffffu || L.c3 > 0xffffu || L.m > 0xffffu || L.m2 > 0xffffu || gap > 0x7fffffffL || gap < -0x7fffffffL) continue;      // (no such walk: no tags)
         bk_samtag_req q{};
-        q.read_ofs = R.rs.offs[rd]; q.chrom_id = h.chrom_id; q.pos = recs.a_start(h, i); q.read_len = (uint16_t)len; q.strand = h.strand; q.gop = gop;
-        q.c5 = (uint16_t)clip5; q.m = (uint16_t)m; q.c3 = (uint16_t)clip3; q.m2 = (uint16_t)m2; q.gap = (int32_t)gap;
+        q.read_ofs = R.rs.offs[rd]; q.chrom_id = h.chrom_id; q.pos = L.pos; q.read_len = (uint16_t)len; q.strand = h.strand; q.gop = (uint8_t)L.gop;
+        q.c5 = (uint16_t)L.c5; q.m = (uint16_t)L.m; q.c3 = (uint16_t)L.c3; q.m2 = (uint16_t)L.m2; q.gap = (int32_t)gap;
         T.slot[i] = (uint32_t)reqs.size();
         reqs.push_back(q);
     }
@@ -281,7 +271,6 @@ int report_bam(Report &R, const std::string &opath)
     const uint32_t n_ent = R.n_ent;
     const size_t nr = recs.hits.size();
     const auto &order = R.order;
-    const auto &seg2 = recs.seg2;
     const int pe_mode = R.pe_mode, fmt = R.fmt, nthreads = R.nthreads, max_rpt_sam_seqs = R.max_rpt_sam_seqs;
     int rc = 0;
     std::vector<uint8_t> has_hit = seqs_with_hits(hits, n_ent, nthreads);
@@ -364,12 +353,11 @@ int report_bam(Report &R, const std::string &opath)
                 aux += ((R.sam_tags & BK_SAMTAG_NM) ? (tags.nm[tq] <= 255 ? 4u : 5u) : 0u) + ((R.sam_tags & BK_SAMTAG_MD) ? 3u + (uint32_t)tags.md_len(tq) + 1u : 0u);
             const char xs = acc ? recs.xs_of(i) : (char)0;          // --splice-strand: XS as A, behind NM / MD
             if (xs) aux += 4u;
-            const bool two = acc && recs.has_seg2(i);
-            // soft clips in target order: read orientation for '+', swapped for '-' (Aligner.cpp:5961-5984)
-            const uint32_t clip5 = acc ? (h.strand == '+' ? recs.TL(i) : recs.TR(i)) : 0u, clip3 = acc ? (h.strand == '+' ? recs.TR(i) : recs.TL(i)) : 0u;
+            // the line as written (Aligner.cpp:5961-6033); a record that is not accepted has none: all 0
+            const bk::Line L = acc ? recs.line(i) : bk::Line{};
+            const bool two = L.gop != 0;
+            const uint32_t clip5 = L.c5, clip3 = L.c3, pos0 = L.pos, hit_len = L.m + L.m2;      // (hit_len: AdjAlignHitLen)
             const uint32_t n_cig = (two ? 3u : 1u) + (clip5 ? 1u : 0u) + (clip3 ? 1u : 0u);
-            const uint32_t pos0 = acc ? recs.a_start(h, i) : 0u;
-            const uint32_t hit_len = acc ? recs.a_len(h, i) + (two ? seg2[recs.RD(i)].match_len : 0u) : 0u;      // AdjAlignHitLen
             const uint32_t block = 32 + l_qn + 4 * n_cig + (len + 1) / 2 + len + aux;
             const size_t at = v.size();
             v.resize(at + 4 + block);
@@ -388,14 +376,11 @@ int report_bam(Report &R, const std::string &opath)
             w32((uint32_t)tlen);
             memcpy(q, qn, l_qn); q += l_qn;
             if (clip5) w32(clip5 << 4 | 4u);
-            w32((acc ? recs.a_len(h, i) : len) << 4);
+            w32((acc ? L.m : len) << 4);
             if (clip3) w32(clip3 << 4 | 4u);
             if (two) {
-                const bk_seg2 &g = seg2[recs.RD(i)];
-                if (g.flags & 4) w32((uint32_t)((long)g.match_loci - ((long)h.match_loci + h.match_len)) << 4 | 3u);
-                else if (g.flags & 2) w32((uint32_t)((long)len - ((long)h.match_len + g.match_len)) << 4 | 1u);
-                else { long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len); w32((uint32_t)(gap < 0 ? -gap : gap) << 4 | 2u); }
-                w32((uint32_t)g.match_len << 4);
+                w32((uint32_t)L.gap_written(len) << 4 | (L.gop == 'N' ? 3u : (L.gop == 'I' ? 1u : 2u)));
+                w32(L.m2 << 4);
             }
             uint8_t byte = 0;
             for (uint32_t o = 0; o < len; o++) {
@@ -574,19 +559,17 @@ int report_text(Report &R)
                 *w++ = '\t';
                 w = put_str(w, ents[h.chrom_id - 1].name);
                 *w++ = '\t';
-                w = put_num(w, (long)recs.a_start(h, i) + 1);
+                const bk::Line L = recs.line(i);                              // CAligner::ReportBAMread, Aligner.cpp:5960-6033
+                w = put_num(w, (long)L.pos + 1);
                 w = put_str(w, "\t255\t");
-                const uint32_t clip5 = h.strand == '+' ? recs.TL(i) : recs.TR(i), clip3 = h.strand == '+' ? recs.TR(i) : recs.TL(i);
-                if (clip5) { w = put_num(w, clip5); *w++ = 'S'; }
-                w = put_num(w, recs.a_len(h, i));
+                if (L.c5) { w = put_num(w, L.c5); *w++ = 'S'; }
+                w = put_num(w, L.m);
                 *w++ = 'M';
-                if (clip3) { w = put_num(w, clip3); *w++ = 'S'; }
-                if (recs.has_seg2(i)) {                                       // CAligner::ReportBAMread, Aligner.cpp:5986-6033
-                    const bk_seg2 &g = seg2[recs.RD(i)];
-                    if (g.flags & 4) { w = put_num(w, (long)g.match_loci - ((long)h.match_loci + h.match_len)); *w++ = 'N'; }
-                    else if (g.flags & 2) { w = put_num(w, (long)len - ((long)h.match_len + g.match_len)); *w++ = 'I'; }
-                    else { long gap = (long)g.match_loci - ((long)h.match_loci + h.match_len); w = put_num(w, gap < 0 ? -gap : gap); *w++ = 'D'; }
-                    w = put_num(w, g.match_len);
+                if (L.c3) { w = put_num(w, L.c3); *w++ = 'S'; }
+                if (L.gop) {
+                    w = put_num(w, L.gap_written(len));
+                    *w++ = L.gop;
+                    w = put_num(w, L.m2);
                     *w++ = 'M';
                 }
                 *w++ = '\t';
@@ -914,7 +897,7 @@ int report_text(Report &R)
                     if (fmt == 4) {
                         if (two) {
                             const bk_seg2 &g = seg2[recs.RD(i)];
-                            const bool sj = (g.flags & 4) != 0;
+                            const bool sj = bk::seg2_op(g) == 'N';
                             const uint32_t end1 = g.match_loci + g.match_len;          // AdjAlignEndLoci + 1
                             int m = snprintf(line, sizeof(line), "%s\t%u\t%u\t%s\t%d\t%c\t%u\t%u\t0\t2\t%u,%u\t0,%u\n", ents[h.chrom_id - 1].name, h.match_loci, end1,
                                              sj ? "arj" : "ari", R.score(h, i), (char)h.strand, h.match_loci, end1, (unsigned)h.match_len, (unsigned)g.match_len, g.match_loci - h.match_loci);
@@ -933,7 +916,7 @@ int report_text(Report &R)
                         const uint32_t s_loci = sg ? seg2[recs.RD(i)].match_loci : recs.a_start(h, i), s_len = sg ? seg2[recs.RD(i)].match_len : recs.a_len(h, i);
                         const uint32_t s_mm = sg ? seg2[recs.RD(i)].mismatches : recs.a_mm(h, i), s_rofs = sg ? seg2[recs.RD(i)].read_ofs : recs.TL(i);       // ReadOfs + TrimLeft
                         int m = snprintf(line, sizeof(line), "%u,\"%s\",\"%s\",\"%s\",%u,%u,%u,\"%c\",%d,0,1,%u,\"N/A\",\"%s\"", i + 1,
-                                         two ? ((seg2[recs.RD(i)].flags & 4) ? "arj" : "ari") : "ar", species.c_str(),
+                                         two ? (bk::seg2_op(seg2[recs.RD(i)]) == 'N' ? "arj" : "ari") : "ar", species.c_str(),
                                          ents[h.chrom_id - 1].name, s_loci, s_loci + s_len - 1, (unsigned)s_len, (char)h.strand, R.score(h, i), (unsigned)s_mm, rs.name(recs.RD(i)));
                         rec.assign(line, (size_t)m);
                         if (fmt >= 2) {                                          // the read as loaded, from the segment's read offset
