@@ -31,6 +31,7 @@
             return e__ == hipErrorOutOfMemory ? BK_ERR_MEM : BK_ERR_INTERNAL;                      \
         }                                                                                          \
     } while (0)
+#define BK_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)      // a step that returns a BK_ code: anything but BK_OK ends the caller with it
 
 namespace bk {
 // the engine's scratch: the device buffers the batch driver and the batch entry points grow on demand (capacities in elements: DevBuf::cap)
@@ -73,10 +74,15 @@ struct ImageBufs {
     DevBuf<uint32_t> grow_kx[kMoreKeys];  // BK_CTX_GROW_IMAGE: what the worker has made - its thread's alone until the batches' thread has
     DevBuf<uint8_t> grow_ktab2;           // .. joined it or acquire-loaded grow_state - and the batches' thread has not yet taken in
 };
+// The words of FixedBufs::small (zeroed by whoever is about to use one; bk_ctx::h_small mirrors them).  kSmCount: length of the list a pass
+// is making - reads with several loci, reads for the indel / chimeric search, PE orphans, SNP sites; kSmCursor: the wave-per-read kernel's
+// cursor over that list (launch_pe takes the two as neighbours); kSmReplayErr: reads whose loci replay disagreed with LowHitInstances;
+// kSmBestCursor: -N, launch_best's cursor; kSmMaxLen: longest read of a batch; kSmMinLenInv: ~(shortest read) (min_len_of reads it)
+enum SmallWord : uint32_t { kSmCount = 0, kSmCursor = 1, kSmReplayErr = 2, kSmBestCursor = 4, kSmMaxLen = 5, kSmMinLenInv = 6, kSmallWords = 16 };
 // the context's small device buffers of fixed size
 struct FixedBufs {
-    DevBuf<uint32_t> small;               // [0] act_cnt [1] next_cnt [2] heavy_cnt [3] cmax [4] cursor [5] maxlen [6] wave_cnt [7] wave cursor
-    DevBuf<PhaseCtl> ctl;                 // kMaxPhases + 2 lines: the counts of a chunk's phases (bk_device.h)
+    DevBuf<uint32_t> small;               // kSmallWords words, by SmallWord (3 and 7 .. 15: nobody's)
+    DevBuf<PhaseCtl> ctl;                 // kCtlLines lines: the counts of a chunk's phases and the batch's line (bk_device.h)
     DevBuf<unsigned long long> seq_counts, ctr, ctr_aux, snp_tot;
     DevBuf<unsigned long long> seq_global;        // bk_seq_counts_allreduce: the counts summed over every context of the run
     DevBuf<uint32_t> snp_planes;          // SNP pile-up: 6 count planes over the concatenated target
@@ -154,7 +160,8 @@ struct bk_ctx {
     }
     // what the batch scratch was sized for (scratch_bytes_per_read, maybe_build_swin)
     uint32_t cap_reads = 0, cap_wpr = 0, cap_iv_cores = 0;
-    bk::PinBuf<uint32_t> h_small;         // pinned mirror of fixed.small (two PhaseCtl lines when the phase loop reads its counts back)
+    bk::PinBuf<uint32_t> h_small;         // pinned mirror of fixed.small
+    bk::PinBuf<bk::PhaseCtl> h_line;      // pinned, two lines: a phase's counts and the next one's, where the phase loop reads them back
     bk::PinBuf<bk::PhaseCtl> h_ctl;       // pinned: the last chunk's counts (fixed.ctl), copied behind its kernels
     hipEvent_t ev_ctl = nullptr;
     bool ctl_pending = false, hist_valid = false;
@@ -190,7 +197,7 @@ struct bk_ctx {
     bool tables_built = false;            // k-mer table, second-level keys, inverse suffix array exist (made behind the suffix array's upload)
     bool tables_under_way = false;        // .. are being made (tables_begin .. tables_end): publish_index leaves their pointers null
     bk::PinBuf<char> sam_text[2];         // bk_sam_format's page-locked text buffers, kept for the next call (giving page-locked memory back costs 0.1 s per GB)
-    void release_pinned_buffers() { h_small.reset(); h_ctl.reset(); h_plan.reset(); sam_text[0].reset(); sam_text[1].reset(); }
+    void release_pinned_buffers() { h_small.reset(); h_line.reset(); h_ctl.reset(); h_plan.reset(); sam_text[0].reset(); sam_text[1].reset(); }
     uint32_t n_chrom_accept = 0;          // entries of buf.chrom_accept (bk_ctx_set_chrom_filter)
     bk_timing timing{};
     std::vector<hipEvent_t> ev_pool;

@@ -200,6 +200,14 @@ struct PhaseCtl {
 // the searching form of the fused read preparation (bk_prep.hip): phase 0's pass A inside it; its work items for pass B go through `stage` into `list`
 struct PrepSearch0 { const DevIndex *ix; int lazy; uint32_t *list, *list_cnt, *stage; };
 constexpr int kMaxPhases = 72;          // AlignReads runs at most MaxTotMM + 2 <= 65 LocateCoreMultiples calls (cMaxTotAllowedSubs 63)
+// A chunk's PhaseCtl lines: phases 0 .. kMaxPhases - 1, line kMaxPhases (what the last phase leaves for one that never runs), and the batch's own line, whose n_act holds the longest read of a batch only its caller has measured
+constexpr int kCtlBatchLine = kMaxPhases + 1, kCtlLines = kMaxPhases + 2;
+inline uint32_t *ctl_longest_read(PhaseCtl *ctl) { return &ctl[kCtlBatchLine].n_act; }
+// the work lists of a chunk's phase loop, as its launchers take them (host side: the kernels get the members they use)
+struct PhaseLists {
+    uint32_t *act_in, *act_out, *wave, *heavy;      // the phase's active list and the next phase's (swapped behind every phase); reads k_flat hands to the wave kernel, to the general kernel
+    uint32_t *slist, *slist_stage, *stage[3], *stripe_cnt;      // pass B's work list and its striped form; striped forms of the three lists k_flat fills, every stripe set's counters
+};
 
 struct HeavyScratch {
     unsigned long long *htab;   // slots * tab_size entries of (epoch<<32 | key)

@@ -7,7 +7,6 @@
 // here; a chunk's temporaries are local DevBufs, so an early return frees them.  Nothing here frees device memory by hand.
 #include "bk_engine_int.h"
 #include "bk_iv_slot.h"
-#include "bk_plan_table.h"
 #include "bk_wave_form.h"
 
 namespace bk {
@@ -167,8 +166,7 @@ static int stage_host_batch(bk_ctx *c, const uint8_t *bases, const uint64_t *off
     const uint64_t nbytes = x.hi - x.lo;
     BatchBufs &m = c->buf;
     HIP_TRY(m.in_bases.ensure(nbytes + 16));
-    int rc = ensure_in_reads(c, nreads, false);
-    if (rc) return rc;
+    BK_TRY(ensure_in_reads(c, nreads, false));
     HIP_TRY(hipMemcpyAsync(m.in_bases.get(), bases + x.lo, nbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(m.in_offs.get(), x.rel.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(m.in_lens.get(), lens, (size_t)nreads * 4, hipMemcpyHostToDevice, c->stream));
@@ -313,11 +311,9 @@ int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipS
 {
     bk_seg2 *d_seg2 = c->params.min_chimeric_len > 0 ? c->buf.seg2.get() : nullptr;       // there: every locus carries its end trims
     LociChunk lc{c, n, s};
-    int rc = lc.begin();
-    if (rc) return rc;
+    BK_TRY(lc.begin());
     launch_loci_count(b.out, n, c->params.clamp_ml ? c->cfg.max_hits : 0, lc.cnt.get(), s);
-    rc = lc.scan();
-    if (rc) return rc;
+    BK_TRY(lc.scan());
     uint32_t n_multi = 0;
     if (lc.total) {
         uint32_t *sm = c->fixed.small.get();
@@ -325,25 +321,23 @@ int collect_loci(bk_ctx *c, const DevBatch &b, uint32_t n, uint32_t maxlen, hipS
             HIP_TRY(lc.trims.ensure((size_t)lc.total));
             HIP_TRY(clear_dev(lc.trims.get(), (size_t)lc.total * sizeof(bk_loci_trims), s));
         }
-        HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
+        HIP_TRY(hipMemsetAsync(sm, 0, kSmallWords * 4, s));
         uint32_t *list = c->buf.act[0].get();          // the phase work lists are free by now
-        launch_loci_single(b.out, n, lc.offs.get(), lc.loci.get(), list, sm + 0, d_seg2, lc.trims.get(), s);
-        HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, 16 * 4, hipMemcpyDeviceToHost, s));
+        launch_loci_single(b.out, n, lc.offs.get(), lc.loci.get(), list, sm + kSmCount, d_seg2, lc.trims.get(), s);
+        HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, kSmallWords * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        n_multi = c->h_small.get()[0];
+        n_multi = c->h_small.get()[kSmCount];
         if (n_multi) {
-            rc = size_heavy_scratch(c);
-            if (rc) return rc;
-            launch_loci_enum(c->ix, c->cfg, b, c->hs, list, n_multi, sm + 1, lc.offs.get(), lc.loci.get(), sm + 2, d_seg2 ? c->params.min_chimeric_len : 0,
+            BK_TRY(size_heavy_scratch(c));
+            launch_loci_enum(c->ix, c->cfg, b, c->hs, list, n_multi, sm + kSmCursor, lc.offs.get(), lc.loci.get(), sm + kSmReplayErr, d_seg2 ? c->params.min_chimeric_len : 0,
                              maxlen > 512 ? 1 : 0, d_seg2, lc.trims.get(), s);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, 16 * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(c->h_small.get(), sm, kSmallWords * 4, hipMemcpyDeviceToHost, s));
         }
     }
-    rc = lc.finish();
-    if (rc) return rc;
-    if (n_multi && c->h_small.get()[2] != 0) {               // a replay that did not reproduce LowHitInstances: never ignore
-        fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small.get()[2]);
+    BK_TRY(lc.finish());
+    if (n_multi && c->h_small.get()[kSmReplayErr] != 0) {               // a replay that did not reproduce LowHitInstances: never ignore
+        fprintf(stderr, "bk: loci replay disagreed with LowHitInstances for %u reads\n", c->h_small.get()[kSmReplayErr]);
         return BK_ERR_INTERNAL;
     }
     return BK_OK;
@@ -356,17 +350,14 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
     const uint32_t width = (uint32_t)c->cfg.max_hits;
     DevBuf<bk_loci> dense;
     LociChunk lc{c, n, s};
-    int rc = lc.begin();
-    if (rc) return rc;
+    BK_TRY(lc.begin());
     HIP_TRY(dense.ensure((size_t)n * width));
-    rc = size_heavy_scratch(c);
-    if (rc) return rc;
+    BK_TRY(size_heavy_scratch(c));
     uint32_t *sm = c->fixed.small.get();
-    HIP_TRY(hipMemsetAsync(sm + 4, 0, 4, s));
-    launch_best(c->ix, c->cfg, b, c->hs, d_list, n_list, sm + 4, lc.cnt.get(), dense.get(), s);
+    HIP_TRY(hipMemsetAsync(sm + kSmBestCursor, 0, 4, s));
+    launch_best(c->ix, c->cfg, b, c->hs, d_list, n_list, sm + kSmBestCursor, lc.cnt.get(), dense.get(), s);
     HIP_TRY(hipGetLastError());
-    rc = lc.scan();
-    if (rc) return rc;
+    BK_TRY(lc.scan());
     if (lc.total) {
         launch_loci_compact(dense.get(), width, lc.offs.get(), n, lc.loci.get(), s);
         HIP_TRY(hipGetLastError());
@@ -374,285 +365,239 @@ int best_matches_chunk(bk_ctx *c, const DevBatch &b, uint32_t n, const uint32_t 
     return lc.finish();
 }
 
-// minlen: the shortest read of the call when somebody has looked (0: not known) - with maxlen it tells whether every read has the same
-// number of 16-base dwords, which the wave kernel's length-specialised forms rely on
-int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, uint32_t minlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
+// ---- one chunk of reads, all phases ---------------------------------------------------------------------------------------
+// The phases' counts stay in device memory (PhaseCtl).  The main path launches the whole schedule from bounds and reads nothing back;
+// the other configurations read the counts back, which sizes their launches exactly.  phase_counts alone knows which of the two runs.
+// PhaseCounts: a phase's counts as the host uses them - read back, or the bounds that stand in for them - and how much of a list a sort takes
+struct PhaseCounts { uint32_t n_act = 0; int cmax = 0; uint64_t n_slist = 0; uint32_t n_wave = 0, n_heavy = 0, sort_slist = 0, sort_wave = 0; };
+enum class Behind { Prep, PassA, Extend, Wave };
+
+// batch scratch; the window array is a luxury: it goes before a batch is refused for want of memory
+static int batch_scratch_or_release_swin(bk_ctx *c, uint32_t n_reads, uint32_t wpr, uint32_t rd2w, uint32_t ivc)
 {
-    uint32_t *sm = c->fixed.small.get(), *hm = c->h_small.get();
-    HIP_TRY(hipMemsetAsync(sm, 0, 16 * 4, s));
-    const uint32_t wpr = words_per_read(maxlen);
-    // register-resident window kernels handle reads of <= 128 / <= 256 / <= 16 * kNwLong / <= 16 * kNwLongest bases
-    const bool reg_path = c->use_wave && maxlen <= 16u * (uint32_t)kNwLongest;
-    const int nw16 = maxlen <= 128 ? 8 : (maxlen <= 256 ? 16 : (maxlen <= 16u * (uint32_t)kNwLong ? kNwLong : kNwLongest));
-    const bool two_bit = reg_path && c->ix.tgt2 != nullptr;
-    const uint32_t ivc = iv_cores_for(c, maxlen);
-    int rc = ensure_batch_scratch(c, n, wpr, two_bit ? (uint32_t)(nw16 / 2) : 0u, ivc);
-    if (rc && c->image.swin.get()) {                        // the window array is a luxury: it goes before a batch is refused for want of memory
-        (void)hipGetLastError();
-        bk::release_swin(c);
-        rc = ensure_batch_scratch(c, n, wpr, two_bit ? (uint32_t)(nw16 / 2) : 0u, ivc);
-    }
-    if (rc) return rc;
+    const int rc = ensure_batch_scratch(c, n_reads, wpr, rd2w, ivc);
+    if (!rc || !c->image.swin.get()) return rc;
+    (void)hipGetLastError();
+    bk::release_swin(c);
+    return ensure_batch_scratch(c, n_reads, wpr, rd2w, ivc);
+}
 
-    BatchBufs &m = c->buf;
-    uint32_t *const d_act[2] = {m.act[0].get(), m.act[1].get()}, *const d_heavy = m.heavy.get(), *const d_wave = m.wave.get();
-    uint32_t *const d_stage[3] = {m.stage[0].get(), m.stage[1].get(), m.stage[2].get()}, *const d_stripe_cnt = m.stripe_cnt.get();
-    DevBatch b = make_batch(c, in, first, n, wpr, ivc, d_out);
-    b.rd2 = two_bit ? m.rd2.get() : nullptr;
-    // (the wave list's job sizes come from k_flat only when every read on that list went through it)
-    b.wave_work = (reg_path && c->cfg.heavy_thresh <= 100) ? m.wave_work.get() : nullptr;
-    b.iv32 = (c->use_iv32 && c->ix.k2) ? m.iv32.get() : nullptr;      // (written by k_search_a_ilp and pass B in phase 0)
-    b.nw = reg_path ? (uint32_t)nw16 : 0u;       // the fused prep kernel packs reads of the register-kernel path
-    const int nstr = c->cfg.align_strand == 0 ? 2 : 1;
-
-    // ---- the phase loop ---------------------------------------------------------------------------------------------------------
-    // Every count the phases produce (active reads, pass B's work items, reads for the wave kernel) stays in device memory (PhaseCtl,
-    // one line per phase) and the kernels size themselves by it.  On the main path - register-window kernels, k_flat, second-level
-    // keys - the host therefore launches the whole schedule without reading anything back: grids come from bounds it knows (an active
-    // list is never longer than the chunk; a read of up to maxlen bases has at most so many cores and phases), the two work-list sorts
-    // are sized from what the previous chunk needed (items beyond that run unsorted: order never changes a result).  The other
-    // configurations (general kernel family, lane-per-read kernels, no key array, -N, BK_DEBUG) keep reading the counts back, which
-    // sizes their launches exactly.
-    PhaseCtl *ctl = c->fixed.ctl.get();
-    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PhaseCtl) * (kMaxPhases + 2), s));
-    auto P = [&](int ph) { return reinterpret_cast<uint32_t *>(ctl + ph); };      // words of ctl[ph]: [0] n_act [1] cmax [2] n_slist [3] n_wave [4] n_heavy [5] wave cursor [6] heavy cursor [7] n_deep
-    // bounds of a read of up to maxlen bases: phases, cores per strand in each
-    int max_phases = 0, cmax_bound[kMaxPhases + 1] = {0};
-    bool cores_fit = true;
-    // (from the plan table, which holds make_plan / phase_params / core_offsets of every length and phase and is kept between batches)
-    { int rp = plan_table_for(c, maxlen, s); if (rp) return rp; }
-    b.plan = c->buf.plan.get();
-    b.plan_stride = c->plan_maxlen + 1;
-    b.plan_n = maxlen + 1;
-    for (uint32_t len = 1; len <= maxlen; len++) {
-        const int n_phases = plan_unpack(c->h_plan.get()[len]).n_phases;
-        max_phases = std::max(max_phases, n_phases);
-        for (int ph = 0; ph < n_phases && ph <= kMaxPhases; ph++) {
-            const int nc = plan_unpack(c->h_plan.get()[(size_t)ph * b.plan_stride + len]).nc;
-            if (nc > kMaxCoresFast) cores_fit = false;
-            cmax_bound[ph] = std::max(cmax_bound[ph], std::min(nc, (int)kMaxCoresFast));
-        }
-    }
-    if (max_phases > kMaxPhases) return BK_ERR_INTERNAL;
-    const bool no_readback = reg_path && c->cfg.heavy_thresh <= 100 && c->ix.k2 != nullptr && cores_fit && !c->params.best_matches &&
-                             !c->debug && c->async_phases;
-    const bool check_maxlen = !tm.on;                 // (a call that only enqueues: its caller named the longest read, nobody has looked)
-    if (check_maxlen) launch_max_len(b.lens, n, P(kMaxPhases + 1) + 0, s);
-    b.iv_stride = n;                               // interval records: a plane per (strand, core), a record per read of the chunk in each
-    // "prep_search0": the fused read preparation also runs phase 0's pass A - one core per strand pass, probed from the bases its lanes
-    // hold - and leaves pass B's work list; that phase's records then go by read number (DevBatch::iv_by_read)
-    const bool search0 = bk::prep_search0_on(c, reg_path, cores_fit, cmax_bound[0]);
-    const int lazy0 = (reg_path && c->lazy_search) ? 1 : 0;
-    PrepSearch0 ps0{&c->ix, lazy0, nullptr, P(0) + 2, nullptr};
-    if (search0) {
-        { int rs = ensure_slist(c, (uint64_t)n * (uint64_t)nstr, s); if (rs) return rs; }
-        ps0.list = m.slist.get();
-        ps0.stage = m.slist_stage.get();
-        b.iv_by_read = 1;
-        if (c->iv_poison) launch_clear_iv(b, nullptr, n, 1, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
-    }
-    hipEvent_t e0 = tm.begin(s);
-    launch_prep(c->cfg, b, d_act[0], P(0) + 0, P(0) + 1, d_stage[0], d_stripe_cnt, s, search0 ? &ps0 : nullptr);
-    HIP_TRY(hipGetLastError());
-    tm.end(Span::Prep, e0, s);
-    uint32_t n_act = n;
-    int cmax = cmax_bound[0];
-    auto read_ctl = [&](int ph) -> int {           // ctl[ph], ctl[ph + 1] -> hm[0..31]
-        HIP_TRY(hipMemcpyAsync(hm, ctl + ph, 2 * sizeof(PhaseCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+struct ChunkRun {                       // what a chunk's run works over: made by chunk_setup, handed from stage to stage
+    bk_ctx *c;
+    hipStream_t s;
+    EvTimer &tm;                        // (off: a call that only enqueues - its caller named the longest read, nobody has looked)
+    uint32_t n, maxlen, minlen;         // reads of the chunk; longest and shortest read of the call (minlen 0: nobody has looked)
+    DevBatch b{}; PhaseLists l{};
+    ChunkBounds cb{};                   // phases and cores a read of up to maxlen bases can have
+    PhaseCtl *ctl = nullptr;            // fixed.ctl: the chunk's lines of counts
+    int act_cur = 0, nw16 = 0, nstr = 1, lazy = 0;      // l.act_in is buf.act[act_cur]; window words of the kernel family (0: not the register-window path), strand passes, lazy search
+    bool reg_path = false, search0 = false, no_readback = false;
+    // scratch, the batch, the plan table and the bounds it gives, which schedule runs and whether the preparation searches phase 0
+    int chunk_setup(const DevReads &in, uint32_t first, bk_hit *d_out)
+    {
+        const uint32_t wpr = words_per_read(maxlen), rd2w = rd2_words(c, maxlen), ivc = iv_cores_for(c, maxlen);
+        nw16 = c->use_wave ? window_words_for(maxlen) : 0, reg_path = nw16 != 0;
+        BK_TRY(batch_scratch_or_release_swin(c, n, wpr, rd2w, ivc));
+        BatchBufs &m = c->buf;
+        l = PhaseLists{m.act[0].get(), m.act[1].get(), m.wave.get(), m.heavy.get(), nullptr, nullptr, {m.stage[0].get(), m.stage[1].get(), m.stage[2].get()}, m.stripe_cnt.get()};
+        b = make_batch(c, in, first, n, wpr, ivc, d_out);
+        b.rd2 = rd2w ? m.rd2.get() : nullptr;
+        // (the wave list's job sizes come from k_flat only when every read on that list went through it)
+        b.wave_work = (reg_path && c->cfg.heavy_thresh <= 100) ? m.wave_work.get() : nullptr;
+        b.iv32 = (c->use_iv32 && c->ix.k2) ? m.iv32.get() : nullptr;      // (written by k_search_a_ilp and pass B in phase 0)
+        b.nw = (uint32_t)nw16;                   // the fused prep kernel packs reads of the register-kernel path
+        b.iv_stride = n;                         // interval records: a plane per (strand, core), a record per read of the chunk in each
+        nstr = c->cfg.align_strand == 0 ? 2 : 1, lazy = (reg_path && c->lazy_search) ? 1 : 0;
+        ctl = c->fixed.ctl.get();
+        HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PhaseCtl) * kCtlLines, s));
+        BK_TRY(plan_table_for(c, maxlen, s));    // (make_plan / phase_params / core_offsets of every length and phase, kept between batches)
+        b.plan = m.plan.get(), b.plan_stride = c->plan_maxlen + 1, b.plan_n = maxlen + 1;
+        cb = chunk_bounds(c->h_plan.get(), b.plan_stride, maxlen);
+        if (cb.max_phases > kMaxPhases) return BK_ERR_INTERNAL;
+        no_readback = reg_path && main_path_common(c->use_wave != 0, c->cfg.heavy_thresh, c->ix.k2 != nullptr, c->debug, c->async_phases != 0) &&
+                        cb.cores_fit && !c->params.best_matches;
+        search0 = bk::prep_search0_on(c, reg_path, cb.cores_fit, cb.cmax_bound[0]);
         return BK_OK;
-    };
-    if (!no_readback) {
-        int rr = read_ctl(0);
-        if (rr) return rr;
-        n_act = hm[0];
-        cmax = (int)hm[1];
     }
-    int cur = 0;
-    if (c->params.best_matches) {
-        hipEvent_t eb = tm.begin(s);
-        int rb = best_matches_chunk(c, b, n, d_act[0], n_act, s);
-        if (rb) return rb;
-        tm.end(Span::Heavy, eb, s);
-        n_act = 0;
+    // pass B's work list for `lanes` items (growing it moves it), then - "iv_poison" - ones into the interval slots the phase of line
+    // `cur` can use, so that a slot read without having been written shows (cur null: slots by read; skip: pass A has filled them)
+    int slist_and_poison(uint64_t lanes, const PhaseCtl *cur, uint32_t n_bound, int cmax, bool skip)
+    {
+        const int rc = ensure_slist(c, lanes, s), as = c->cfg.align_strand;
+        l.slist = c->buf.slist.get(), l.slist_stage = c->buf.slist_stage.get();
+        if (!rc && !skip && c->iv_poison) launch_clear_iv(b, cur, n_bound, cmax, as == 2 ? 1 : 0, as == 1 ? 0 : 1, 0xFFFFFFFFu, s);
+        return rc;
     }
-    if (no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe of the wave kernel
-    for (int phase = 0; no_readback ? phase < max_phases : n_act > 0; phase++) {
-        const uint32_t *ext_list = d_act[cur];
-        b.act = ext_list;
-        const bool searched = search0 && phase == 0;       // pass A of this phase ran inside the read preparation
-        b.iv_by_read = searched ? 1u : 0u;                 // (every later phase: by position in its active list)
-        if (no_readback) cmax = cmax_bound[phase];
-        const uint32_t n_bound = n_act;            // (no read-back: the chunk's size; else the list's length)
-        uint32_t *ctl_p = P(phase), *ctl_n = P(phase + 1);
-        const int lazy = (reg_path && c->lazy_search) ? 1 : 0;
-        if (cmax > 0) {
-            hipEvent_t e1 = tm.begin(s);
-            if (c->ix.k2) {
-                const uint64_t lanes = (uint64_t)n_bound * (uint64_t)(cmax * nstr);
-                { int rs = ensure_slist(c, lanes, s); if (rs) return rs; }
-                uint32_t *const d_slist = m.slist.get();
-                // (no clearing of the interval records: pass A stores the slot of every core a read has, empty results included, or hands
-                // it to pass B, which stores it on every path; the consumers never look at a core the read does not have.  "iv_poison"
-                // puts ones into the slots this phase can use, so that a slot read without having been written shows.)
-                if (!searched) {
-                    if (c->iv_poison) launch_clear_iv(b, ctl_p + 0, n_bound, cmax, c->cfg.align_strand == 2 ? 1 : 0, c->cfg.align_strand == 1 ? 0 : 1, 0xFFFFFFFFu, s);
-                    hipEvent_t ea = tm.begin(s);
-                    launch_search_a(c->ix, c->cfg, b, d_act[cur], ctl_p + 0, n_bound, phase, cmax, nstr, lazy, d_slist, ctl_p + 2,
-                                    m.slist_stage.get(), d_stripe_cnt, s);
-                    HIP_TRY(hipGetLastError());
-                    tm.end(Span::SearchA, ea, s);
-                }
-                // pass B's work list, grouped by k-mer bucket: the sort's size is the list's length when that was read back, else what
-                // the previous chunk's phase needed (plus a margin; capped at the sort buffers)
-                uint64_t n_slist_bound = lanes;
-                uint32_t n_sort = 0;
-                if (!no_readback) {
-                    HIP_TRY(hipMemcpyAsync(hm + 2, ctl_p + 2, 4, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    n_slist_bound = hm[2];
-                    n_sort = hm[2];
-                } else {
-                    const double f = c->hist_valid ? c->hist_slist[phase] * 1.05 : 0.30;
-                    n_sort = (uint32_t)std::min<uint64_t>({(uint64_t)(f * n) + 4096, lanes, (uint64_t)0x7FFFFFF0});
-                }
-                if (no_readback && m.sort[2].cap() >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, m.sort[2].cap());      // (no growing - it waits for the stream - for a guess)
-                const uint32_t *sorted = nullptr;
-                if ((c->sort_lists & 1) && n_sort >= 4096) {
-                    int rs = ensure_sort_scratch(c, n_sort, s);
-                    if (rs) return rs;
-                    hipEvent_t es = tm.begin(s);
-                    launch_keys_search(b, d_slist, ctl_p + 2, n_sort, c->sort_shift, m.sort[0].get(), s);
-                    rs = sort_work(c, d_slist, n_sort, s, &sorted);
-                    if (rs) return rs;
-                    tm.end(Span::SearchSort, es, s);
-                } else
-                    n_sort = 0;
-                if (n_slist_bound) {
-                    hipEvent_t eb = tm.begin(s);
-                    // "search_split": the items the key levels do not settle are finished by a second, dense launch.  Their list takes
-                    // pass A's place - the work list and its stripes are free once k_search_b has read them - and its length a spare
-                    // word of the phase's line, zero since the chunk began; both launches are pass B's time
-                    const bool split = bk::search_split_on(c);
-                    launch_search_b(c->ix, c->cfg, b, phase, lazy, d_slist, sorted, n_sort, ctl_p + 2, n_slist_bound, split ? d_slist : nullptr,
-                                    split ? ctl_p + 7 : nullptr, m.slist_stage.get(), d_stripe_cnt, s);
-                    tm.end(Span::SearchB, eb, s);
-                }
-            } else
-                launch_search(c->ix, c->cfg, b, d_act[cur], n_act, phase, cmax, nstr, lazy, s);
-            HIP_TRY(hipGetLastError());
-            tm.end(Span::Search, e1, s);
+    // the read preparation: rows, the first active list and its counts in ctl[0] - and phase 0's pass A where search0 says so
+    int prepare_reads()
+    {
+        if (!tm.on) launch_max_len(b.lens, n, ctl_longest_read(ctl), s);
+        b.iv_by_read = search0 ? 1u : 0u;
+        if (search0) BK_TRY(slist_and_poison((uint64_t)n * (uint64_t)nstr, nullptr, n, 1, false));
+        const PrepSearch0 ps0{&c->ix, lazy, l.slist, &ctl[0].n_slist, l.slist_stage};
+        hipEvent_t e0 = tm.begin(s);
+        launch_prep(c->cfg, b, l.act_in, &ctl[0].n_act, &ctl[0].cmax, l.stage[0], l.stripe_cnt, s, search0 ? &ps0 : nullptr);
+        HIP_TRY(hipGetLastError());
+        tm.end(Span::Prep, e0, s);
+        return BK_OK;
+    }
+    // The counts of `phase` the host goes on with: behind the preparation (n_act, cmax of phase 0), behind pass A (n_slist), behind the
+    // extension (n_wave, n_heavy), behind the wave and general kernels (n_act, cmax of the NEXT phase).  Without read-backs: the bounds of
+    // the chunk's size and the plan table, sort_prefix's guess for a sort; else the lines read back (h_line), a sort takes the whole list.
+    int phase_counts(int phase, Behind at, PhaseCounts &k)
+    {
+        if (no_readback) {
+            if (at == Behind::Prep && c->ix.isa == nullptr) BK_TRY(size_heavy_scratch(c));      // the wave kernel's hash-set dedupe, sized before the schedule starts: nothing allocates or waits in the middle of it
+            k.n_act = k.n_wave = n;                                // (any read of the chunk may still be active, and may go to the wave kernel)
+            k.n_heavy = 0;                                           // (the core bound rules the general kernel out: take_phase_history checks)
+            k.cmax = cb.cmax_bound[at == Behind::Wave ? phase + 1 : phase];
+            k.n_slist = (uint64_t)n * (uint64_t)(k.cmax * nstr);
+            const uint64_t cap = c->buf.sort[2].cap();               // (no growing - it waits for the stream - for a guess)
+            if (at == Behind::PassA) k.sort_slist = sort_prefix(c->hist_valid, c->hist_slist[phase], 0.30, n, k.n_slist, cap, kSortCeiling);
+            if (at == Behind::Extend) k.sort_wave = sort_prefix(c->hist_valid, c->hist_wave[phase], 0.25, n, k.n_wave, cap, kNoCeiling);
+            return BK_OK;
         }
-        if (phase == c->dbg_stop_phase) {
-            // (test hook, bk_debug_intervals: the interval records the search of this phase wrote stay where they are; nothing of the
-            // phase's extension or of the phases behind it runs, so the batch's result records are not to be used)
-            c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = phase; c->dbg_by_read = searched; c->dbg_valid = true;
-            break;
+        PhaseCtl *h = c->h_line.get();                               // h[0]: this phase, h[1]: the next
+        if (at == Behind::PassA) {
+            HIP_TRY(hipMemcpyAsync(&h[0].n_slist, &ctl[phase].n_slist, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            k.n_slist = h[0].n_slist;
+            k.sort_slist = h[0].n_slist >= 4096 ? h[0].n_slist : 0;
+            return BK_OK;
         }
-        hipEvent_t e2 = tm.begin(s);
-        // 5-byte indexes: the reference's seen-target set is keyed by the target start truncated to 32 bits (SfxArrayV2.cpp:5932), a
-        // rule that depends on every earlier candidate of the strand pass.  k_flat and the hash-set kernels reproduce it; the
-        // lane-per-read kernels dedupe on exact starts, so on an index of more than 2^32 bases they only finish the calls without candidates and hand
-        // every other one to the hash-set kernels.
+        if (at != Behind::Wave || k.n_wave || k.n_heavy) {           // (behind kernels that did not run the lines are as the extension left them)
+            HIP_TRY(hipMemcpyAsync(h, ctl + phase, 2 * sizeof(PhaseCtl), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (at == Behind::Extend) {
+            k.n_heavy = h[0].n_heavy, k.n_wave = h[0].n_wave;
+            k.sort_wave = k.n_wave >= 4096 ? k.n_wave : 0;
+            return BK_OK;
+        }
+        if (at == Behind::Wave && c->debug)
+            fprintf(stderr, "bk: phase %d n_act %u cmax %d n_heavy %u n_wave %u -> next n_act %u cmax %u\n", phase, k.n_act, k.cmax, k.n_heavy, k.n_wave, h[1].n_act, h[1].cmax);
+        k.n_act = h[at == Behind::Wave].n_act, k.cmax = (int)h[at == Behind::Wave].cmax;
+        return BK_OK;
+    }
+    // The search of a phase - LocateFirstExact / LocateLastExact of every core of every active read, into the interval records.  With
+    // second-level keys: pass A (unless the preparation ran it), pass B's work list grouped by k-mer bucket, pass B; else one kernel.
+    int search_phase(int phase, PhaseCounts &k)
+    {
+        PhaseCtl *cur = ctl + phase;
+        if (k.cmax <= 0) return BK_OK;
+        hipEvent_t e1 = tm.begin(s);
+        if (c->ix.k2) {
+            // (the interval records are not cleared: launch_clear_iv, bk_search.hip)
+            BK_TRY(slist_and_poison((uint64_t)k.n_act * (uint64_t)(k.cmax * nstr), cur, k.n_act, k.cmax, b.iv_by_read != 0));
+            if (!b.iv_by_read) {                     // (by read: pass A of this phase ran inside the read preparation)
+                hipEvent_t ea = tm.begin(s);
+                launch_search_a(c->ix, c->cfg, b, l, cur, k.n_act, phase, k.cmax, nstr, lazy, s);
+                HIP_TRY(hipGetLastError());
+                tm.end(Span::SearchA, ea, s);
+            }
+            BK_TRY(phase_counts(phase, Behind::PassA, k));
+            const uint32_t *sorted = nullptr;
+            const uint32_t n_sort = (c->sort_lists & 1) ? k.sort_slist : 0;
+            if (n_sort) {
+                BK_TRY(ensure_sort_scratch(c, n_sort, s));
+                hipEvent_t es = tm.begin(s);
+                launch_keys_search(b, l, cur, n_sort, c->sort_shift, c->buf.sort[0].get(), s);
+                BK_TRY(sort_work(c, l.slist, n_sort, s, &sorted));
+                tm.end(Span::SearchSort, es, s);
+            }
+            if (k.n_slist) {
+                // ("search_split": a second, dense launch finishes the items the key levels do not settle - launch_search_b; both are pass B's time)
+                hipEvent_t eb = tm.begin(s);
+                launch_search_b(c->ix, c->cfg, b, l, cur, phase, lazy, sorted, n_sort, k.n_slist, bk::search_split_on(c), s);
+                tm.end(Span::SearchB, eb, s);
+            }
+        } else
+            launch_search(c->ix, c->cfg, b, l.act_in, k.n_act, phase, k.cmax, nstr, lazy, s);
+        HIP_TRY(hipGetLastError());
+        tm.end(Span::Search, e1, s);
+        return BK_OK;
+    }
+    // The extension of a phase: k_flat on the register-window path, else the lane-per-read kernel.  5-byte indexes: the reference's seen-target set is keyed by the target start truncated to 32 bits (SfxArrayV2.cpp:5932), a rule that
+    // depends on every earlier candidate of the strand pass.  k_flat and the hash-set kernels reproduce it; the lane-per-read kernels
+    // dedupe on exact starts, so on an index of more than 2^32 bases they only finish the calls without candidates and hand every other
+    // one to the hash-set kernels.
+    int extend_phase(int phase, const PhaseCounts &k)
+    {
+        PhaseCtl *cur = ctl + phase;
         DevAlignCfg cfg_lane = c->cfg;
         if (c->ix.n > (1ULL << 32)) cfg_lane.heavy_thresh = 0;            // (below that the truncated keys are the exact ones)
-        if (n_bound == 0) {}
+        hipEvent_t e2 = tm.begin(s);
+        if (k.n_act == 0) {}
         else if (reg_path && c->cfg.heavy_thresh <= 100)
-            launch_flat(c->ix, c->cfg, b, ext_list, ctl_p + 0, n_bound, phase, nstr * std::max(cmax, 1), d_act[cur ^ 1], ctl_n + 0, d_heavy, ctl_p + 4,
-                        d_wave, ctl_p + 3, ctl_n + 1, d_stage, d_stripe_cnt, nw16, s);
+            launch_flat(c->ix, c->cfg, b, l, cur, cur + 1, k.n_act, phase, nstr * std::max(k.cmax, 1), nw16, s);
         else
-            launch_extend(c->ix, cfg_lane, b, ext_list, n_act, phase, d_act[cur ^ 1], ctl_n + 0, d_heavy, ctl_p + 4, ctl_n + 1, s);
+            launch_extend(c->ix, cfg_lane, b, l, cur, cur + 1, k.n_act, phase, s);
         HIP_TRY(hipGetLastError());
         tm.end(Span::Extend, e2, s);
-        uint32_t n_heavy = 0, n_wave = n_bound;    // (no read-back: any read of the list may have gone to the wave kernel)
-        if (!no_readback) {
-            int rr = read_ctl(phase);
-            if (rr) return rr;
-            n_heavy = hm[4];
-            n_wave = hm[3];
-        }
-        if (n_wave) {
+        return BK_OK;
+    }
+    // the reads the extension handed on: the wave kernel over its list (sorted by index position or job size where that pays), the general kernel over its own
+    int wave_phase(int phase, const PhaseCounts &k)
+    {
+        PhaseCtl *cur = ctl + phase;
+        if (k.n_wave) {
             hipEvent_t e3 = tm.begin(s);
             const uint32_t *wsorted = nullptr;
-            uint32_t n_sort = n_wave;
-            if (no_readback) {
-                const double f = c->hist_valid ? c->hist_wave[phase] * 1.05 : 0.25;
-                n_sort = (uint32_t)std::min<uint64_t>((uint64_t)(f * n) + 4096, n_wave);
-                if (m.sort[2].cap() >= 4096) n_sort = (uint32_t)std::min<uint64_t>(n_sort, m.sort[2].cap());
+            const uint32_t n_sort = (c->sort_lists & 2) ? k.sort_wave : 0;
+            if (n_sort) {
+                BK_TRY(ensure_sort_scratch(c, n_sort, s));
+                launch_keys_wave(c->cfg, b, phase, l, cur, n_sort, (c->sort_lists & 4) ? -1 : c->sort_shift, c->buf.sort[0].get(), b.wave_work, s);
+                BK_TRY(sort_work(c, l.wave, n_sort, s, &wsorted));
             }
-            if ((c->sort_lists & 2) && n_sort >= 4096) {
-                int rs = ensure_sort_scratch(c, n_sort, s);
-                if (rs) return rs;
-                launch_keys_wave(c->cfg, b, phase, d_wave, ctl_p + 3, n_sort, (c->sort_lists & 4) ? -1 : c->sort_shift, m.sort[0].get(), b.wave_work, s);
-                rs = sort_work(c, d_wave, n_sort, s, &wsorted);
-                if (rs) return rs;
-            } else
-                n_sort = 0;
-            if (!no_readback && c->ix.isa == nullptr) { int rh = size_heavy_scratch(c); if (rh) return rh; }      // hash-set dedupe
-            launch_wave(c->ix, c->cfg, b, c->hs, d_wave, wsorted, n_sort, ctl_p + 3, n_wave, phase, ctl_p + 5, d_act[cur ^ 1], ctl_n + 0, ctl_n + 1,
-                        nw16, c->wave_waves, c->wave_len_spec ? uniform_dwords(minlen, maxlen) : 0, s);
+            if (c->ix.isa == nullptr) BK_TRY(size_heavy_scratch(c));      // hash-set dedupe (where no count is read back: sized already, nothing to do)
+            launch_wave(c->ix, c->cfg, b, c->hs, l, cur, cur + 1, wsorted, n_sort, k.n_wave, phase, nw16, c->wave_waves,
+                        c->wave_len_spec ? uniform_dwords(minlen, maxlen) : 0, s);
             HIP_TRY(hipGetLastError());
             tm.end(Span::Heavy, e3, s);
         }
-        if (n_heavy) {
+        if (k.n_heavy) {
             hipEvent_t e3 = tm.begin(s);
-            { int rh = size_heavy_scratch(c); if (rh) return rh; }
-            launch_heavy(c->ix, c->cfg, b, c->hs, d_heavy, n_heavy, phase, ctl_p + 6, d_act[cur ^ 1], ctl_n + 0, ctl_n + 1, s);
+            BK_TRY(size_heavy_scratch(c));
+            launch_heavy(c->ix, c->cfg, b, c->hs, l, cur, cur + 1, k.n_heavy, phase, s);
             HIP_TRY(hipGetLastError());
             tm.end(Span::Heavy, e3, s);
         }
-        if (!no_readback) {
-            if (n_wave || n_heavy) { int rr = read_ctl(phase); if (rr) return rr; }
-            if (c->debug)
-                fprintf(stderr, "bk: phase %d n_act %u cmax %d n_heavy %u n_wave %u -> next n_act %u cmax %u\n", phase, n_act, cmax, n_heavy, n_wave, hm[16], hm[17]);
-            n_act = hm[16];                        // ctl[phase + 1].n_act, .cmax
-            cmax = (int)hm[17];
-        }
-        cur ^= 1;
-        if (phase > 70) return BK_ERR_INTERNAL;
+        return BK_OK;
     }
-    if (c->dbg_stop_phase >= 0 && !c->dbg_valid) {       // (no read reached that phase: an empty list - ctl[kMaxPhases] is never written)
-        c->dbg_n = n; c->dbg_ivc = ivc; c->dbg_cur = cur; c->dbg_phase = kMaxPhases; c->dbg_by_read = false; c->dbg_valid = true;
+    // test hook, bk_debug_intervals: the interval records the search of `phase` wrote stay where they are; nothing of the phase's extension
+    // or of the phases behind it runs, so the batch's result records are not to be used
+    void debug_stop(int phase, bool by_read)
+    {
+        c->dbg_n = n; c->dbg_ivc = b.iv_cores; c->dbg_cur = act_cur; c->dbg_phase = phase; c->dbg_by_read = by_read; c->dbg_valid = true;
     }
-    if (no_readback) {
-        // what the phases needed goes to the host on its own time: it sizes the next chunk's sorts (and says whether a read was handed to the
-        // general kernel, which this schedule never launches: the core bound above rules it out)
-        HIP_TRY(hipMemcpyAsync(c->h_ctl.get(), ctl, sizeof(PhaseCtl) * (kMaxPhases + 2), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(c->ev_ctl, s));
-        c->ctl_pending = true;
-        c->ctl_pending_reads = n;
-        c->ctl_pending_phases = max_phases;
-        c->ctl_pending_maxlen = check_maxlen ? maxlen : 0;
-    }
-    if (c->params.micro_indel_len > 0 || c->params.splice_junct_len > 0 || c->params.min_chimeric_len > 0) {
-        // AlignReads' branches for what is still unaligned (SfxArrayV2.cpp:7722-7757): microInDels, then splice junctions, then the
-        // chimeric (end-trimmed) placement
+    // AlignReads' branches for what is still unaligned (SfxArrayV2.cpp:7722-7757): microInDels, then splice junctions, then the chimeric
+    // (end-trimmed) placement; the chunk's second segments appended to the context's
+    int second_segments()
+    {
+        const bk_align_params &p = c->params;
+        uint32_t *sm = c->fixed.small.get(), *hm = c->h_small.get(), *list = c->buf.act[0].get();      // (the phase work lists are free by now)
         hipEvent_t ei = tm.begin(s);
-        { int r2 = ensure_seg2(c, n); if (r2) return r2; }
-        bk_seg2 *d_seg2 = m.seg2.get();
+        BK_TRY(ensure_seg2(c, n));
+        bk_seg2 *d_seg2 = c->buf.seg2.get();
         hipError_t eh = clear_dev(d_seg2, (size_t)n * sizeof(bk_seg2), s);
         int rc2 = BK_OK;
-        if (eh == hipSuccess && (c->params.micro_indel_len > 0 || c->params.splice_junct_len > 0)) {
-            eh = hipMemsetAsync(sm, 0, 16 * 4, s);
+        if (eh == hipSuccess && (p.micro_indel_len > 0 || p.splice_junct_len > 0)) {
+            eh = hipMemsetAsync(sm, 0, kSmallWords * 4, s);
             if (eh == hipSuccess) {
-                launch_indel(c->ix, c->cfg, b, n, c->params.micro_indel_len, c->params.splice_junct_len, c->params.min_chimeric_len > 0 ? 1 : 0, d_act[0], sm + 0,
-                             hm + 0, sm + 1, d_seg2, s);
+                launch_indel(c->ix, c->cfg, b, n, p.micro_indel_len, p.splice_junct_len, p.min_chimeric_len > 0 ? 1 : 0, list, sm + kSmCount, hm + kSmCount, sm + kSmCursor, d_seg2, s);
                 eh = hipGetLastError();
             }
         }
-        if (eh == hipSuccess && c->params.min_chimeric_len > 0) {
-            rc2 = size_heavy_scratch(c);
-            if (rc2 == BK_OK) {
-                eh = hipMemsetAsync(sm, 0, 16 * 4, s);
-                if (eh == hipSuccess) {
-                    launch_unaligned_list(b.out, n, d_act[0], sm + 0, s);
-                    eh = hipMemcpyAsync(hm, sm, 4, hipMemcpyDeviceToHost, s);
-                }
-                if (eh == hipSuccess) eh = hipStreamSynchronize(s);
-                if (eh == hipSuccess && hm[0]) {
-                    launch_chimeric(c->ix, c->cfg, b, c->hs, d_act[0], hm[0], c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, sm + 1, d_seg2, s);
-                    eh = hipGetLastError();
-                }
+        if (eh == hipSuccess && p.min_chimeric_len > 0 && (rc2 = size_heavy_scratch(c)) == BK_OK) {
+            eh = hipMemsetAsync(sm, 0, kSmallWords * 4, s);
+            if (eh == hipSuccess) {
+                launch_unaligned_list(b.out, n, list, sm + kSmCount, s);
+                eh = hipMemcpyAsync(hm + kSmCount, sm + kSmCount, 4, hipMemcpyDeviceToHost, s);
+            }
+            if (eh == hipSuccess) eh = hipStreamSynchronize(s);
+            if (eh == hipSuccess && hm[kSmCount]) {
+                launch_chimeric(c->ix, c->cfg, b, c->hs, list, hm[kSmCount], p.min_chimeric_len, maxlen > 512 ? 1 : 0, sm + kSmCursor, d_seg2, s);
+                eh = hipGetLastError();
             }
         }
         const size_t at = c->seg2.size();
@@ -661,19 +606,56 @@ int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint3
         if (eh == hipSuccess) eh = hipStreamSynchronize(s);
         if (rc2 != BK_OK) return rc2;
         if (eh != hipSuccess) return BK_ERR_INTERNAL;
-        if (c->params.min_chimeric_len > 0 && c->cfg.max_hits > 1)          // (the chimeric call's note to the loci replay, see k_heavy)
+        if (p.min_chimeric_len > 0 && c->cfg.max_hits > 1)          // (the chimeric call's note to the loci replay, see k_heavy)
             for (size_t i = at; i < at + n; i++)
                 if (c->seg2[i].flags == 0x40) c->seg2[i] = bk_seg2{};
         tm.end(Span::Heavy, ei, s);
+        return BK_OK;
     }
+};
+
+// One chunk of reads through AlignReads' schedule, until no read is active - or, where no count is read back, for as many
+// phases as a read of maxlen bases can have
+int align_chunk(bk_ctx *c, const DevReads &in, uint32_t first, uint32_t n, uint32_t maxlen, uint32_t minlen, bk_hit *d_out, hipStream_t s, EvTimer &tm)
+{
+    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, kSmallWords * 4, s));
+    ChunkRun r{c, s, tm, n, maxlen, minlen};
+    BK_TRY(r.chunk_setup(in, first, d_out));
+    BK_TRY(r.prepare_reads());
+    PhaseCounts k;
+    BK_TRY(r.phase_counts(0, Behind::Prep, k));
+    if (c->params.best_matches) {
+        hipEvent_t eb = tm.begin(s);
+        BK_TRY(best_matches_chunk(c, r.b, n, r.l.act_in, k.n_act, s));
+        tm.end(Span::Heavy, eb, s);
+        k.n_act = 0;
+    }
+    for (int phase = 0; r.no_readback ? phase < r.cb.max_phases : k.n_act > 0; phase++) {
+        static_assert((kMaxPhases - 1) + 1 < kCtlBatchLine && kCtlBatchLine + 1 == kCtlLines, "line phase + 1 of the last phase, kMaxPhases - 1 by the guard below, lies below the batch's line, the array's last");
+        r.b.act = r.l.act_in;
+        r.b.iv_by_read = (r.search0 && phase == 0) ? 1u : 0u;      // (pass A ran inside the read preparation; every later phase: by position in its active list)
+        BK_TRY(r.search_phase(phase, k));
+        if (phase == c->dbg_stop_phase) { r.debug_stop(phase, r.b.iv_by_read != 0); break; }
+        BK_TRY(r.extend_phase(phase, k));
+        BK_TRY(r.phase_counts(phase, Behind::Extend, k));
+        BK_TRY(r.wave_phase(phase, k));
+        BK_TRY(r.phase_counts(phase, Behind::Wave, k));
+        std::swap(r.l.act_in, r.l.act_out), r.act_cur ^= 1;
+        if (phase + 1 > kMaxPhases - 1) return BK_ERR_INTERNAL;
+    }
+    if (c->dbg_stop_phase >= 0 && !c->dbg_valid) r.debug_stop(kMaxPhases, false);       // (no read reached that phase: an empty list - ctl[kMaxPhases] is never written)
+    if (r.no_readback) {
+        // what the phases needed goes to the host on its own time: the next chunk's sort sizes, reads left for the general kernel (take_phase_history)
+        HIP_TRY(hipMemcpyAsync(c->h_ctl.get(), r.ctl, sizeof(PhaseCtl) * kCtlLines, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c->ev_ctl, s));
+        c->ctl_pending = true, c->ctl_pending_reads = n, c->ctl_pending_phases = r.cb.max_phases, c->ctl_pending_maxlen = tm.on ? 0 : maxlen;
+    }
+    if (c->params.micro_indel_len > 0 || c->params.splice_junct_len > 0 || c->params.min_chimeric_len > 0) BK_TRY(r.second_segments());
     hipEvent_t e4 = tm.begin(s);
     launch_count_seqs(d_out, n, c->image.id2idx.get(), c->ix.n_ent, c->fixed.seq_counts.get(), s);
     HIP_TRY(hipGetLastError());
     tm.end(Span::Other, e4, s);
-    if (c->cfg.max_hits > 1 && !c->params.best_matches) {
-        int rl = collect_loci(c, b, n, maxlen, s);
-        if (rl) return rl;
-    }
+    if (c->cfg.max_hits > 1 && !c->params.best_matches) return collect_loci(c, r.b, n, maxlen, s);
     return BK_OK;
 }
 
@@ -687,7 +669,7 @@ int take_phase_history(bk_ctx *c, bool wait)
     if (wait) HIP_TRY(bk::wait_event(c->ev_ctl));
     else if (hipEventQuery(c->ev_ctl) != hipSuccess) { (void)hipGetLastError(); return BK_OK; }
     c->ctl_pending = false;
-    const PhaseCtl *h = c->h_ctl.get();
+    PhaseCtl *h = c->h_ctl.get();
     const double n = (double)std::max<uint32_t>(c->ctl_pending_reads, 1);
     for (int ph = 0; ph < kMaxPhases; ph++) {
         c->hist_slist[ph] = ph < c->ctl_pending_phases ? (double)h[ph].n_slist / n : 0.0;
@@ -698,8 +680,8 @@ int take_phase_history(bk_ctx *c, bool wait)
         }
     }
     // (bk_align_batch_device_async: the longest read its caller promised against the longest the batch really held)
-    if (c->ctl_pending_maxlen && h[kMaxPhases + 1].n_act > c->ctl_pending_maxlen) {
-        fprintf(stderr, "biokanga_amd: a batch held a read of %u bases, its caller had promised at most %u\n", h[kMaxPhases + 1].n_act, c->ctl_pending_maxlen);
+    if (c->ctl_pending_maxlen && *ctl_longest_read(h) > c->ctl_pending_maxlen) {
+        fprintf(stderr, "biokanga_amd: a batch held a read of %u bases, its caller had promised at most %u\n", *ctl_longest_read(h), c->ctl_pending_maxlen);
         c->async_error = BK_ERR_PARAMS;
     }
     c->hist_valid = true;
@@ -717,11 +699,11 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     if (enqueue_only) {
         const uint32_t ml = maxlen_known;
         const bool plain = c->cfg.max_hits == 1 && !c->params.best_matches && !c->params.micro_indel_len && !c->params.splice_junct_len && !c->params.min_chimeric_len;
-        const bool fits = ml >= 1 && ml <= 16u * (uint32_t)kNwLongest && nreads <= c->cap_reads && nreads <= c->chunk_reads && words_per_read(ml) <= c->cap_wpr &&
+        const bool fits = ml >= 1 && window_words_for(ml) != 0 && nreads <= c->cap_reads && nreads <= c->chunk_reads && words_per_read(ml) <= c->cap_wpr &&
                           iv_cores_for(c, ml) <= c->cap_iv_cores && rd2w_for(ml) <= c->cap_rd2w &&
                           (uint64_t)nreads * iv_cores_for(c, ml) * (c->cfg.align_strand == 0 ? 2u : 1u) <= c->buf.slist.cap() && (c->ix.isa != nullptr || c->hs.htab != nullptr) &&
                           plan_table_covers(c, ml);         // (made by bk_ctx_reserve; making it here would allocate and wait)
-        const bool main_path = c->use_wave && c->cfg.heavy_thresh <= 100 && c->ix.k2 != nullptr && c->ix.tgt2 != nullptr && !c->debug && c->async_phases;
+        const bool main_path = main_path_common(c->use_wave != 0, c->cfg.heavy_thresh, c->ix.k2 != nullptr, c->debug, c->async_phases != 0) && c->ix.tgt2 != nullptr;
         if (!plain || !fits || !main_path) return BK_ERR_PARAMS;
     }
     EvTimer tm{c};
@@ -735,13 +717,13 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     // .. and the shortest beside it, where the caller has looked or this call looks anyway: 0, not known, for a call that only enqueues
     uint32_t maxlen = maxlen_known, minlen = maxlen_known ? minlen_known : 0;
     if (!maxlen) {
-        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
-        launch_max_len(d_lens, nreads, c->fixed.small.get() + 5, s);
-        launch_min_len(d_lens, nreads, c->fixed.small.get() + 6, s);
-        HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, kSmallWords * 4, s));
+        launch_max_len(d_lens, nreads, c->fixed.small.get() + kSmMaxLen, s);
+        launch_min_len(d_lens, nreads, c->fixed.small.get() + kSmMinLenInv, s);
+        HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), kSmallWords * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        maxlen = c->h_small.get()[5];
-        minlen = min_len_of(c->h_small.get()[6]);
+        maxlen = c->h_small.get()[kSmMaxLen];
+        minlen = min_len_of(c->h_small.get()[kSmMinLenInv]);
     }
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
     c->last_maxlen = maxlen;
@@ -771,14 +753,13 @@ int align_device(bk_ctx *c, const DevReads &in, uint32_t nreads, bk_hit *d_out, 
     }
     for (uint32_t done = 0; done < nreads;) {
         uint32_t n = std::min(chunk, nreads - done);
-        int rc = align_chunk(c, in, done, n, maxlen, minlen, d_out + done, s, tm);
-        if (rc) return rc;
+        BK_TRY(align_chunk(c, in, done, n, maxlen, minlen, d_out + done, s, tm));
         done += n;
     }
     if (enqueue_only) return BK_OK;          // (the chunk's counts reach the host behind its kernels: take_phase_history of the next call)
     hipEvent_t t1 = tm.begin(s);
     HIP_TRY(bk::wait_stream(s, c->ev_wait));             // (asleep: the caller's thread leaves its CPU to others meanwhile)
-    { int rh = take_phase_history(c, true); if (rh) return rh; }
+    BK_TRY(take_phase_history(c, true));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, t0, t1);
     c->timing.ms_total += ms;
@@ -855,25 +836,18 @@ int bk::engine_pair_device(bk_ctx *c, const DevReads &in, uint32_t n_pairs, bk_h
     const uint32_t wpr = words_per_read(maxlen);
     // (launch_pe never touches the interval records: the slots keep whatever core count the SE pass sized them for)
     const uint32_t ivc = c->cap_iv_cores ? c->cap_iv_cores : iv_cores_for(c, maxlen);
-    int rc = ensure_batch_scratch(c, nreads, wpr, 0, ivc);
-    if (rc && c->image.swin.get()) {                        // the window array goes before a batch is refused for want of memory (as in align_chunk)
-        (void)hipGetLastError();
-        bk::release_swin(c);
-        rc = ensure_batch_scratch(c, nreads, wpr, 0, ivc);
-    }
-    if (rc) return rc;
+    BK_TRY(batch_scratch_or_release_swin(c, nreads, wpr, 0, ivc));
     const DevBatch b = make_batch(c, in, 0, nreads, wpr, c->cap_iv_cores, d_hits);
     if (c->params.min_chimeric_len > 0 && !seg2_host && !seg2_dev) return BK_ERR_PARAMS;
     bk_seg2 *d_seg2 = seg2_dev;
     if (!d_seg2 && seg2_host) {
-        rc = ensure_seg2(c, nreads);
-        if (rc) return rc;
+        BK_TRY(ensure_seg2(c, nreads));
         d_seg2 = c->buf.seg2.get();
         HIP_TRY(hipMemcpyAsync(d_seg2, seg2_host, (size_t)nreads * sizeof(bk_seg2), hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
+    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, kSmallWords * 4, s));
     launch_pe(c->ix, c->cfg, b, pe->pe_mode, pe->pair_min_len, pe->pair_max_len, pe->pair_strand ? 1 : 0, d_hits, n_pairs,
-              c->buf.heavy.get(), c->fixed.small.get(), c->h_small.get(), d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
+              c->buf.heavy.get(), c->fixed.small.get() + kSmCount, c->h_small.get() + kSmCount, d_seg2, c->params.min_chimeric_len, maxlen > 512 ? 1 : 0, c->buf.chrom_accept.get(), c->n_chrom_accept, s);
     HIP_TRY(hipGetLastError());
     if (seg2_host && !seg2_dev) HIP_TRY(hipMemcpyAsync(seg2_host, d_seg2, (size_t)nreads * sizeof(bk_seg2), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -957,7 +931,7 @@ int bk_align_batch_device_async(bk_ctx *c, const void *d_bases, const void *d_of
     if (!c || !max_read_len || (nreads && (!d_bases || !d_offs || !d_lens || !d_out))) return BK_ERR_PARAMS;
     if (!nreads) return BK_OK;
     HIP_TRY(hipSetDevice(c->device));
-    { int rh = take_phase_history(c, false); if (rh) return rh; }       // (also: what an earlier call of this kind found wrong with its batch)
+    BK_TRY(take_phase_history(c, false));       // (also: what an earlier call of this kind found wrong with its batch)
     if (c->async_error) { const int e = c->async_error; c->async_error = 0; return e; }
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     DevReads in;
@@ -972,12 +946,10 @@ int bk_align_batch(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, const 
     HIP_TRY(hipSetDevice(c->device));
     HostExtent x;
     DevReads in;
-    int rc = stage_host_batch(c, bases, offs, lens, nreads, x, in);
-    if (rc) return rc;
+    BK_TRY(stage_host_batch(c, bases, offs, lens, nreads, x, in));
     HIP_TRY(hipStreamSynchronize(c->stream));
     bk_hit *d_out = c->buf.in_out.get();
-    rc = align_device(c, in, nreads, d_out, c->stream);
-    if (rc) return rc;
+    BK_TRY(align_device(c, in, nreads, d_out, c->stream));
     HIP_TRY(hipMemcpy(out, d_out, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
@@ -1097,18 +1069,15 @@ int bk_align_batch_packed(bk_ctx *c, const uint32_t *words, uint64_t n_words, co
     BatchBufs &m = c->buf;
     HIP_TRY(m.in_words.ensure(n_words + kPackedPadWords));
     HIP_TRY(m.in_exc.ensure(n_exc));
-    int rc = ensure_in_reads(c, nreads, true);
-    if (rc) return rc;
+    BK_TRY(ensure_in_reads(c, nreads, true));
     if (n_words) HIP_TRY(hipMemcpyAsync(m.in_words.get(), words, n_words * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(m.in_lens16.get(), lens, (size_t)nreads * 2, hipMemcpyHostToDevice, s));
     if (n_exc) HIP_TRY(hipMemcpyAsync(m.in_exc.get(), exc, n_exc * sizeof(bk_nbase), hipMemcpyHostToDevice, s));
     uint32_t maxlen = 0, minlen = 0;
-    rc = engine_prepare_packed(c, m.in_lens16.get(), nreads, n_words, m.in_exc.get(), n_exc, m.in_lens.get(), m.in_offs.get(), &maxlen, &minlen, s);
-    if (rc) return rc;
+    BK_TRY(engine_prepare_packed(c, m.in_lens16.get(), nreads, n_words, m.in_exc.get(), n_exc, m.in_lens.get(), m.in_offs.get(), &maxlen, &minlen, s));
     DevReads in;
     in.offs = m.in_offs.get(); in.lens = m.in_lens.get(); in.words = m.in_words.get(); in.exc = m.in_exc.get(); in.n_exc = n_exc;
-    rc = align_device(c, in, nreads, m.in_out.get(), s);
-    if (rc) return rc;
+    BK_TRY(align_device(c, in, nreads, m.in_out.get(), s));
     HIP_TRY(hipMemcpy(out, m.in_out.get(), (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
@@ -1131,14 +1100,12 @@ int bk_pair_batch_seg2(bk_ctx *c, const uint8_t *bases, const uint64_t *offs, co
     const uint32_t nreads = 2 * n_pairs;
     HostExtent x;
     DevReads in;
-    int rc = stage_host_batch(c, bases, offs, lens, nreads, x, in);
-    if (rc) return rc;
+    BK_TRY(stage_host_batch(c, bases, offs, lens, nreads, x, in));
     hipStream_t s = c->stream;
     bk_hit *d_hits = c->buf.in_out.get();
     HIP_TRY(hipMemcpyAsync(d_hits, hits, (size_t)nreads * sizeof(bk_hit), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
-    rc = engine_pair_device(c, in, n_pairs, d_hits, x.maxlen, pe, s, seg2, nullptr);
-    if (rc) return rc;
+    BK_TRY(engine_pair_device(c, in, n_pairs, d_hits, x.maxlen, pe, s, seg2, nullptr));
     HIP_TRY(hipMemcpy(hits, d_hits, (size_t)nreads * sizeof(bk_hit), hipMemcpyDeviceToHost));
     return BK_OK;
 }
@@ -1162,11 +1129,11 @@ int bk_pair_batch_seg2_device(bk_ctx *c, const void *d_bases, const void *d_offs
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t nreads = 2 * n_pairs;
     hipStream_t s = c->stream;
-    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
-    launch_max_len((const uint32_t *)d_lens, nreads, c->fixed.small.get() + 5, s);
-    HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), 16 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, kSmallWords * 4, s));
+    launch_max_len((const uint32_t *)d_lens, nreads, c->fixed.small.get() + kSmMaxLen, s);
+    HIP_TRY(hipMemcpyAsync(c->h_small.get(), c->fixed.small.get(), kSmallWords * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t maxlen = c->h_small.get()[5];
+    const uint32_t maxlen = c->h_small.get()[kSmMaxLen];
     if (maxlen > (uint32_t)kMaxReadLenAbs) return BK_ERR_PARAMS;
     DevReads in;
     in.bases = (const uint8_t *)d_bases; in.offs = (const uint64_t *)d_offs; in.lens = (const uint32_t *)d_lens;
@@ -1196,10 +1163,7 @@ int bk_debug_intervals(bk_ctx *c, uint32_t cap_reads, uint32_t *n_act, uint32_t 
     for (uint32_t a = 0; a < na; a++) {
         if (act[a] >= c->dbg_n) return BK_ERR_INTERNAL;
         const int len = (int)(meta[act[a]] & kReadLenMask);
-        const ReadPlan p = make_plan(len, c->cfg);
-        int mm, cl, cd, dummy[1];
-        phase_params(p, c->cfg, c->dbg_phase, mm, cl, cd);
-        const int n = core_offsets(len, cl, cd, p.max_slides, dummy, 0);
+        const int n = plan_geo_direct(len, c->dbg_phase, c->cfg).nc;
         nc[a] = n <= kMaxCoresFast ? (uint32_t)n : 0u;
     }
     // (a phase whose slots go by read - bk_iv_slot.h; 4-byte indexes only - is handed out by position all the same)

@@ -24,6 +24,7 @@
 #include <rccl/rccl.h>
 
 #include "bk_ctx_int.h"
+#include "bk_phase_plan.h"
 #include "bk_cpus.h"
 #include "bk_wait.h"
 #include "bk_env.h"
@@ -56,9 +57,6 @@ void launch_prep(const DevAlignCfg &cfg, const DevBatch &b, uint32_t *act, uint3
                  uint32_t *stripe_cnt, hipStream_t s, const PrepSearch0 *s0 = nullptr);
 void launch_search(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
                    int phase, int cmax, int nstr, int lazy, hipStream_t s);
-void launch_extend(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
-                   int phase, uint32_t *next_act, uint32_t *next_cnt, uint32_t *heavy, uint32_t *heavy_cnt,
-                   uint32_t *cmax_next, hipStream_t s);
 void launch_build_isa(const uint32_t *sa, uint64_t n, uint32_t *isa, hipStream_t s, uint64_t i0 = 0, uint64_t i1 = 0);
 void launch_build_swin(const DevIndex &ix, void *swin, int words, hipStream_t s);
 void launch_swin_breaks(const DevIndex &ix, const int *w, int n_levels, unsigned long long *const *brk, uint64_t a, uint64_t e, uint64_t n_words,
@@ -71,25 +69,19 @@ void launch_swin_fill(const DevIndex &ix, const uint32_t *map, void *swin, int w
 void launch_build_k2(const DevIndex &ix, uint32_t *k2, uint32_t *k3, uint32_t *k4, unsigned long long *bad, hipStream_t s, uint64_t i0 = 0, uint64_t i1 = 0, bool write_k2 = true);
 void launch_build_k2_levels(uint32_t *k2, uint64_t n, hipStream_t s);
 void launch_make_ktab2(const uint32_t *tab, const uint32_t *k2, uint64_t n_entries, uint64_t n, void *out, hipStream_t s, const uint32_t *sa_elem = nullptr);
-void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, const uint32_t *p_n_act, uint32_t n_act_bound,
-                     int phase, int cmax, int nstr, int lazy, uint32_t *list, uint32_t *list_cnt, uint32_t *stage, uint32_t *stripe_cnt,
-                     hipStream_t s);
-void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int phase, int lazy, const uint32_t *list, const uint32_t *sorted,
-                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, uint32_t *deep_list, uint32_t *deep_cnt, uint32_t *stage,
-                     uint32_t *stripe_cnt, hipStream_t s);
-void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s);
+// .. the launchers of a phase: `cur` is the phase's line of counts, `next` the next phase's, `l` the chunk's lists (bk_device.h)
+void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, uint32_t n_act_bound, int phase, int cmax, int nstr, int lazy, hipStream_t s);
+void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, int phase, int lazy, const uint32_t *sorted, uint32_t n_sorted, uint64_t n_bound, bool split, hipStream_t s);
+void launch_clear_iv(const DevBatch &b, const PhaseCtl *cur, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s);
+void launch_keys_search(const DevBatch &b, const PhaseLists &l, const PhaseCtl *cur, uint32_t n_sort, int shift, uint32_t *keys, hipStream_t s);
+void launch_extend(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_act, int phase, hipStream_t s);
+void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_act_bound, int phase, int slots_max, int nw, hipStream_t s);
+void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, const PhaseLists &l, const PhaseCtl *cur, uint32_t n_sort, int shift, uint32_t *keys, const uint32_t *work_of, hipStream_t s);
+void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, const uint32_t *sorted, uint32_t n_sorted, uint32_t n_bound, int phase, int nw, uint32_t max_waves, int len_dwords, hipStream_t s);
+void launch_heavy(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_list, int phase, hipStream_t s);
 void launch_pe(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int pe_mode, int min_len, int max_len, int pair_strand,
                bk_hit *hits, uint32_t n_pairs, uint32_t *orphans, uint32_t *counters, uint32_t *h_count, bk_seg2 *seg2, int min_chim,
                int long_reads, const uint8_t *accept, uint32_t n_accept, hipStream_t s);
-void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, const uint32_t *p_n_act, uint32_t n_act_bound, int phase,
-                 int slots_max, uint32_t *next_act, uint32_t *next_cnt, uint32_t *heavy, uint32_t *heavy_cnt, uint32_t *wave,
-                 uint32_t *wave_cnt, uint32_t *cmax_next, uint32_t *const *stage, uint32_t *stripe_cnt, int nw, hipStream_t s);
-void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const uint32_t *list, const uint32_t *sorted,
-                 uint32_t n_sorted, const uint32_t *p_n_list, uint32_t n_bound, int phase, uint32_t *cursor, uint32_t *next_act, uint32_t *next_cnt,
-                 uint32_t *cmax_next, int nw, uint32_t max_waves, int len_dwords, hipStream_t s);
-void launch_heavy(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const uint32_t *list,
-                  uint32_t n_list, int phase, uint32_t *cursor, uint32_t *next_act, uint32_t *next_cnt, uint32_t *cmax_next,
-                  hipStream_t s);
 int build_sa_device(const uint8_t *d_seq, uint64_t n, void *d_sa_out, int el_size, hipStream_t s);
 int scan_counts_u64(const unsigned long long *in, unsigned long long *out, uint32_t n, void *tmp, size_t *tmp_bytes, hipStream_t s);
 void launch_loci_count(const bk_hit *out, uint32_t n, int clamp_to, unsigned long long *cnt, hipStream_t s);
@@ -108,9 +100,6 @@ void launch_loci_enum(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch
                       bk_seg2 *seg2, bk_loci_trims *trims, hipStream_t s);
 int sort_list_by_key(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, uint32_t n,
                      void *tmp, size_t *tmp_bytes, hipStream_t s);
-void launch_keys_search(const DevBatch &b, const uint32_t *list, const uint32_t *p_n, uint32_t n_sort, int shift, uint32_t *keys, hipStream_t s);
-void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, const uint32_t *list, const uint32_t *p_n, uint32_t n_sort, int shift, uint32_t *keys,
-                      const uint32_t *work_of, hipStream_t s);
 
 // BK_TIMING=1: wall-clock of the set-up stages on stderr
 struct StageClock {
@@ -149,10 +138,10 @@ inline bool prep_search0_on(const bk_ctx *c, bool reg_path, bool cores_fit, int 
            cores_fit && cmax0 == 1 && !c->params.best_matches;
 }
 
-// 64-bit words of a read's 2 bit/base row in the register-window kernel family that takes reads of up to maxlen bases
-inline uint32_t rd2w_for(uint32_t maxlen)
+// 64-bit words of a read's 2 bit/base row (rd2w_for, bk_phase_plan.h) as a batch of this context gets them: none off the register-window path (no wave kernels, longer reads) or without the 2-bit target
+inline uint32_t rd2_words(const bk_ctx *c, uint32_t maxlen)
 {
-    return maxlen <= 128 ? 4u : (maxlen <= 256 ? 8u : (maxlen <= 16u * (uint32_t)kNwLong ? (uint32_t)kNwLong / 2 : (uint32_t)kNwLongest / 2));
+    return c->use_wave && c->ix.tgt2 != nullptr ? (uint32_t)window_words_for(maxlen) / 2 : 0u;
 }
 
 // per-read bytes of batch scratch: packed rows in both forms, interval records, work lists (reads, search items and their striped

@@ -668,20 +668,16 @@ __global__ void __launch_bounds__(BS) k_flat(DevIndex ix, DevAlignCfg cfg, DevBa
 #endif
 }
 
-void launch_extend(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, uint32_t n_act,
-                   int phase, uint32_t *next_act, uint32_t *next_cnt, uint32_t *heavy, uint32_t *heavy_cnt,
-                   uint32_t *cmax_next, hipStream_t s)
+void launch_extend(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_act, int phase, hipStream_t s)
 {
     unsigned blocks = (n_act + 255) / 256;
-    if (ix.sa_hi) hipLaunchKernelGGL(k_extend<true>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, act, n_act, phase, next_act, next_cnt, heavy, heavy_cnt, cmax_next);
-    else hipLaunchKernelGGL(k_extend<false>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, act, n_act, phase, next_act, next_cnt, heavy, heavy_cnt, cmax_next);
+    if (ix.sa_hi) hipLaunchKernelGGL(k_extend<true>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, l.act_in, n_act, phase, l.act_out, &next->n_act, l.heavy, &cur->n_heavy, &next->cmax);
+    else hipLaunchKernelGGL(k_extend<false>, dim3(blocks), dim3(256), 0, s, ix, cfg, b, l.act_in, n_act, phase, l.act_out, &next->n_act, l.heavy, &cur->n_heavy, &next->cmax);
 }
 
-// stage: three buffers of at least n_act + (kListStripes + 2) * 1024 entries, stripe_cnt: kListStripes * 16 words, zero between launches
-// n_act_bound: no more reads than this are on the active list (its length is *p_n_act, in device memory)
-void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, const uint32_t *p_n_act, uint32_t n_act_bound, int phase,
-                 int slots_max, uint32_t *next_act, uint32_t *next_cnt, uint32_t *heavy, uint32_t *heavy_cnt, uint32_t *wave,
-                 uint32_t *wave_cnt, uint32_t *cmax_next, uint32_t *const *stage, uint32_t *stripe_cnt, int nw, hipStream_t s)
+// l.stage: three buffers of at least n_act + (kListStripes + 2) * 1024 entries, l.stripe_cnt: kListStripes * 16 words, zero between launches
+// n_act_bound: no more reads than this are on the active list (its length is cur->n_act, in device memory)
+void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_act_bound, int phase, int slots_max, int nw, hipStream_t s)
 {
     constexpr int bs = 256;                            // reads (= threads) per block: 64 .. 1024 measured, 256 best (profiles/NOTES.md, round 2)
     nw &= 0xff;
@@ -692,19 +688,19 @@ void launch_flat(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, 
     size_t lds = (size_t)bs * slots_max * (flat_caches_first(wide, bs, slots_max) ? 6 : 2);
     if (flat_plan_in_lds(nw)) lds += 2 * (size_t)b.plan_n * sizeof(uint2);      // this phase's row of the plan table and the next one's
     StripeSet out;
-    out.cnt = stripe_cnt;
-    for (int i = 0; i < 3; i++) out.stage[i] = stage[i];
+    out.cnt = l.stripe_cnt;
+    for (int i = 0; i < 3; i++) out.stage[i] = l.stage[i];
     out.cap = stripe_cap(blocks, (unsigned)bs);
-    const int have_wave = wave != nullptr;
-#define BK_FLAT(W, N) hipLaunchKernelGGL((k_flat<W, N, 256>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, act, p_n_act, phase, slots_max, out, have_wave)
+    const int have_wave = l.wave != nullptr;
+#define BK_FLAT(W, N) hipLaunchKernelGGL((k_flat<W, N, 256>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, l.act_in, &cur->n_act, phase, slots_max, out, have_wave)
     if (nw <= 8) { if (wide) BK_FLAT(true, 8); else BK_FLAT(false, 8); }
     else if (nw <= 16) { if (wide) BK_FLAT(true, 16); else BK_FLAT(false, 16); }
     else if (nw <= kNwLong) { if (wide) BK_FLAT(true, kNwLong); else BK_FLAT(false, kNwLong); }
     else { if (wide) BK_FLAT(true, kNwLongest); else BK_FLAT(false, kNwLongest); }
 #undef BK_FLAT
     // list order of the set: next phase, wave kernel, general kernel (the wave list may be absent: then it stays empty)
-    uint32_t *dense[3] = {next_act, have_wave ? wave : heavy, heavy}, *total[3] = {next_cnt, have_wave ? wave_cnt : heavy_cnt, heavy_cnt};
-    launch_compact(out, dense, total, 3, cmax_next, s);
+    uint32_t *dense[3] = {l.act_out, have_wave ? l.wave : l.heavy, l.heavy}, *total[3] = {&next->n_act, have_wave ? &cur->n_wave : &cur->n_heavy, &cur->n_heavy};
+    launch_compact(out, dense, total, 3, &next->cmax, s);
 }
 
 #ifdef BK_PROF

@@ -510,15 +510,13 @@ __global__ void __launch_bounds__(256) k_loci_single(const bk_hit *__restrict__ 
         list[atomicAdd(list_cnt, 1u)] = r;
 }
 
-void launch_heavy(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const uint32_t *list,
-                  uint32_t n_list, int phase, uint32_t *cursor, uint32_t *next_act, uint32_t *next_cnt, uint32_t *cmax_next,
-                  hipStream_t s)
+void launch_heavy(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, uint32_t n_list, int phase, hipStream_t s)
 {
     uint32_t waves = n_list < hs.n_slots ? n_list : hs.n_slots;
     unsigned blocks = (waves + 3) / 4;
-    expand_rd4(b, list, n_list, s);
-    if (ix.sa_hi) hipLaunchKernelGGL((k_heavy<true, 0>), dim3(blocks), dim3(256), 0, s, ix, cfg, b, hs, list, n_list, phase, cursor, next_act, next_cnt, cmax_next, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((k_heavy<false, 0>), dim3(blocks), dim3(256), 0, s, ix, cfg, b, hs, list, n_list, phase, cursor, next_act, next_cnt, cmax_next, nullptr, nullptr, nullptr);
+    expand_rd4(b, l.heavy, n_list, s);
+    if (ix.sa_hi) hipLaunchKernelGGL((k_heavy<true, 0>), dim3(blocks), dim3(256), 0, s, ix, cfg, b, hs, l.heavy, n_list, phase, &cur->heavy_cursor, l.act_out, &next->n_act, &next->cmax, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((k_heavy<false, 0>), dim3(blocks), dim3(256), 0, s, ix, cfg, b, hs, l.heavy, n_list, phase, &cur->heavy_cursor, l.act_out, &next->n_act, &next->cmax, nullptr, nullptr, nullptr);
 }
 
 // -c: the chimeric LocateCoreMultiples call for every read of `list` (reads nothing else aligned); trims into seg2[]

@@ -495,13 +495,14 @@ int setup_entries(bk_ctx *c, const bk_entry_info *entries, uint32_t n_entries)
     HIP_TRY(dev_zero_now(fx.seq_counts.get(), n_entries * 8));
     HIP_TRY(fx.ctr.ensure((size_t)kCtrStripes * 8));
     HIP_TRY(dev_zero_now(fx.ctr.get(), (size_t)kCtrStripes * 8 * 8));
-    HIP_TRY(fx.small.ensure(16));
-    HIP_TRY(fx.ctl.ensure(kMaxPhases + 2));
-    HIP_TRY(c->h_ctl.ensure(kMaxPhases + 2));
+    HIP_TRY(fx.small.ensure(kSmallWords));
+    HIP_TRY(fx.ctl.ensure(kCtlLines));
+    HIP_TRY(c->h_ctl.ensure(kCtlLines));
+    HIP_TRY(c->h_line.ensure(2));
     HIP_TRY(bk::make_wait_event(&c->ev_ctl));
     HIP_TRY(bk::make_wait_event(&c->ev_wait));
     HIP_TRY(fx.ctr_aux.ensure(4));
-    HIP_TRY(c->h_small.ensure(2 * sizeof(PhaseCtl) / sizeof(uint32_t)));
+    HIP_TRY(c->h_small.ensure(kSmallWords));
     int rc = derive_cfg(c);
     clk0.lap("entry table, small buffers");
     return rc;

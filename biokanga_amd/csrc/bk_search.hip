@@ -519,20 +519,19 @@ __global__ void __launch_bounds__(256) k_keys_search(DevBatch b, const uint32_t 
         keys[i] = i < n ? (uint32_t)(iv_start(b, list[i]) >> shift) : 0xFFFFFFFFu;
 }
 
-void launch_keys_search(const DevBatch &b, const uint32_t *list, const uint32_t *p_n, uint32_t n_sort, int shift, uint32_t *keys, hipStream_t s)
+void launch_keys_search(const DevBatch &b, const PhaseLists &l, const PhaseCtl *cur, uint32_t n_sort, int shift, uint32_t *keys, hipStream_t s)
 {
     if (!n_sort) return;
     unsigned blocks = (n_sort + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_keys_search, dim3(blocks), dim3(256), 0, s, b, list, p_n, n_sort, shift, keys);
+    hipLaunchKernelGGL(k_keys_search, dim3(blocks), dim3(256), 0, s, b, l.slist, &cur->n_slist, n_sort, shift, keys);
 }
 
-// stage: at least n_act * cmax * nstr + (kListStripes + 2) * 1024 entries; stripe_cnt: kListStripes * 16 words, zero between launches
-// n_act_bound: no more reads than this are on the active list (its length is *p_n_act, in device memory)
-void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const uint32_t *act, const uint32_t *p_n_act, uint32_t n_act_bound,
-                     int phase, int cmax, int nstr, int lazy, uint32_t *list, uint32_t *list_cnt, uint32_t *stage, uint32_t *stripe_cnt,
-                     hipStream_t s)
+// l.slist_stage: at least n_act * cmax * nstr + (kListStripes + 2) * 1024 entries; l.stripe_cnt: kListStripes * 16 words, zero between launches
+// n_act_bound: no more reads than this are on the active list (its length is cur->n_act, in device memory)
+void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, uint32_t n_act_bound, int phase, int cmax, int nstr, int lazy, hipStream_t s)
 {
+    uint32_t *list = l.slist, *list_cnt = &cur->n_slist;
     uint64_t threads = (uint64_t)n_act_bound * (uint64_t)(cmax * nstr);
     if (!threads) return;
     lazy &= 0xff;
@@ -541,36 +540,35 @@ void launch_search_a(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch 
     const uint64_t tiles = (threads + per - 1) / per;
     const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 16384);       // (a block takes tiles until the list is done)
     StripeSet out;
-    out.cnt = stripe_cnt;
-    out.stage[0] = out.stage[1] = out.stage[2] = stage;
+    out.cnt = l.stripe_cnt;
+    out.stage[0] = out.stage[1] = out.stage[2] = l.slist_stage;
     out.cap = stripe_cap((unsigned)tiles, (unsigned)per);             // (stripes go by tile number)
     static_assert(256 * ilp <= (int)kItemMaxLaneOfs, "a lane's offset within a tile must stay in item_decode's range");
     const ItemGeo ig = item_geo_make((uint32_t)(cmax * nstr), (uint32_t)cmax, (uint64_t)blocks * per);
     const size_t lds = (size_t)b.plan_n * sizeof(uint2);           // the phase's row of the plan table
-    hipLaunchKernelGGL(k_search_a_ilp<ilp>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, act, p_n_act, phase, cmax, nstr, lazy, out, ig);
+    hipLaunchKernelGGL(k_search_a_ilp<ilp>, dim3(blocks), dim3(256), lds, s, ix, cfg, b, l.act_in, &cur->n_act, phase, cmax, nstr, lazy, out, ig);
     launch_compact(out, &list, &list_cnt, 1, nullptr, s);
 }
 
-// list: the work items as pass A left them (*p_n_list of them, at most n_bound); sorted / n_sorted: the grouped copy of the first n_sorted (or null)
-// deep_cnt null: a lane carries its item to the end.  Else ("search_split") the items the key levels do not settle are finished by a second
-// launch: their slots go through the stripes of `stage` (at least n_bound + (kListStripes + 2) * 1024 entries; stripe_cnt as for pass A)
-// into `deep_list` (at least n_bound entries; it may be `list` itself, which nobody reads once k_search_b has ended) and their number is
-// added to *deep_cnt, zero before the call.  k_search_deep is sized by n_bound as well: blocks beyond the count leave at once, none at all
-// does nothing.
-void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, int phase, int lazy, const uint32_t *list, const uint32_t *sorted,
-                     uint32_t n_sorted, const uint32_t *p_n_list, uint64_t n_bound, uint32_t *deep_list, uint32_t *deep_cnt, uint32_t *stage,
-                     uint32_t *stripe_cnt, hipStream_t s)
+// l.slist: the work items as pass A left them (cur->n_slist of them, at most n_bound); sorted / n_sorted: the grouped copy of the first n_sorted (or null)
+// split false: a lane carries its item to the end.  Else ("search_split") the items the key levels do not settle are finished by a second
+// launch: their slots go through the stripes of l.slist_stage (at least n_bound + (kListStripes + 2) * 1024 entries; l.stripe_cnt as for
+// pass A) back into l.slist, which nobody reads once k_search_b has ended, and their number is added to cur->n_deep, zero since the chunk
+// began.  k_search_deep is sized by n_bound as well: blocks beyond the count leave at once, none at all does nothing.
+void launch_search_b(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const PhaseLists &l, PhaseCtl *cur, int phase, int lazy, const uint32_t *sorted, uint32_t n_sorted, uint64_t n_bound, bool split, hipStream_t s)
 {
     if (!n_bound) return;
+    const uint32_t *list = l.slist, *p_n_list = &cur->n_slist;
+    uint32_t *deep_list = l.slist, *deep_cnt = &cur->n_deep;
     const uint64_t tiles = (n_bound + 255) / 256;
     unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 32768);
     const SlotGeo sg = slot_geo_make(b.iv_stride, b.iv_cores);
     const size_t lds = (size_t)b.plan_n * sizeof(uint2);
     StripeSet deep;
-    deep.cnt = stripe_cnt;
-    deep.stage[0] = deep.stage[1] = deep.stage[2] = stage;
+    deep.cnt = l.stripe_cnt;
+    deep.stage[0] = deep.stage[1] = deep.stage[2] = l.slist_stage;
     deep.cap = stripe_cap((unsigned)tiles, 256);                      // (stripes go by tile number)
-    if (deep_cnt == nullptr) {
+    if (!split) {
         if (ix.sa_hi) hipLaunchKernelGGL((k_search_b<true, false>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
         else hipLaunchKernelGGL((k_search_b<false, false>), dim3(blocks), dim3(256), lds, s, ix, cfg, b, phase, lazy, list, sorted, n_sorted, p_n_list, sg, deep);
         return;
@@ -600,12 +598,12 @@ __global__ void __launch_bounds__(256) k_clear_iv(DevBatch b, const uint32_t *__
     }
 }
 
-void launch_clear_iv(const DevBatch &b, const uint32_t *p_n_act, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s)
+void launch_clear_iv(const DevBatch &b, const PhaseCtl *cur, uint32_t n_act_bound, int cmax, int st0, int st1, uint32_t word, hipStream_t s)
 {
     const uint64_t total = (uint64_t)n_act_bound * (uint64_t)cmax * (uint64_t)(st1 - st0 + 1);
     if (!total) return;
     const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 16384);
-    hipLaunchKernelGGL(k_clear_iv, dim3(blocks), dim3(256), 0, s, b, p_n_act, cmax, st0, st1, word);
+    hipLaunchKernelGGL(k_clear_iv, dim3(blocks), dim3(256), 0, s, b, cur ? &cur->n_act : nullptr, cmax, st0, st1, word);      // (cur null: slots by read, nobody reads the count)
 }
 
 }  // namespace bk

@@ -114,12 +114,12 @@ int bk_snp_sites(bk_ctx *c, uint32_t chrom_id, int32_t min_reads, double min_non
     unsigned long long h_tot[4] = {0, 0, 0, 0};
     uint32_t n = 0;
     for (;;) {                                                        // second pass only when the list outgrew its buffer
-        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, 16 * 4, s));
+        HIP_TRY(hipMemsetAsync(c->fixed.small.get(), 0, kSmallWords * 4, s));
         HIP_TRY(hipMemsetAsync(c->fixed.snp_tot.get(), 0, 4 * 8, s));
         launch_snp_sites(c->ix, c->fixed.snp_planes.get(), ent->start_ofs, (uint32_t)ent->seq_len, (uint32_t)min_reads, min_nonref_prop, d_sites.get(),
-                         (uint32_t)d_sites.cap(), c->fixed.small.get(), c->fixed.snp_tot.get(), s);
+                         (uint32_t)d_sites.cap(), c->fixed.small.get() + kSmCount, c->fixed.snp_tot.get(), s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&n, c->fixed.small.get(), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n, c->fixed.small.get() + kSmCount, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h_tot, c->fixed.snp_tot.get(), sizeof(h_tot), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (n <= d_sites.cap()) break;

@@ -13,23 +13,15 @@ int bk_ctx_reserve(bk_ctx *c, uint32_t max_batch_reads, uint32_t max_read_len)
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t n = std::min(max_batch_reads, c->chunk_reads);
     const uint32_t wpr = words_per_read(max_read_len);
-    const bool reg_path = c->use_wave && max_read_len <= 16u * (uint32_t)kNwLongest;
-    const bool two_bit = reg_path && c->ix.tgt2 != nullptr;
     const uint32_t ivc = iv_cores_for(c, max_read_len);
-    int rc = ensure_batch_scratch(c, n, wpr, two_bit ? rd2w_for(max_read_len) : 0u, ivc);
-    if (rc) return rc;
-    if (c->ix.k2) {
-        // pass B's work list: at most one item per (read, strand, core)
-        const uint64_t lanes = (uint64_t)n * ivc * (c->cfg.align_strand == 0 ? 2u : 1u);
-        rc = ensure_slist(c, lanes, c->stream);
-        if (rc) return rc;
-    }
-    if (c->sort_lists) { rc = ensure_sort_scratch(c, n, c->stream); if (rc) return rc; }      // (grown when a phase's list is longer)
-    if (c->use_wave && c->ix.isa == nullptr) { rc = size_heavy_scratch(c); if (rc) return rc; }     // hash-set dedupe of the wave kernel
+    BK_TRY(ensure_batch_scratch(c, n, wpr, rd2_words(c, max_read_len), ivc));
+    // pass B's work list: at most one item per (read, strand, core)
+    if (c->ix.k2) BK_TRY(ensure_slist(c, (uint64_t)n * ivc * (c->cfg.align_strand == 0 ? 2u : 1u), c->stream));
+    if (c->sort_lists) BK_TRY(ensure_sort_scratch(c, n, c->stream));      // (grown when a phase's list is longer)
+    if (c->use_wave && c->ix.isa == nullptr) BK_TRY(size_heavy_scratch(c));     // hash-set dedupe of the wave kernel
     // the plan table for reads of up to max_read_len bases under the parameters as they stand, in HBM when the call returns: a batch on
     // any stream may read it, and the call that only enqueues never makes it
-    rc = plan_table_for(c, max_read_len, c->stream);
-    if (rc) return rc;
+    BK_TRY(plan_table_for(c, max_read_len, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BK_OK;
 }

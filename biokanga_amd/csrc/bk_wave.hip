@@ -738,29 +738,25 @@ __global__ void __launch_bounds__(256) k_keys_wave(DevAlignCfg cfg, DevBatch b, 
   }
 }
 
-void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, const uint32_t *list, const uint32_t *p_n, uint32_t n_sort, int shift, uint32_t *keys,
-                      const uint32_t *work_of, hipStream_t s)
+void launch_keys_wave(const DevAlignCfg &cfg, const DevBatch &b, int phase, const PhaseLists &l, const PhaseCtl *cur, uint32_t n_sort, int shift, uint32_t *keys, const uint32_t *work_of, hipStream_t s)
 {
     if (!n_sort) return;
     unsigned blocks = (n_sort + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_keys_wave, dim3(blocks), dim3(256), 0, s, cfg, b, phase, list, p_n, n_sort, shift, keys, work_of);
+    hipLaunchKernelGGL(k_keys_wave, dim3(blocks), dim3(256), 0, s, cfg, b, phase, l.wave, &cur->n_wave, n_sort, shift, keys, work_of);
 }
 
-// list: the reads k_flat handed on (*p_n_list of them, at most n_bound); sorted / n_sorted: the sorted copy of the first n_sorted (or null)
+// l.wave: the reads k_flat handed on (cur->n_wave of them, at most n_bound); sorted / n_sorted: the sorted copy of the first n_sorted (or null)
 // len_dwords: (len + 15) >> 4 of EVERY read of the batch when they all agree in it, else 0 (uniform_dwords, bk_wave_form.h) - the
 // 8-word window-array form is then launched in its length-specialised form
-void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const uint32_t *list, const uint32_t *sorted,
-                 uint32_t n_sorted, const uint32_t *p_n_list, uint32_t n_bound,
-                 int phase, uint32_t *cursor, uint32_t *next_act, uint32_t *next_cnt, uint32_t *cmax_next, int nw, uint32_t max_waves,
-                 int len_dwords, hipStream_t s)
+void launch_wave(const DevIndex &ix, const DevAlignCfg &cfg, const DevBatch &b, const HeavyScratch &hs, const PhaseLists &l, PhaseCtl *cur, PhaseCtl *next, const uint32_t *sorted, uint32_t n_sorted, uint32_t n_bound, int phase, int nw, uint32_t max_waves, int len_dwords, hipStream_t s)
 {
     if (!n_bound) return;
     const bool wide = ix.sa_hi != nullptr, hash = ix.isa == nullptr;
     uint32_t waves = n_bound < max_waves ? n_bound : max_waves;
     if (hash && waves > hs.n_slots) waves = hs.n_slots;
     unsigned blocks = (waves + 3) / 4;
-    const WaveArgs wa{ix, cfg, b, hs, list, sorted, n_sorted, p_n_list, phase, cursor, next_act, next_cnt, cmax_next};
+    const WaveArgs wa{ix, cfg, b, hs, l.wave, sorted, n_sorted, &cur->n_wave, phase, &cur->wave_cursor, l.act_out, &next->n_act, &next->cmax};
 #define BK_WAVE(N, W, H, S, G) hipLaunchKernelGGL((k_wave<N, W, H, S, G>), dim3(blocks), dim3(256), 0, s, wa)
     const bool sw = ix.swin != nullptr && b.rd2 != nullptr && ix.sw_words == ((nw & 0xff) <= 8 ? 3 : 5);      // (entries of this kernel family's size)
     // (reads of up to 128 bases have four cores or so per strand: their small intervals take a round each; sharing rounds, as the wider
