@@ -226,12 +226,15 @@ __device__ void explore_splice(const uint64_t *__restrict__ rdw, const uint64_t 
                 if (pb > 4 || tb > 4) break;
                 continue;
             }
-            int score = kIndelBase + plen * kIndelMatch - ((k + cmm) * kIndelMismatch + (gap / 1000) * kSpliceLenCost);
+            // the reference scores in a UINT32 and keeps the score as a UINT16 (SfxArrayV2.cpp:8448,8699, SfxArrayV2.h:238): once the length
+            // cost exceeds the rest (an intron of some 80 000 bases under a 100-base read) the score wraps, beats whatever was kept so
+            // far and stays behind as its low 16 bits - such junctions are reported, the last one scanned wins
+            uint32_t score = (uint32_t)(kIndelBase + plen * kIndelMatch - ((k + cmm) * kIndelMismatch + (gap / 1000) * kSpliceLenCost));
             // donor = first two intron bases after the kept part, acceptor = last two before the moved part (target order)
-            if (RIGHT) score += splice_bonus(plus, T(mo), T(mo + 1), T(ts - 1), T(ts - 2));
-            else score += splice_bonus(plus, T(ts - 1), T(ts - 2), T(mo), T(mo + 1));
-            if (score > cur.score) {
-                cur.score = score; cur.r = 3;
+            if (RIGHT) score += (uint32_t)splice_bonus(plus, T(mo), T(mo + 1), T(ts - 1), T(ts - 2));
+            else score += (uint32_t)splice_bonus(plus, T(ts - 1), T(ts - 2), T(mo), T(mo + 1));
+            if (score > (uint32_t)cur.score) {
+                cur.score = (int)(score & 0xFFFFu); cur.r = 3;
                 if (RIGHT) {
                     cur.s0_len = mo; cur.s0_loci = t; cur.s0_mm = k;
                     cur.s1_len = seg_len; cur.s1_loci = t + (uint64_t)mo + (uint64_t)gap; cur.s1_mm = cmm; cur.s1_ofs = mo;

@@ -944,13 +944,16 @@ static int explore_splice_right(char strand, int max_junct, int max_mm, int core
                 if (pb > B_N || tb > B_N) break;
                 continue;
             }
-            int score = BASE_SCORE + plen * SCORE_MATCH - ((k + cmm) * SCORE_MISMATCH + (gap / 1000) * SPLICE_LEN);
-            score += splice_bonus(strand, donor[0] & 7, donor[1] & 7, t_start[-1] & 7, t_start[-2] & 7);
-            if (score > cur.score) {
+            /* CurScore is a UINT32 there and tsHitLoci.Score a UINT16 (:8448, SfxArrayV2.h:238): once the length cost exceeds the rest (an
+             * intron of some 80 000 bases for a 100-base read) the score wraps, beats every placement scored so far and is kept as its low
+             * 16 bits - such junctions are reported, the last one scanned wins */
+            uint32_t score = (uint32_t)(BASE_SCORE + plen * SCORE_MATCH - ((k + cmm) * SCORE_MISMATCH + (gap / 1000) * SPLICE_LEN));
+            score += (uint32_t)splice_bonus(strand, donor[0] & 7, donor[1] & 7, t_start[-1] & 7, t_start[-2] & 7);
+            if (score > (uint32_t)cur.score) {
                 memset(&cur, 0, sizeof(cur));
                 cur.s0_len = mm_ofs[k]; cur.s0_loci = (uint64_t)targ_ofs; cur.s0_mm = k; cur.strand = strand;
                 cur.s1_len = plen - mm_ofs[k]; cur.s1_loci = (uint64_t)(targ_ofs + mm_ofs[k] + gap); cur.s1_mm = cmm;
-                cur.s1_read_ofs = mm_ofs[k]; cur.score = score; cur.is_indel = 2;      /* here: 2 = FlgSplice */
+                cur.s1_read_ofs = mm_ofs[k]; cur.score = (int)(uint16_t)score; cur.is_indel = 2;      /* here: 2 = FlgSplice */
             }
         }
     }
@@ -1027,13 +1030,13 @@ static int explore_splice_left(char strand, int max_junct, int max_mm, int core_
                 if (pb > B_N || tb > B_N) break;
                 continue;
             }
-            int score = BASE_SCORE + plen * SCORE_MATCH - ((k + cmm) * SCORE_MISMATCH + (gap / 1000) * SPLICE_LEN);
-            score += splice_bonus(strand, t_start[1] & 7, t_start[2] & 7, donor[0] & 7, donor[-1] & 7);
-            if (score > cur.score) {
+            uint32_t score = (uint32_t)(BASE_SCORE + plen * SCORE_MATCH - ((k + cmm) * SCORE_MISMATCH + (gap / 1000) * SPLICE_LEN));      /* (:8699) */
+            score += (uint32_t)splice_bonus(strand, t_start[1] & 7, t_start[2] & 7, donor[0] & 7, donor[-1] & 7);
+            if (score > (uint32_t)cur.score) {
                 memset(&cur, 0, sizeof(cur));
                 cur.s0_len = plen - mm_ofs[k]; cur.s0_loci = (uint64_t)(targ_ofs - gap); cur.s0_mm = cmm; cur.strand = strand;
                 cur.s1_len = mm_ofs[k]; cur.s1_loci = cur.s0_loci + (uint64_t)cur.s0_len + (uint64_t)gap; cur.s1_mm = k;
-                cur.s1_read_ofs = cur.s0_len; cur.score = score; cur.is_indel = 2;
+                cur.s1_read_ofs = cur.s0_len; cur.score = (int)(uint16_t)score; cur.is_indel = 2;
             }
         }
     }

@@ -14,6 +14,9 @@ Fixtures
   repeat/  unique background + four families of an exact 25-mer repeated K = 2000/3000/4000/6000
            times; reads whose only clean core is the repeat (pins the 100-candidate copy-count
            cut-off and MaxIter truncation, SfxArrayV2.cpp:5857-5875)
+  indeledge/  (make_golden_indel_edges.py) edge cases of -a / -A: flank and length limits, sequence and
+           concatenation ends, read lengths 30..1000, mismatch budgets, Ns, ties, large anchor intervals;
+           some of its runs use the repeat/ genome
 """
 import gzip
 import os

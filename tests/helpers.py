@@ -727,3 +727,59 @@ def write_big_genome(path, big_len=537_000_000, small_len=1_000_000, seed=5377):
             if n % 70:
                 f.write(seq[full * 70:].tobytes() + b"\n")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# tests/golden/indeledge (tests/golden/make_golden_indel_edges.py): microInDel / splice junction edge cases, some of its runs on the
+# tests/golden/repeat genome
+def indel_edge_params(flags):
+    """the reference's flags of a run in cases.json -> (make_params / AlignParams keywords, min read length, max read length)"""
+    kw, lo, hi = {}, 50, 500
+    keys = {"-s": "max_subs", "-a": "micro_indel_len", "-A": "splice_junct_len", "-Q": "align_strand", "-R": "max_ml", "-c": "min_chimeric_len"}
+    for f in flags:
+        if f[:2] in keys:
+            kw[keys[f[:2]]] = int(f[2:])
+        elif f[:2] == "-l":
+            lo = int(f[2:])
+        elif f[:2] == "-L":
+            hi = int(f[2:])
+        else:
+            assert f[:2] == "-r", f
+    return kw, lo, hi
+
+
+def indel_edge_fixture(dst):
+    """unpacks the fixture into dst -> (cases.json, {genome: .sfx path}, {reads file: (names, bases, offs, lens)})"""
+    import json
+    src = os.path.join(GOLDEN, "indeledge")
+    with open(os.path.join(src, "cases.json")) as f:
+        cases = json.load(f)
+    sfx = {"indeledge": gunzip_to(os.path.join(src, "genome.sfx.gz"), os.path.join(dst, "indeledge.sfx")),
+           "repeat": gunzip_to(os.path.join(GOLDEN, "repeat", "genome.sfx.gz"), os.path.join(dst, "repeat.sfx"))}
+    reads = {n: read_fasta_reads(os.path.join(src, n)) for n in ("reads.fa.gz", "reads_repeat.fa.gz")}
+    return cases, sfx, reads
+
+
+def read_sfx(path):
+    """(bases incl. EOS, suffix array, [(name, seq_len)]) of a one-block .sfx file with 4-byte elements (the layout write_sfx writes; a
+    .gz is read through gzip)"""
+    import struct
+    with (gzip.open if path.endswith(".gz") else open)(path, "rb") as f:
+        raw = f.read()
+    _, n_ent, n, el = struct.unpack_from("<IIQI", raw, 1224)
+    assert el == 4
+    seq = np.frombuffer(raw, dtype=np.uint8, count=n, offset=1244).copy()
+    sa = np.frombuffer(raw, dtype="<u4", count=n, offset=1244 + n).copy()
+    at = 1244 + 5 * n + 8
+    ents = []
+    for i in range(n_ent):
+        rec = raw[at + 111 * i:at + 111 * (i + 1)]
+        ents.append((rec[8:89].split(b"\0")[0].decode(), struct.unpack_from("<I", rec, 91)[0]))
+    return seq, sa, ents
+
+
+def rewrite_sfx_5byte(src, dst, dataset="wide"):
+    """the sequences and suffix array of a .sfx file (one block, 4-byte elements) written again with 5-byte elements"""
+    seq, sa, ents = read_sfx(src)
+    write_sfx(dst, dataset, ents, seq, sa.astype(np.uint64), el_size=5)
+    return dst

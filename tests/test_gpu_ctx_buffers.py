@@ -9,7 +9,8 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_iv_records import COMP, _batch, _cut_reads, _read_sfx
+import helpers
+from test_gpu_iv_records import COMP, _batch, _cut_reads
 from test_gpu_parity import assert_hits_equal
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def _bk():
 @pytest.fixture(scope="module")
 def repeat(golden_tmp):
     path = os.path.join(golden_tmp["repeat"], "genome.sfx")
-    seq, sa, _ = _read_sfx(path)
+    seq, sa, _ = helpers.read_sfx(path)
     return {"sfx": path, "seq": seq, "sa": sa}
 
 

@@ -4,7 +4,6 @@ included - and slots of cores a read does not have must never be looked at.  "iv
 use with ones in front of its search: a slot read without having been written then changes results and counters.  Everything runs on
 the `repeat` golden index and is compared with the CPU oracle, or with the same batch on a fresh context."""
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -24,25 +23,10 @@ def _bk():
     return biokanga_amd
 
 
-def _read_sfx(path):
-    """(bases incl. EOS, suffix array, [(name, seq_len)]) of a one-block .sfx file with 4-byte elements (the layout helpers.write_sfx writes)"""
-    raw = open(path, "rb").read()
-    _, n_ent, n, el = struct.unpack_from("<IIQI", raw, 1224)
-    assert el == 4
-    seq = np.frombuffer(raw, dtype=np.uint8, count=n, offset=1244).copy()
-    sa = np.frombuffer(raw, dtype="<u4", count=n, offset=1244 + n).copy()
-    at = 1244 + 5 * n + 8
-    ents = []
-    for i in range(n_ent):
-        rec = raw[at + 111 * i:at + 111 * (i + 1)]
-        ents.append((rec[8:89].split(b"\0")[0].decode(), struct.unpack_from("<I", rec, 91)[0]))
-    return seq, sa, ents
-
-
 @pytest.fixture(scope="module")
 def repeat(golden_tmp):
     path = os.path.join(golden_tmp["repeat"], "genome.sfx")
-    seq, sa, ents = _read_sfx(path)
+    seq, sa, ents = helpers.read_sfx(path)
     return {"sfx": path, "seq": seq, "sa": sa, "ents": ents}
 
 

@@ -11,7 +11,8 @@ import re
 import numpy as np
 import pytest
 
-from test_gpu_iv_records import _cut_reads, _read_sfx
+import helpers
+from test_gpu_iv_records import _cut_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ def _bk():
 @pytest.fixture(scope="module")
 def repeat(golden_tmp):
     path = os.path.join(golden_tmp["repeat"], "genome.sfx")
-    seq, _, _ = _read_sfx(path)
+    seq, _, _ = helpers.read_sfx(path)
     return {"sfx": path, "seq": seq}
 
 

@@ -144,8 +144,7 @@ def test_bad_parameters_are_refused(files, requests):
 
 
 def test_index_of_5_byte_elements(files, genome, requests, expected, tmp_path):
-    from test_gpu_iv_records import _read_sfx
-    seq, sa, ents = _read_sfx(files["genome.sfx"])
+    seq, sa, ents = helpers.read_sfx(files["genome.sfx"])
     path = str(tmp_path / "genome5.sfx")
     helpers.write_sfx(path, "siteprefs5", ents, seq, sa.astype(np.uint64), el_size=5)
     with _aligner(path) as al:
